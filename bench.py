@@ -11,7 +11,11 @@ pair: 1x extract_stereo + 1x device match, src/StereoFrontEnd.cc:14,33).  The de
 chunk different images) makes 20 timed steps last > 2 s.  Independent pairs shard across ranks with no data-path
 collective (weak scaling: every rank runs its own batch); `value` = all pairs of all ranks / max-over-ranks wall time.
 
-Prints ONE JSON line with the driver's fields plus
+A plain run sets up, warms up, times the steps and prints ONE JSON line with the driver's fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step = wall milliseconds of one timed step) and the workload's config.
+--dump-outputs DIR also writes the outputs of the last step's calls as .npy files (dump_outputs below); the inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
+--full adds everything below, all measured after the timed region (and the power poller during it):
   self_check    : after the timed region, one chunk's batched outputs against the per-pair path (keypoints bit-identical,
                   descriptors <= 1 ulp, matches within the matcher bars); the process exits non-zero if it fails
   roofline      : the dominant kernel (conv1a+conv1b+pool, 36 % of the pair's FLOPs); `traffic` = HBM bytes per launch measured IN THIS RUN
@@ -32,7 +36,9 @@ Prints ONE JSON line with the driver's fields plus
                   cap, so joules per pair is the unit kernel work is priced in; `joules_per_launch` on every roofline_mfma / roofline_hbm row
                   comes from a >= 0.6 s loop of that stage under the same poller (rank 0; --no-power switches it off)
   cpu_baseline  : the CPU oracle (kind "port") on this box's host cores, bounded sample, rank 0 at N = 1 only.
---headline-only runs the warm-up and the timed steps and nothing else (profiling passes: every launch is a headline launch).
+  scale_extras  : N > 1 only: per-rank rates and the RCCL exchange (scale_extras below).
+--full --headline-only runs the power poller, the warm-up and the timed steps and nothing else (profiling passes: every launch is a
+headline launch); a run without --full does the same without the power poller.
 """
 import argparse
 import ctypes as C
@@ -298,6 +304,41 @@ def make_chunks(torch, base, chunks):
     return out
 
 
+DUMP_BUDGET = 64 << 20      # bytes of all --dump-outputs files together
+DUMP_DESC_ROWS = 4096       # descriptor rows kept per call (a seeded sample of the 2P x max_kp rows)
+
+
+def dump_outputs(torch, np, fe, chunks, stream, d):
+    """--dump-outputs DIR: what a caller of the timed path receives from the calls of one step, one leading axis entry per call
+    (the step's chunks in order):
+      kp [calls, 2P, K, 3] f32, n [calls, 2P] (i32 as f64), matches0 [calls, P, K] (i32 as f64), mscores0 [calls, P, K] f32,
+      desc_sample [calls, R, 256] (f16 as f32) = the rows desc_sample_rows [R] (flat image * K + keypoint, seeded) of desc [2P, K, 256].
+    Entries past an image's keypoint count (a pair's left count for matches0 / mscores0) hold no result and are written as 0.
+    The output buffers keep only the last call, so the step runs once more after the timed region, on the same inputs and handles,
+    and every call's outputs are copied (repeated calls on one input are bit-identical: scripts/dev/soak_determinism.py)."""
+    P, B, K, CH = fe.pairs, fe.kp.shape[0], fe.kp.shape[1], len(chunks)
+    full = CH * (B * K * 3 * 4 + B * 8 + P * K * (8 + 4))
+    rows = min(B * K, DUMP_DESC_ROWS, (DUMP_BUDGET - full) // (CH * 256 * 4 + 8))
+    if rows < 1:
+        raise SystemExit(f"--dump-outputs: {CH} calls of {P} pairs at {K} keypoints exceed the {DUMP_BUDGET >> 20} MB dump")
+    sel = torch.from_numpy(np.sort(np.random.default_rng(0).choice(B * K, size=rows, replace=False))).cuda()
+    acc = {k: [] for k in ("kp", "n", "matches0", "mscores0", "desc_sample")}
+    for x in chunks:
+        fe.run(x, stream)
+        torch.cuda.synchronize()
+        valid = torch.arange(K, device="cuda")[None, :] < fe.n[:, None].long()          # [2P, K]
+        acc["kp"].append((fe.kp * valid[..., None]).cpu())
+        acc["n"].append(fe.n.cpu())
+        acc["matches0"].append(torch.where(valid[0::2], fe.matches0, 0).cpu())
+        acc["mscores0"].append(torch.where(valid[0::2], fe.mscores0, 0).cpu())
+        acc["desc_sample"].append((fe.desc.float() * valid[..., None]).reshape(B * K, 256).index_select(0, sel).cpu())
+    os.makedirs(d, exist_ok=True)
+    for k, v in acc.items():
+        a = torch.stack(v).numpy()
+        np.save(os.path.join(d, k + ".npy"), a.astype(np.float64 if a.dtype == np.int32 else np.float32))
+    np.save(os.path.join(d, "desc_sample_rows.npy"), sel.cpu().numpy().astype(np.float64))
+
+
 def main():
     import faulthandler
 
@@ -309,8 +350,13 @@ def main():
     ap.add_argument("--pairs", type=int, default=64, help="stereo pairs per library call (per GPU)")
     ap.add_argument("--chunks", type=int, default=8, help="library calls per step: a step processes chunks x pairs pairs resident in HBM")
     ap.add_argument("--max-kp", type=int, default=600, help="superpoint.max_keypoints (600 = the KITTI YAML)")
+    ap.add_argument("--full", action="store_true", help="everything next to the headline: power telemetry, self_check, rooflines, "
+                                                       "per-stage figures, n1024, end_to_end, latency, eigenplaces, cpu_baseline, "
+                                                       "scale_extras (N > 1).  Without it a run is set-up, warm-up, timed steps and the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last step's calls as DIR/<name>.npy (float32 / float64, < 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--headline-only", action="store_true", help="warm-up + timed steps only (profiling passes)")
+    ap.add_argument("--headline-only", action="store_true", help="with --full: warm-up + timed steps only (profiling passes)")
     ap.add_argument("--measure-traffic", dest="measure_traffic", action="store_true", default=True,
                     help="(default) measure roofline.traffic IN THIS RUN: two rocprofv3 --pmc passes over `bench.py --headline-only` as child processes "
                          "(scripts/pmc_traffic.sh, ~20-60 s, 150 s limit; needs rocprofv3 on PATH).  On any failure the figure is READ from "
@@ -378,7 +424,7 @@ def main():
     # socket power / shader clock of rank 0's GPU, sampled by a thread while the steps run (reads of a sysfs file; the timed region itself
     # is untouched: same calls, same synchronisation)
     poller = None
-    if rank == 0 and not args.no_power:
+    if rank == 0 and args.full and not args.no_power:
         sys.path.insert(0, os.path.join(ROOT, "scripts"))
         import power_telemetry
 
@@ -403,10 +449,11 @@ def main():
     dt_own = dt
     if use_dist:
         dt = all_reduce_max_seconds(dt)   # the slowest rank defines the step time
-    scale = scale_extras(torch, dist, rank, world, backend, dt_own, P * CH * args.steps) if (use_dist and world > 1) else None
-
     n_kp = fe.n.cpu().numpy()
     n_match = int((fe.matches0.cpu().numpy() >= 0).sum())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, np, fe, chunks, stream, args.dump_outputs)
+    scale = scale_extras(torch, dist, rank, world, backend, dt_own, P * CH * args.steps) if (args.full and use_dist and world > 1) else None
     total_pairs = world * P * CH * args.steps
     value = total_pairs / dt
     flops_pair = 2 * sp_flops_per_image(H, W) + lg_flops_per_pair(args.max_kp)
@@ -450,7 +497,7 @@ def main():
                 out["power"] = blk
             else:
                 out["power"] = {"error": "no power telemetry backend answered on this box (sysfs hwmon, librocm_smi64, rocm-smi)"}
-        if not args.headline_only:
+        if args.full and not args.headline_only:
             out["self_check"] = self_check(torch, np, fe, chunks[CH - 1], stream, wdir, args.max_kp)
             extras(out, args, torch, np, L, sp, lg, fe, chunks, base, stream, wdir, world, spw, lgw, pairs, poller)
         if poller is not None:
@@ -460,7 +507,7 @@ def main():
                     json.dump({"backend": poller.backend.name, "cap_W": poller.cap_w, "timed_region": [tm0, tm1], "pairs_timed": P * CH * args.steps,
                                "samples": [[round(t, 4), w, c] for (t, w, c) in poller.samples]}, f)
         print(json.dumps(out), flush=True)
-        if not args.headline_only and not out["self_check"]["ok"]:
+        if "self_check" in out and not out["self_check"]["ok"]:
             sp.close(); lg.close()
             raise SystemExit("bench.py self-check FAILED: the batched call and the per-pair path disagree: " + json.dumps(out["self_check"]))
     sp.close(); lg.close()

@@ -7,7 +7,7 @@ tail -25 $O/pytest_fuse2.log
 for i in 1 2; do
 for mode in split fused; do
   echo "== $mode"
-  SSHIP_DEV_LIBRARY=$DEV SUPERSLAM_HIP_CONV2=$mode timeout 300 python bench.py --library $DEV --headline-only --steps 6 --warmup 2 2>&1 | tail -1 | python -c "
+  SSHIP_DEV_LIBRARY=$DEV SUPERSLAM_HIP_CONV2=$mode timeout 300 python bench.py --full --library $DEV --headline-only --steps 6 --warmup 2 2>&1 | tail -1 | python -c "
 import sys, json
 b = json.loads(sys.stdin.read()); print(json.dumps({k: b.get(k) for k in ('value', 'ms_per_step', 'power')}))"
 done

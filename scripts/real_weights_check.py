@@ -20,7 +20,7 @@ happen the first time the real files are on a machine, in the order that localis
   python scripts/real_weights_check.py --superpoint ~/weights/superpoint_v1.pth --lightglue ~/weights/superpoint_lightglue.pth
   python scripts/real_weights_check.py --seeded          # the seeded test weights, saved in the published layouts first (CI)
   SUPERSLAM_SP_WEIGHTS=... SUPERSLAM_LG_WEIGHTS=... python scripts/real_weights_check.py --from-env
-The last form is what `__graft_entry__.smoke()` and `bench.py` run (verdict_from_env below) when the two variables are set: the first
+The last form is what `__graft_entry__.smoke()` and `bench.py --full` run (verdict_from_env below) when the two variables are set: the first
 machine that has the files gets the verdict inside the records the driver already collects, with no extra step.
 
 Exit status 0 = every executed step passed (skipped steps are listed under "skipped"), 1 = a step failed, 2 = bad arguments.

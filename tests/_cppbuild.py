@@ -13,8 +13,10 @@ OUTDIR = os.path.join(ROOT, "tests", "_build")
 SAN_FLAGS = ["-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-fno-sanitize-recover=undefined", "-g"]
 
 
-def cpp_binary(name, srcs, deps=(), includes=(), link_lib=True, extra=(), opt="-O1", sanitize=False, force=False, outdir=None):
-    """Compile `srcs` into <outdir>/<name> when any of srcs + deps is newer; returns the path."""
+def cpp_binary(name, srcs, deps=(), includes=(), link_lib=True, extra=(), opt="-O1", sanitize=False, force=False, outdir=None,
+               relocatable=False):
+    """Compile `srcs` into <outdir>/<name> when any of srcs + deps is newer; returns the path.  relocatable=True: the library is
+    found relative to the binary ($ORIGIN), for binaries that are built once and run from another checkout of the tree."""
     outdir = outdir or OUTDIR
     os.makedirs(outdir, exist_ok=True)
     out = os.path.join(outdir, name + ("_san" if sanitize else ""))
@@ -23,7 +25,8 @@ def cpp_binary(name, srcs, deps=(), includes=(), link_lib=True, extra=(), opt="-
         cmd = ["g++", "-std=c++17", opt, "-Wall", *(SAN_FLAGS if sanitize else []), *["-I" + i for i in includes],
                "-I" + os.path.join(ROOT, "include"), *srcs, "-o", out]
         if link_lib:
-            cmd += ["-L" + LIBDIR, "-lsuperslam_hip", "-Wl,-rpath," + LIBDIR, "-Wl,-rpath,/opt/rocm/lib"]
+            libdir = os.path.join("$ORIGIN", os.path.relpath(LIBDIR, outdir)) if relocatable else LIBDIR
+            cmd += ["-L" + LIBDIR, "-lsuperslam_hip", "-Wl,-rpath," + libdir, "-Wl,-rpath,/opt/rocm/lib"]
         cmd += list(extra)
         subprocess.check_call(cmd)
     return out

@@ -1,36 +1,28 @@
 """The reference-side binding is COMPILED (round-1 VERDICT "What's missing" 5): integration/reference_side/{SuperPoint,LightGlue}.h
-+ the reference's own include/*.h and src/StereoFrontEnd.cc (read from /root/reference at build time, never copied) against the
-stand-in OpenCV / GTSAM / spdlog declarations of tests/cpp/shim.  The binary is built here (CPU, needs /root/reference) and by
-__graft_entry__.build(); it travels to the GPU box, where the reference tree does not exist, as a build product."""
++ the reference's own include/*.h and src/StereoFrontEnd.cc (read from the reference tree at build time, never copied) against the
+stand-in OpenCV / GTSAM / spdlog declarations of tests/cpp/shim.  __graft_entry__.build() builds the binary into oracle/_ref/ by the recipe
+oracle/ref_binding.py wherever the reference tree exists; the tests here run that build product, also on machines without the tree."""
 import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-BIN = os.path.join(ROOT, "tests", "_build", "test_reference_binding")   # test artefact: outside the package directory (git-ignored, travels to the GPU box)
+from oracle import ref_binding
+
+BIN = ref_binding.path()
 
 
 def build(force=False, sanitize=False):
-    from _cppbuild import cpp_binary
-
-    srcs = [os.path.join(ROOT, "tests", "cpp", "test_reference_binding.cc"), os.path.join(REF, "src", "StereoFrontEnd.cc"),
-            os.path.join(REF, "src", "PlaceRecognizer.cc")]   # the adapter holds the reference's own CosineDescriptorIndex
-    deps = srcs + [os.path.join(ROOT, "integration", "reference_side", f) for f in ("SuperPoint.h", "LightGlue.h", "EigenPlaces.h")] + \
-        [os.path.join(ROOT, "include", "superslam_hip", "frontend.hpp"), os.path.join(ROOT, "tests", "cpp", "shim", "opencv4", "opencv2", "core.hpp")]
-    return cpp_binary("test_reference_binding", srcs, deps=deps, force=force, sanitize=sanitize, extra=["-Wno-unused-function"],
-                      includes=[os.path.join(ROOT, "integration", "reference_side"),   # SuperPoint.h / LightGlue.h resolve to the adapters
-                                os.path.join(ROOT, "tests", "cpp", "shim"),
-                                os.path.join(REF, "include")])                          # everything else: the reference's own headers
+    return ref_binding.build(force=force, sanitize=sanitize)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists only in the build container")
+@pytest.mark.skipif(not (os.path.exists(BIN) or ref_binding.available()),
+                    reason="oracle/_ref/test_reference_binding was not built: build() makes it where the reference tree exists")
 def test_binding_compiles_against_the_reference_headers_and_passes_cpu_cases():
     from superslam_amd import _lib
 
     _lib.lib()
-    out = subprocess.run([build()], capture_output=True, text=True, timeout=120)
+    out = subprocess.run([build() if ref_binding.available() else BIN], capture_output=True, text=True, timeout=120)
     print(out.stdout, out.stderr[-2000:])
     assert out.returncode == 0, out.stdout + out.stderr
     assert "all checks passed (cpu)" in out.stdout
@@ -46,9 +38,7 @@ def test_binding_compiles_against_the_reference_headers_and_passes_cpu_cases():
 @pytest.mark.gpu
 def test_binding_runs_the_reference_front_end_on_the_gpu(weights_dir):
     if not os.path.exists(BIN):
-        if not os.path.isdir(REF):
-            pytest.fail("tests/_build/test_reference_binding is missing: __graft_entry__.build() produces it in the build container")
-        build()
+        pytest.fail("oracle/_ref/test_reference_binding is missing: __graft_entry__.build() produces it where the reference tree exists")
     from superslam_amd.weights import make_eigenplaces_weights, save_safetensors
 
     ep_path = os.path.join(weights_dir["dir"], "eigenplaces.safetensors")

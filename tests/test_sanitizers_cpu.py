@@ -10,8 +10,9 @@ import zlib
 import numpy as np
 import pytest
 
+from oracle import ref_binding
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 
 def _run(cmd, **kw):
@@ -67,12 +68,13 @@ def test_image_decoders_clean_under_asan_ubsan(tmp_path):
     assert _run([binp, str(tmp_path / "short.pgm")]).returncode == 1
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists only in the build container")
+@pytest.mark.skipif(not (os.path.exists(ref_binding.path(sanitize=True)) or ref_binding.available()),
+                    reason="oracle/_ref/test_reference_binding_san was not built: build() makes it where the reference tree exists")
 def test_reference_binding_clean_under_asan_ubsan():
-    """The reference's own src/StereoFrontEnd.cc + PlaceRecognizer.cc on the adapters, CPU cases, sanitized."""
-    import test_reference_binding as B
+    """The reference's own src/StereoFrontEnd.cc + PlaceRecognizer.cc on the adapters, CPU cases, sanitized (oracle/ref_binding.py)."""
     from superslam_amd import _lib
 
     _lib.lib()
-    out = _run([B.build(sanitize=True)], text=True)
+    binp = ref_binding.build(sanitize=True) if ref_binding.available() else ref_binding.path(sanitize=True)
+    out = _run([binp], text=True)
     assert out.returncode == 0 and "all checks passed (cpu)" in out.stdout, out.stdout[-2000:] + out.stderr[-2000:]
