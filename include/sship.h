@@ -240,6 +240,21 @@ int sship_lg_match_host(sship_lg* lg, const float* kp0, int kp_stride0, int n0, 
  * [pairs, max_kp]; rows >= n are -1 / 0. */
 int sship_lg_match_batch_device(sship_lg* lg, const float* kp_dev, const int* n_dev, const void* desc_dev,
                                 int pairs, int32_t* matches0_dev, float* mscores0_dev, void* stream);
+/* Adaptive depth (upstream LightGlue's depth_confidence; the reference has no counterpart: its ONNX export turns it off).
+ * Per handle, OFF by default; it applies to every call enqueued after it returns (one call in flight per handle, as everywhere here),
+ * through every entry point: sship_lg_match_device / _match_host / _match_batch_device and sship_frontend_batch_device.
+ * With depth_confidence = d in (0, 1] each pair p of a call is decided on its own:
+ *   after layer i (i = 0..7, self and cross block of both images), c = sigmoid(w_i . x + b_i) for every valid token of both images,
+ *   (w_i, b_i) = token_confidence.{i}.token.0.{weight,bias}, x = the residual stream after layer i; thr_i = fp32(clip(0.8 + 0.1 exp(-4 i / 9), 0, 1)).
+ *   The pair stops after layer i if  1 - count(c < thr_i) / (n0 + n1) > d  (fp32, this form; n0 + n1 = 0 never stops) and is matched with
+ *   log_assignment[i] (final_proj and matchability) on x after layer i; a pair that never stops runs nine layers and uses log_assignment[8].
+ *   The filter (threshold 0.1, mutual check) is unchanged.  A pair's result does not depend on the other pairs of the call.
+ * sship_lg_set_depth_confidence: d <= 0 turns it off (today's path, bit for bit); NaN or d > 1 -> SSHIP_ERR_INVALID; d > 0 with weights that
+ *   lack any of token_confidence.{0..7} or log_assignment.{0..7} -> SSHIP_ERR_INVALID (the handle keeps its previous setting).
+ * sship_lg_layers_run: layers run by each of the first `pairs` pairs of the last call (i + 1 for a pair that stopped after layer i, 9
+ *   otherwise; upstream's `stop`), device-synchronising like sship_lg_debug_read.  With the option off every pair reports the layers run. */
+int sship_lg_set_depth_confidence(sship_lg* lg, float depth_confidence);
+int sship_lg_layers_run(sship_lg* lg, int* out_host, int pairs);
 /* Test-only introspection of the matcher (no reference counterpart; used by the parity suite to compare the internals
  * with the oracle layer by layer - the product never calls these).
  * sship_lg_debug_set_layers: the NEXT match call on this handle (one-shot) runs only the first n_layers (1..9) transformer

@@ -279,9 +279,28 @@ public:
     if (sship_lg_create(engine_->weights, image_width_, image_height_, max_keypoints_, 1, &lg_) != SSHIP_OK) {
       last_error_ = sship_last_error(); lg_ = nullptr; return false;
     }
+    if (depth_confidence_ > 0.f && sship_lg_set_depth_confidence(lg_, depth_confidence_) != SSHIP_OK) {
+      last_error_ = sship_last_error(); sship_lg_destroy(lg_); lg_ = nullptr; return false;
+    }
     return true;
   }
   std::shared_ptr<LightGlueEngine> shared_engine() const { return engine_; }
+
+  // Adaptive depth (upstream LightGlue's depth_confidence; include/sship.h): <= 0 off (the default), (0, 1] on.  Before initialize()
+  // the value is kept and applied there; after it, it applies to the next match.  false (last_error()) for NaN, > 1, or weights
+  // without the token-confidence / early assignment heads.
+  bool set_depth_confidence(float depth_confidence) {
+    if (lg_ && sship_lg_set_depth_confidence(lg_, depth_confidence) != SSHIP_OK) { last_error_ = sship_last_error(); return false; }
+    if (!lg_ && !(depth_confidence <= 1.f)) { last_error_ = "set_depth_confidence: depth_confidence must be <= 1"; return false; }
+    depth_confidence_ = depth_confidence;
+    return true;
+  }
+  // layers the last match ran (9 = all; i + 1 = stopped after layer i); 0 before the first match
+  int layers_run() {
+    int n = 0;
+    if (!lg_ || sship_lg_layers_run(lg_, &n, 1) != SSHIP_OK) return 0;
+    return n;
+  }
 
   // 5-argument form (src/LightGlue.cc:285-324): false for an uninitialised matcher or an empty set.
   bool match(const std::vector<KeyPoint>& kp0, const HostDescriptors& d0, const std::vector<KeyPoint>& kp1,
@@ -339,6 +358,7 @@ private:
   int image_width_, image_height_, max_keypoints_;
   std::shared_ptr<LightGlueEngine> engine_;
   sship_lg* lg_ = nullptr;
+  float depth_confidence_ = -1.f;
   std::string last_error_;
 };
 typedef std::shared_ptr<LightGlue> LightGluePtr;

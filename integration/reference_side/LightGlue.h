@@ -28,6 +28,13 @@ public:
     return ok;
   }
   std::shared_ptr<LightGlueEngine> shared_engine() const { return impl_.shared_engine(); }
+  // Upstream LightGlue's adaptive depth (no counterpart in the TensorRT runner, whose export turns it off): <= 0 off (default), (0, 1] on.
+  bool set_depth_confidence(float depth_confidence) {
+    const bool ok = impl_.set_depth_confidence(depth_confidence);
+    if (!ok) SLOG_ERROR("LightGlue(HIP): {}", impl_.last_error());
+    return ok;
+  }
+  int layers_run() { return impl_.layers_run(); }
 
   bool match(const std::vector<cv::KeyPoint>& kp0, const cv::Mat& d0, const std::vector<cv::KeyPoint>& kp1,
              const cv::Mat& d1, MatchResult& result) {

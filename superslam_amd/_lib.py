@@ -89,6 +89,8 @@ _SIGS = {
     "sship_lg_match_device": (ip, [vp, vp, ip, ip, vp, vp, ip, ip, vp, vp, vp]),
     "sship_lg_match_host": (ip, [vp, vp, ip, ip, vp, vp, ip, ip, vp, vp, vp]),
     "sship_lg_match_batch_device": (ip, [vp, vp, vp, vp, ip, vp, vp, vp]),
+    "sship_lg_set_depth_confidence": (ip, [vp, fp]),
+    "sship_lg_layers_run": (ip, [vp, vp, ip]),
     "sship_lg_debug_set_layers": (ip, [vp, ip]),
     "sship_lg_debug_read": (ip, [vp, ip, ip, ip, ip, vp]),
     "sship_filter_matches": (ip, [vp, vp, ip, vp, vp, vp]),

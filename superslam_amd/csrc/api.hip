@@ -1287,6 +1287,17 @@ struct sship_lg_weights {
   float* match_w = nullptr;
   float match_b = 0.f;
   float* wr = nullptr;
+  // adaptive depth (sship_lg_set_depth_confidence): token_confidence[0..7] and log_assignment[0..7], when the file holds them.  The
+  // nine assignment heads sit at a fixed stride (head h at h * 65536) so that a kernel selects one by index; head 8 is the packed final_t
+  // above and is not used from here.
+  bool has_depth = false;
+  std::string depth_missing;   // the first missing tensor (the error text of sship_lg_set_depth_confidence)
+  float* tc_w = nullptr;       // [8][256]
+  float tc_b[8] = {};
+  float* head_wt = nullptr;    // [9][256 in][256 out]: final_proj^T, scaled by 256^-0.25 like final_t
+  float* head_b = nullptr;     // [9][256], scaled likewise
+  float* head_mw = nullptr;    // [9][256] matchability weights
+  float* head_mb = nullptr;    // [9]
 };
 static void lg_weights_free(sship_lg_weights* w) {
   for (int i = 0; i < kLgLayers; ++i) {
@@ -1295,6 +1306,7 @@ static void lg_weights_free(sship_lg_weights* w) {
     for (float* p : {w->ln_g_s[i], w->ln_b_s[i], w->ln_g_c[i], w->ln_b_c[i]}) if (p) (void)hipFree(p);
   }
   free_conv(w->final_t);
+  for (float* p : {w->tc_w, w->head_wt, w->head_b, w->head_mw, w->head_mb}) if (p) (void)hipFree(p);
   if (w->match_w) (void)hipFree(w->match_w);
   if (w->wr) (void)hipFree(w->wr);
   delete w;
@@ -1432,6 +1444,46 @@ extern "C" int sship_lg_weights_load(const char* path, sship_lg_weights** out) {
     if (!wr) return bail(SSHIP_ERR_IO, err);
     if ((rc = upload_floats(wr->data.data(), 64, &w->wr))) return bail(rc, g_err);
   }
+  {
+    // adaptive depth's heads: optional (a file without them loads as before; sship_lg_set_depth_confidence refuses to turn it on)
+    auto opt = [&](const std::string& name, std::initializer_list<int64_t> shape) -> const Tensor* {
+      auto it = sd.find(name);
+      if (it != sd.end() && it->second.shape == std::vector<int64_t>(shape)) return &it->second;
+      if (w->depth_missing.empty()) w->depth_missing = name;
+      return nullptr;
+    };
+    std::vector<float> tcw(8 * 256), hwt((size_t)9 * 65536, 0.f), hb(9 * 256, 0.f), hmw(9 * 256, 0.f), hmb(9, 0.f);
+    const float sc = fp_scale[0];
+    bool ok = true;
+    for (int i = 0; i < kLgLayers - 1 && ok; ++i) {
+      const std::string pt = "token_confidence." + std::to_string(i) + ".token.0.";
+      const std::string pa = "log_assignment." + std::to_string(i) + ".";
+      const Tensor* tw = opt(pt + "weight", {1, 256});
+      const Tensor* tb = tw ? opt(pt + "bias", {1}) : nullptr;
+      const Tensor* fw = tb ? opt(pa + "final_proj.weight", {256, 256}) : nullptr;
+      const Tensor* fb = fw ? opt(pa + "final_proj.bias", {256}) : nullptr;
+      const Tensor* mw = fb ? opt(pa + "matchability.weight", {1, 256}) : nullptr;
+      const Tensor* mb = mw ? opt(pa + "matchability.bias", {1}) : nullptr;
+      if (!mb) { ok = false; break; }
+      memcpy(tcw.data() + i * 256, tw->data.data(), 256 * 4);
+      w->tc_b[i] = tb->data[0];
+      for (int o = 0; o < 256; ++o) {
+        for (int k = 0; k < 256; ++k) hwt[(size_t)i * 65536 + (size_t)k * 256 + o] = fw->data[(size_t)o * 256 + k] * sc;
+        hb[i * 256 + o] = fb->data[o] * sc;
+      }
+      memcpy(hmw.data() + i * 256, mw->data.data(), 256 * 4);
+      hmb[i] = mb->data[0];
+    }
+    if (ok) {
+      int rc = 0;
+      if ((rc = upload_floats(tcw.data(), tcw.size(), &w->tc_w)) || (rc = upload_floats(hwt.data(), hwt.size(), &w->head_wt)) ||
+          (rc = upload_floats(hb.data(), hb.size(), &w->head_b)) || (rc = upload_floats(hmw.data(), hmw.size(), &w->head_mw)) ||
+          (rc = upload_floats(hmb.data(), hmb.size(), &w->head_mb)))
+        return bail(rc, g_err);
+      w->has_depth = true;
+      w->depth_missing.clear();
+    }
+  }
   *out = w;
   return SSHIP_OK;
 }
@@ -1459,6 +1511,11 @@ struct sship_lg {
   DevBuf kpn;     // normalised keypoints [S*NP][2] f32 (src/LightGlue.cc:241-251 on the device; read back by sship_lg_debug_read)
   int debug_layers = kLgLayers;  // sship_lg_debug_set_layers
   int last_pairs = 0;
+  // adaptive depth (sship_lg_set_depth_confidence): <= 0 = off.  dep: the per-call state of include/.../kernels.h LgDepth for every pair
+  float depth_conf = -1.f;
+  bool last_adaptive = false;
+  int last_layers = kLgLayers;
+  DevBuf dep;
   PinBuf h_kp, h_lens, h_m0, h_ms0, h_desc;
   // throughput batches run their transformer layers as two half-batches on two streams (lg_forward): the second stream and the
   // fork / join events
@@ -1467,6 +1524,8 @@ struct sship_lg {
   hipEvent_t ev_fork = nullptr, ev_join[kAux] = {nullptr, nullptr, nullptr};
 };
 
+// Adaptive depth state layout in sship_lg::dep (ints): cnt [P][8] | layers_run [P] | lens_live [2P] | live [P + kAux + 1] | tickets [kAux + 1]
+static size_t lg_dep_ints(int P) { return (size_t)P * 8 + P + 2 * (size_t)P + P + sship_lg::kAux + 1 + sship_lg::kAux + 1; }
 extern "C" int sship_lg_create(sship_lg_weights* w, int image_w, int image_h, int max_kp, int max_pairs, sship_lg** out) {
   bind_thread();
   if (!w || !out || image_w <= 0 || image_h <= 0) return fail(SSHIP_ERR_INVALID, "lg_create: bad arguments");
@@ -1500,6 +1559,7 @@ extern "C" int sship_lg_create(sship_lg_weights* w, int image_w, int image_h, in
   SSHIP_HIP_CHECK(lg->h_m0.ensure((size_t)max_kp * 4));
   SSHIP_HIP_CHECK(lg->h_ms0.ensure((size_t)max_kp * 4));
   SSHIP_HIP_CHECK(lg->h_desc.ensure(2 * (size_t)max_kp * 256 * 2));
+  SSHIP_HIP_CHECK(lg->dep.ensure(lg_dep_ints(max_pairs) * 4));
   // q/k/vt/ctx of padded tokens must stay finite: start from zeros (prep rewrites x every call).
   SSHIP_HIP_CHECK(hipMemset(lg->q.p, 0, lg->q.bytes));
   SSHIP_HIP_CHECK(hipMemset(lg->k.p, 0, lg->k.bytes));
@@ -1585,6 +1645,47 @@ extern "C" int sship_lg_debug_read(sship_lg* lg, int what, int index, int rows, 
   }
 }
 
+// the state of launch group `part` (pairs [p0, p0 + np))
+static LgDepth lg_depth_state(sship_lg* lg, int p0, int part) {
+  const int P = lg->max_pairs;
+  int* b = lg->dep.as<int>();
+  int* cnt = b;
+  int* lr = cnt + (size_t)P * 8;
+  int* ll = lr + P;
+  int* live = ll + 2 * (size_t)P;
+  unsigned* tk = reinterpret_cast<unsigned*>(live + P + sship_lg::kAux + 1);
+  // live lists of consecutive groups: [p0 + part, p0 + part + np + 1) never overlap (p0 grows by np, part by 1)
+  return LgDepth{cnt + (size_t)p0 * 8, lr + p0, ll + 2 * (size_t)p0, live + p0 + part, tk + part};
+}
+// thr_i = clip(0.8 + 0.1 exp(-4 i / 9), 0, 1) (upstream LightGlue.confidence_threshold, n_layers = 9), rounded to fp32
+static float lg_depth_threshold(int i) {
+  const double t = 0.8 + 0.1 * std::exp(-4.0 * i / (double)kLgLayers);
+  return (float)std::min(1.0, std::max(0.0, t));
+}
+extern "C" int sship_lg_set_depth_confidence(sship_lg* lg, float depth_confidence) {
+  bind_thread();
+  if (!lg) return fail(SSHIP_ERR_INVALID, "lg_set_depth_confidence: null handle");
+  if (std::isnan(depth_confidence) || depth_confidence > 1.f)
+    return fail(SSHIP_ERR_INVALID, "lg_set_depth_confidence: depth_confidence must be <= 1 (<= 0 turns adaptive depth off)");
+  if (depth_confidence > 0.f && !lg->w->has_depth)
+    return fail(SSHIP_ERR_INVALID, "lg_set_depth_confidence: the weights hold no token_confidence / early log_assignment heads (missing '" +
+                                       lg->w->depth_missing + "'); adaptive depth needs token_confidence.{0..7} and log_assignment.{0..7}");
+  lg->depth_conf = depth_confidence > 0.f ? depth_confidence : -1.f;
+  return SSHIP_OK;
+}
+extern "C" int sship_lg_layers_run(sship_lg* lg, int* out_host, int pairs) {
+  bind_thread();
+  if (!lg || !out_host || pairs <= 0) return fail(SSHIP_ERR_INVALID, "lg_layers_run: bad arguments");
+  if (pairs > lg->last_pairs) return fail(SSHIP_ERR_INVALID, "lg_layers_run: pairs exceeds the pairs of the last call");
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());
+  if (!lg->last_adaptive) {
+    for (int p = 0; p < pairs; ++p) out_host[p] = lg->last_layers;
+    return SSHIP_OK;
+  }
+  SSHIP_HIP_CHECK(hipMemcpy(out_host, lg->dep.as<int>() + (size_t)lg->max_pairs * 8, (size_t)pairs * 4, hipMemcpyDeviceToHost));
+  return SSHIP_OK;
+}
+
 // The matcher proper: `pairs` problems, everything on the device.  9 x (SelfBlock x2 images, CrossBlock), then
 // log_assignment[8] + filter_matches.
 static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_stride, const int* lens,
@@ -1601,16 +1702,28 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
                  (float)lg->image_w, (float)lg->image_h, d, x, rope, lg->kpn.as<float>(), s);
   lens = lg->lens_c.as<int>();
   lg->last_pairs = pairs;
+  // adaptive depth: layer i's token confidence after its CrossBlock, the running set for layers i + 1 ..; the exit head after the join
+  const bool adaptive = lg->depth_conf > 0.f;
+#if SSHIP_DEV_SWITCHES
+  // the developer kernels that do not know the running set: refuse rather than ignore the setting
+  if (adaptive && ((dev_env("SUPERSLAM_HIP_FFN") && atoi(dev_env("SUPERSLAM_HIP_FFN")) == 16) ||
+                   (dev_env("SUPERSLAM_HIP_ATTN") && std::string(dev_env("SUPERSLAM_HIP_ATTN")) == "res")))
+    return fail(SSHIP_ERR_INVALID, "lightglue: adaptive depth is not supported by the 16-wave FFN or the LDS-resident-key attention");
+#endif
+  lg->last_adaptive = adaptive;
+  lg->last_layers = lg->debug_layers;
   // 3 launches per block: [projection fused into the previous FFN's tail] -> attention -> FFN(+ next projection).
   static const bool igemm_qkv0 = dev_env("SUPERSLAM_HIP_LG_QKV0") && std::string(dev_env("SUPERSLAM_HIP_LG_QKV0")) == "igemm";  // A/B
   const int n_layers = lg->debug_layers;  // kLgLayers except under sship_lg_debug_set_layers (test-only)
   // the layer stack of pairs [p0, p0 + np) on stream st: every buffer is sequence-major, pairs are independent
-  auto layers = [&](int p0, int np, hipStream_t st, bool shared_gpu) -> int {
+  auto layers = [&](int p0, int np, hipStream_t st, bool shared_gpu, int part) -> int {
     const LgDims ds{2 * np, lg->NP};
+    const LgDepth dep = lg_depth_state(lg, p0, part);
     const size_t tok = (size_t)2 * p0 * lg->NP;
     _Float16 *xs = x + tok * 256, *qs = q + tok * 256, *ks = k + tok * 256, *vs = vt + tok * 256, *cs = ctx + tok * 256;
     const float* rs = rope + tok * 64;
     const int* ls = lens + 2 * p0;
+    if (adaptive) launch_lg_depth_init(ls, np, dep, st);
     // what each FFN launch streams (w0, w3, the fused projection): handed to the launch BEFORE it as a prefetch hint (latency mode)
     auto self_w = [&](int i, const ConvW** o) { o[0] = &w->ffn0_s[i]; o[1] = &w->ffn3_s[i]; o[2] = &w->cqkv_t[i]; };
     auto cross_w = [&](int i, const ConvW** o) { o[0] = &w->ffn0_c[i]; o[1] = &w->ffn3_c[i]; o[2] = i + 1 < kLgLayers ? &w->qkv_t[i + 1] : &w->final_t; };
@@ -1622,21 +1735,27 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
 #endif
     SSHIP_HIP_CHECK(launch_lg_proj_heads(w->qkv_t[0], xs, ds, /*rope_segs=*/2, /*t_seg=*/2, rs, qs, ks, vs, st, pf));
     for (int i = 0; i < n_layers; ++i) {
+      // adaptive depth, layers >= 1: the attention launches see the counts of running pairs only (0 for stopped ones: their
+      // workgroups return at once), the FFN launches walk the tiles of running pairs only.  Layer 0 runs as without it.
+      const int* la = adaptive && i > 0 ? dep.lens_live : ls;
+      const int* live = adaptive && i > 0 ? dep.live : nullptr;
       // SelfBlock (both images of every pair in one launch); its FFN also emits CrossBlock's [to_qk | to_v]
-      launch_lg_attention(qs, ks, vs, ls, ds, false, cs, st, shared_gpu);
+      launch_lg_attention(qs, ks, vs, la, ds, false, cs, st, shared_gpu);
       cross_w(i, pf);
       launch_lg_ffn(w->ffn0_s[i], w->ffn3_s[i], w->ln_g_s[i], w->ln_b_s[i], cs, xs, ds, &w->cqkv_t[i], true, /*rope_segs=*/0,
-                    /*t_seg=*/1, rs, qs, ks, vs, nullptr, nullptr, 0.f, nullptr, st, pf);
+                    /*t_seg=*/1, rs, qs, ks, vs, nullptr, nullptr, 0.f, nullptr, st, pf, live);
       // CrossBlock (qk shared by both directions; sequence s attends to s^1); its FFN emits the next layer's Wqkv,
       // or final_proj + matchability after the last layer
-      launch_lg_attention(qs, qs, vs, ls, ds, true, cs, st, shared_gpu);
+      launch_lg_attention(qs, qs, vs, la, ds, true, cs, st, shared_gpu);
       if (i + 1 < kLgLayers) {
         self_w(i + 1, pf);
         launch_lg_ffn(w->ffn0_c[i], w->ffn3_c[i], w->ln_g_c[i], w->ln_b_c[i], cs, xs, ds, &w->qkv_t[i + 1], true, 2, 2, rs, qs, ks,
-                      vs, nullptr, nullptr, 0.f, nullptr, st, pf);
+                      vs, nullptr, nullptr, 0.f, nullptr, st, pf, live);
+        if (adaptive)  // token confidence of layer i and the stop rule (reads x after layer i)
+          launch_lg_depth_conf(xs, ls, lg->NP, np, w->tc_w + i * 256, w->tc_b[i], lg_depth_threshold(i), lg->depth_conf, i, dep, st);
       } else
         launch_lg_ffn(w->ffn0_c[i], w->ffn3_c[i], w->ln_g_c[i], w->ln_b_c[i], cs, xs, ds, &w->final_t, false, 0, 0, rs, qs, ks, vs,
-                      lg->md.as<_Float16>() + tok * 256, w->match_w, w->match_b, lg->logsig.as<float>() + tok, st);
+                      lg->md.as<_Float16>() + tok * 256, w->match_w, w->match_b, lg->logsig.as<float>() + tok, st, nullptr, live);
     }
     SSHIP_HIP_CHECK(hipGetLastError());
     return SSHIP_OK;
@@ -1662,10 +1781,10 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
       const int np = i + 1 < parts ? pairs / parts : pairs - p0;
       if ((he = hipStreamWaitEvent(lg->aux[i - 1], lg->ev_fork, 0)) != hipSuccess) break;
       forked = i;
-      rc = layers(p0, np, lg->aux[i - 1], true);
+      rc = layers(p0, np, lg->aux[i - 1], true, i);
       p0 += np;
     }
-    if (rc == SSHIP_OK && he == hipSuccess) rc = layers(0, pairs / parts, s, true);
+    if (rc == SSHIP_OK && he == hipSuccess) rc = layers(0, pairs / parts, s, true, 0);
     for (int i = 1; i <= forked; ++i) {  // join (also on the error path; best effort there)
       hipError_t e1 = hipEventRecord(lg->ev_join[i - 1], lg->aux[i - 1]);
       if (e1 == hipSuccess) e1 = hipStreamWaitEvent(s, lg->ev_join[i - 1], 0);
@@ -1674,7 +1793,7 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
     if (rc != SSHIP_OK) return rc;
     SSHIP_HIP_CHECK(he);
   } else {
-    if (int rc = layers(0, pairs, s, false)) return rc;
+    if (int rc = layers(0, pairs, s, false, 0)) return rc;
   }
   SSHIP_HIP_CHECK(hipGetLastError());
   g_timer.mark("fe_lg_stereo_match:layers_x9", s);
@@ -1685,6 +1804,9 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
     SSHIP_HIP_CHECK(hipMemsetAsync(ms0, 0, (size_t)pairs * lg->max_kp * 4, s));
     return SSHIP_OK;
   }
+  if (adaptive)  // md / logsig of the pairs that stopped early, from the assignment head of the layer they stopped after
+    launch_lg_exit_head(x, lg->NP, pairs, lg->dep.as<int>() + (size_t)lg->max_pairs * 8, w->head_wt, w->head_b, w->head_mw, w->head_mb,
+                        lg->md.as<_Float16>(), lg->logsig.as<float>(), s);
   // log-assignment + mutual filter straight from md (lg_kernels.hip: k_assign_stream); lg->sim is the partials' scratch
   launch_lg_assign(lg->md.as<_Float16>(), lg->logsig.as<float>(), lens, d, lg->ws.as<float>(), lg->sim.as<float>(), lg->max_kp, m0, ms0,
                    0.1f /* filter_threshold */, 0, s);

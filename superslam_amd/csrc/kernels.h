@@ -133,7 +133,23 @@ hipError_t launch_lg_proj_heads(const ConvW& next, _Float16* x, LgDims d, int ro
 void launch_lg_ffn(const ConvW& w0, const ConvW& w3, const float* gamma, const float* beta, const _Float16* ctx,
                    _Float16* x, LgDims d, const ConvW* next, bool heads, int rope_segs, int t_seg, const float* rope,
                    _Float16* q, _Float16* k, _Float16* vt, _Float16* out, const float* match_w, float match_b,
-                   float* logsig, hipStream_t s, const ConvW* const* prefetch = nullptr);
+                   float* logsig, hipStream_t s, const ConvW* const* prefetch = nullptr, const int* live = nullptr);
+// Adaptive depth (sship_lg_set_depth_confidence).  State of the pairs [p0, p0 + np) of one launch group, every pointer offset to p0:
+struct LgDepth {
+  int* cnt;         // [np][8]: valid tokens with confidence < thr_i after layer i (integer atomics: exact, order-independent)
+  int* layers_run;  // [np]: 9 while running, i + 1 once stopped after layer i
+  int* lens_live;   // [2 np]: the clamped counts of running pairs, 0 for stopped ones (what the attention launches of layers >= 1 read)
+  int* live;        // [1 + np]: count, then the running pairs' indices (what the FFN launches of layers >= 1 walk)
+  unsigned* ticket; // one counter: the last workgroup of a k_lg_depth_conf launch takes the decisions
+};
+void launch_lg_depth_init(const int* lens, int np, LgDepth dep, hipStream_t s);
+// token confidence of layer i: counts, then (last workgroup) the stop rule for every pair of the group
+void launch_lg_depth_conf(const _Float16* x, const int* lens, int NP, int np, const float* tw, float tb, float thr, float depth_conf,
+                          int layer, LgDepth dep, hipStream_t s);
+// the assignment inputs of every stopped pair from head layers_run - 1: md = final_proj(x) (scale folded in), logsig = logsigmoid(matchability . x)
+// wt [9][256 in][256 out] fp32, bias [9][256], mw [9][256], mb [9]
+void launch_lg_exit_head(const _Float16* x, int NP, int pairs, const int* layers_run, const float* wt, const float* bias, const float* mw,
+                         const float* mb, _Float16* md, float* logsig, hipStream_t s);
 void launch_lg_sim(const _Float16* md, const int* lens, LgDims d, float* sim, hipStream_t s);
 void launch_lg_assign(const _Float16* md, const float* logsig, const int* lens, LgDims d, float* ws, float* pcol, int max_kp,
                       int32_t* matches0, float* mscores0, float thr, int stage, hipStream_t s);

@@ -41,6 +41,10 @@ struct FfnTail {
   int n_main;              // 0: no prefetch workgroups (gridDim.x workgroups walk the tiles)
   const void* pf_ptr[3];
   int pf_bytes[3];
+  // adaptive depth (the AD instantiations only): live[0] = pairs of this launch still running, live[1 ..] their indices relative
+  // to the launch; a pair's tiles_per_pair tiles are consecutive.  Written by k_lg_depth_conf, complete at the kernel boundary.
+  const int* live;
+  int tiles_per_pair;
 };
 
 // lg_ffn16.hip: the 16-wave, one-workgroup-per-CU form of the fused block (throughput batches)

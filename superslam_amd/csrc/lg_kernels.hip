@@ -615,7 +615,18 @@ void launch_lg_attention(const _Float16* q, const _Float16* k, const _Float16* v
 // (barrier, residual operand) are not address-path time (tail MFMA 5.1 -> 4.25 k / 9.3 -> 7.6 k, residual unchanged), and barriers
 // that wait for LDS traffic only (__syncthreads() drains vmcnt too and would stall every wave on its own prefetch).
 __device__ __forceinline__ void ffn_bar_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <int NEXT_MT, bool HEADS, int NT, bool PROJ>
+// adaptive depth (AD instantiations): a launch walks only the tiles of its running pairs.  li = index among those tiles.
+template <bool AD>
+__device__ __forceinline__ int ffn_live_tiles(const FfnTail& t) {
+  if constexpr (AD) return t.live[0] * t.tiles_per_pair;
+  else return t.ntiles;
+}
+template <bool AD>
+__device__ __forceinline__ int ffn_tile_of(const FfnTail& t, int li) {
+  if constexpr (AD) return t.live[1 + li / t.tiles_per_pair] * t.tiles_per_pair + li % t.tiles_per_pair;
+  else return li;
+}
+template <int NEXT_MT, bool HEADS, int NT, bool PROJ, bool AD = false>
 __global__ __launch_bounds__(512, 2) void k_lg_ffn(const _Float16* __restrict__ ctx, const _Float16* __restrict__ w0p,
                                                 const float* __restrict__ b0, const float* __restrict__ gamma,
                                                 const float* __restrict__ beta, const _Float16* __restrict__ w3p,
@@ -681,16 +692,18 @@ __global__ __launch_bounds__(512, 2) void k_lg_ffn(const _Float16* __restrict__ 
     if (acc == 0x9e3779b9u && tail.trace) tail.trace[0] = acc;  // keeps the loads alive; never true in practice and harmless if it is
     return;
   }
-  if (tile0 >= tail.ntiles) return;
-  stage_tile(tile0, s_xbuf, threadIdx.x >> 6, threadIdx.x & 63);
+  const int ntl = ffn_live_tiles<AD>(tail);
+  if (tile0 >= ntl) return;
+  stage_tile(ffn_tile_of<AD>(tail, tile0), s_xbuf, threadIdx.x >> 6, threadIdx.x & 63);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   int it = 0;
 #pragma unroll 1
-  for (int tile = tile0; tile < tail.ntiles; tile += nwg, ++it) {
+  for (int li = tile0; li < ntl; li += nwg, ++it) {
+  const int tile = ffn_tile_of<AD>(tail, li);
   _Float16* s_x = s_xbuf + (NT <= 2 ? (it & 1) : 0) * XBUF;
   _Float16* s_xn = s_xbuf + (NT <= 2 ? ((it + 1) & 1) : 0) * XBUF;
-  const bool has_next = tile + nwg < tail.ntiles;
+  const bool has_next = li + nwg < ntl;
   const size_t t0 = (size_t)tile * NTOK;
   // Everything below that does not depend on the tile (weight fragments, biases, LayerNorm parameters) is loop
   // invariant: LICM would hoist those loads out of the tile loop and spill hundreds of registers.  An opaque zero
@@ -796,7 +809,7 @@ __global__ __launch_bounds__(512, 2) void k_lg_ffn(const _Float16* __restrict__ 
   // every wave has passed the LayerNorm barriers, i.e. finished the previous tile: its buffer takes the next tile.
   // Issued here because no weight prefetch is in flight (an older DMA would sit in front of it in the in-order vmcnt
   // queue) and the GELU math + ffn.3 that follow cover the HBM latency.
-  if (NT <= 2 && has_next) stage_tile(tile + nwg, s_xn, wave, lane);
+  if (NT <= 2 && has_next) stage_tile(ffn_tile_of<AD>(tail, li + nwg), s_xn, wave, lane);
   // the residual operand (this lane's 16 x values per N-tile) is requested before the GELU math: its L2 round trip
   // used to sit between the ffn.3 loop and the barrier that opens the fused projection
   h4_t xres[4][NT];
@@ -972,7 +985,7 @@ __global__ __launch_bounds__(512, 2) void k_lg_ffn(const _Float16* __restrict__ 
         for (int i = 0; i < GT; ++i) kstep(PFK + grp * GT + i, at[grp & 1][i]);
       }
       stamp(8);
-      if (PROJ && NT <= 2 && has_next) stage_tile(tile + nwg, s_xn, wave, lane);  // the epilogue covers the DMA
+      if (PROJ && NT <= 2 && has_next) stage_tile(ffn_tile_of<AD>(tail, li + nwg), s_xn, wave, lane);  // the epilogue covers the DMA
       if (SSHIP_FFN_ABL & 32) return;
       if constexpr (HEADS) {
         const int NP = pj.np, nt32 = NP >> 5;
@@ -1053,7 +1066,7 @@ __global__ __launch_bounds__(512, 2) void k_lg_ffn(const _Float16* __restrict__ 
   stamp(9);
   if (NT > 2 && has_next) {  // single tile buffer: synchronous restage
     __syncthreads();
-    stage_tile(tile + nwg, s_xn, wave, lane);
+    stage_tile(ffn_tile_of<AD>(tail, li + nwg), s_xn, wave, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   }
   if constexpr (PROJ) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1061,11 +1074,11 @@ __global__ __launch_bounds__(512, 2) void k_lg_ffn(const _Float16* __restrict__ 
   stamp(10);
   }  // tile loop
 }
-template <int NEXT_MT, bool HEADS, int NT, bool PROJ, typename... A>
+template <int NEXT_MT, bool HEADS, int NT, bool PROJ, bool AD = false, typename... A>
 static hipError_t launch_ffn_nt(int tokens, int extra_wg, hipStream_t s, A... args) {
   constexpr size_t smem = (size_t)(NT <= 2 ? 2 : 1) * NT * 32 * kFfnLd * 2 + 16 * NT * 32 * 4 + 1792 * 4;
   static_assert(smem <= 163840, "LDS budget");
-  auto kern = k_lg_ffn<NEXT_MT, HEADS, NT, PROJ>;
+  auto kern = k_lg_ffn<NEXT_MT, HEADS, NT, PROJ, AD>;
   // thread-safe one-time opt-in to > 64 KiB of dynamic LDS (C++11 magic static; handles may be created on any thread)
   static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (attr_rc != hipSuccess) return attr_rc;
@@ -1092,12 +1105,13 @@ static void ffn_trace_report(unsigned long long* dev, int nwg, int next_mt, hipS
   for (int i = 0; i < 10; ++i) { fprintf(stderr, " %s=%.0f", names[i], sum[i] / cnt); tot += sum[i] / cnt; }
   fprintf(stderr, " | tile=%.0f clk\n", tot);
 }
-template <int NEXT_MT, bool HEADS, typename... A>
+template <int NEXT_MT, bool HEADS, bool AD = false, typename... A>
 static hipError_t launch_ffn(int nt, int tokens, int extra_wg, hipStream_t s, A... args) {
   // 64-token tiles for throughput, 32-token tiles when the launch cannot even give half of the CUs a workgroup (a few
   // pairs: twice the workgroups in flight, half the MFMA work per weight stream).  128 tokens measured 9 % slower end to
   // end (1.25 tiles per CU at 32 pairs, single tile buffer) and no longer fits the registers: not instantiated.
-  return nt == 1 ? launch_ffn_nt<NEXT_MT, HEADS, 1, false>(tokens, extra_wg, s, args...) : launch_ffn_nt<NEXT_MT, HEADS, 2, false>(tokens, extra_wg, s, args...);
+  return nt == 1 ? launch_ffn_nt<NEXT_MT, HEADS, 1, false, AD>(tokens, extra_wg, s, args...)
+                 : launch_ffn_nt<NEXT_MT, HEADS, 2, false, AD>(tokens, extra_wg, s, args...);
 }
 // ---------------------------------------------------------------------------------------------------
 // k_lg_ffn4: the same fused block with FOUR waves per workgroup and TWO workgroups per CU (throughput batches).
@@ -1142,7 +1156,7 @@ __device__ __forceinline__ f16x_t mfma32_abl(h8_t a, h8_t b, f16x_t c) {
     return mfma32(a, b, c);
   }
 }
-template <int NEXT_MT, bool HEADS, bool PROJ>
+template <int NEXT_MT, bool HEADS, bool PROJ, bool AD = false>
 __global__ __launch_bounds__(256, 2) void k_lg_ffn4(const _Float16* __restrict__ ctx, const _Float16* __restrict__ w0p,
                                                     const float* __restrict__ b0, const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, const _Float16* __restrict__ w3p,
@@ -1179,14 +1193,16 @@ __global__ __launch_bounds__(256, 2) void k_lg_ffn4(const _Float16* __restrict__
     }
   };
   const int tile0 = blockIdx.x;
-  if (tile0 >= tail.ntiles) return;
-  stage_tile(tile0, threadIdx.x >> 6, threadIdx.x & 63);
+  const int ntl = ffn_live_tiles<AD>(tail);
+  if (tile0 >= ntl) return;
+  stage_tile(ffn_tile_of<AD>(tail, tile0), threadIdx.x >> 6, threadIdx.x & 63);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   int it = 0;
 #pragma unroll 1
-  for (int tile = tile0; tile < tail.ntiles; tile += gridDim.x, ++it) {
-  const bool has_next = tile + (int)gridDim.x < tail.ntiles;
+  for (int li = tile0; li < ntl; li += gridDim.x, ++it) {
+  const int tile = ffn_tile_of<AD>(tail, li);
+  const bool has_next = li + (int)gridDim.x < ntl;
   const size_t t0 = (size_t)tile * NTOK;
   int zero = 0;
   asm volatile("" : "+s"(zero));  // keeps loop-invariant weight / parameter loads inside the iteration (see k_lg_ffn)
@@ -1573,18 +1589,18 @@ __global__ __launch_bounds__(256, 2) void k_lg_ffn4(const _Float16* __restrict__
   stamp(10);
   if (has_next) {
     __syncthreads();  // every wave has finished with the tile buffer
-    stage_tile(tile + gridDim.x, wave, lane);
+    stage_tile(ffn_tile_of<AD>(tail, li + (int)gridDim.x), wave, lane);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
   }
   stamp(11);
   }  // tile loop
 }
-template <int NEXT_MT, bool HEADS, bool PROJ, typename... A>
+template <int NEXT_MT, bool HEADS, bool PROJ, bool AD = false, typename... A>
 static hipError_t launch_ffn4(int tokens, hipStream_t s, A... args) {
   constexpr size_t smem = (size_t)64 * kFfnLd * 2 + 8 * 64 * 4 + (1792 + 768 + 512) * 4;  // 80,896 B: two workgroups per CU
   static_assert(2 * smem <= 163840, "two workgroups must fit the CU's LDS");
-  auto kern = k_lg_ffn4<NEXT_MT, HEADS, PROJ>;
+  auto kern = k_lg_ffn4<NEXT_MT, HEADS, PROJ, AD>;
   static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   if (attr_rc != hipSuccess) return attr_rc;
   const int ntiles = tokens / 64;
@@ -1654,7 +1670,7 @@ static int ffn_prefetch_setup(FfnTail& t, int n_main, const ConvW* const* pf) {
 void launch_lg_ffn(const ConvW& w0, const ConvW& w3, const float* gamma, const float* beta, const _Float16* ctx,
                    _Float16* x, LgDims d, const ConvW* next, bool heads, int rope_segs, int t_seg, const float* rope,
                    _Float16* q, _Float16* k, _Float16* vt, _Float16* out, const float* match_w, float match_b,
-                   float* logsig, hipStream_t s, const ConvW* const* prefetch) {
+                   float* logsig, hipStream_t s, const ConvW* const* prefetch, const int* live) {
   const int tokens = d.S * d.NP;
   FfnTail t{};
   static const int nt_env = dev_env("SUPERSLAM_HIP_FFN_NT") ? atoi(dev_env("SUPERSLAM_HIP_FFN_NT")) : 0;  // A/B: 1 | 2
@@ -1681,23 +1697,37 @@ void launch_lg_ffn(const ConvW& w0, const ConvW& w3, const float* gamma, const f
   t.match_w = match_w; t.match_b = match_b; t.logsig = logsig;
   const int mt = next->cout / 256;  // rows per wave / 32: 768 -> 3, 512 -> 2, 256 -> 1
 #if SSHIP_DEV_SWITCHES
-  if (use_ffn16(tokens) && ffn16_applicable(tokens, mt, heads)) {
+  if (!live && use_ffn16(tokens) && ffn16_applicable(tokens, mt, heads)) {  // adaptive depth: lg_forward refuses this switch
     (void)launch_lg_ffn16(tokens, mt, heads, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
     return;
   }
 #endif
+  // live != null (adaptive depth): the AD instantiations, which walk the tiles of the running pairs only (same tile math)
+  t.live = live;
   if (use_ffn4(tokens) && !trace_on_is8()) {
     t.ntiles = tokens / 64;
-    if (heads && mt == 3) (void)launch_ffn4<3, true, false>(tokens, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
-    else if (heads && mt == 2) (void)launch_ffn4<2, true, false>(tokens, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
-    else (void)launch_ffn4<1, false, false>(tokens, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
+    t.tiles_per_pair = 2 * d.NP / 64;
+    auto go4 = [&](auto ad) {
+      constexpr bool AD = decltype(ad)::value;
+      if (heads && mt == 3) (void)launch_ffn4<3, true, false, AD>(tokens, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
+      else if (heads && mt == 2) (void)launch_ffn4<2, true, false, AD>(tokens, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
+      else (void)launch_ffn4<1, false, false, AD>(tokens, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
+    };
+    if (live) go4(std::true_type{});
+    else go4(std::false_type{});
     if (trace_on) ffn4_trace_report(trace_buf, t.ntiles < 2 * cu_count() ? t.ntiles : 2 * cu_count(), mt, s);
     return;
   }
+  t.tiles_per_pair = 2 * d.NP / (nt * 32);
   const int extra = ffn_prefetch_setup(t, trace_wg, prefetch);  // trace_wg = the workgroups that walk the tiles
-  if (heads && mt == 3) (void)launch_ffn<3, true>(nt, tokens, extra, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
-  else if (heads && mt == 2) (void)launch_ffn<2, true>(nt, tokens, extra, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
-  else (void)launch_ffn<1, false>(nt, tokens, extra, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
+  auto go = [&](auto ad) {
+    constexpr bool AD = decltype(ad)::value;
+    if (heads && mt == 3) (void)launch_ffn<3, true, AD>(nt, tokens, extra, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
+    else if (heads && mt == 2) (void)launch_ffn<2, true, AD>(nt, tokens, extra, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
+    else (void)launch_ffn<1, false, AD>(nt, tokens, extra, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
+  };
+  if (live) go(std::true_type{});
+  else go(std::false_type{});
   if (trace_on) ffn_trace_report(trace_buf, trace_wg, mt, s);
 }
 
@@ -2148,6 +2178,152 @@ void launch_lg_assign(const _Float16* md, const float* logsig, const int* lens, 
     if (stage == 0)
       hipLaunchKernelGGL(k_assign_mutual, dim3((max_kp + 255) / 256, P), dim3(256), 0, s, pcol1, prow1, lens, d.NP, max_kp, thr, matches0, mscores0);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Adaptive depth (upstream LightGlue's depth_confidence; include/sship.h "Adaptive depth").  Off by default: none of the
+// launches below is made, and the layer stack runs its usual kernels.  On, per launch group of pairs (lg_forward):
+//   init -> layer 0 -> conf(0) -> layer 1 -> conf(1) -> ... -> layer 8 ; after the join: exit head -> assignment.
+// conf(i) counts the settled tokens of every running pair; its last workgroup applies the stop rule and publishes the running set
+// (lens_live for the attention launches, the live list for the FFN launches of later layers).  Everything stays on the device.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_lg_depth_init(const int* __restrict__ lens, int np, LgDepth dep) {
+  for (int q = threadIdx.x; q < np; q += 256) {
+    dep.layers_run[q] = 9;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) dep.cnt[q * 8 + i] = 0;
+    dep.lens_live[2 * q] = lens[2 * q];
+    dep.lens_live[2 * q + 1] = lens[2 * q + 1];
+    dep.live[1 + q] = q;
+  }
+  if (threadIdx.x == 0) { dep.live[0] = np; *dep.ticket = 0u; }
+}
+void launch_lg_depth_init(const int* lens, int np, LgDepth dep, hipStream_t s) {
+  hipLaunchKernelGGL(k_lg_depth_init, dim3(1), dim3(256), 0, s, lens, np, dep);
+}
+
+// One workgroup = 64 consecutive tokens of one pair (2 NP is a multiple of 64), 16 per wave.  Token t's logit is a 64-lane dot
+// product of its x row (fp16, as the FFN stored it) with token_confidence[i]; lane t keeps t's verdict, one ballot + popcount
+// counts the wave's settled tokens, and the workgroup adds its count with ONE integer atomic.  Then a ticket: the workgroup that
+// comes last (every other one has added its count) reads the complete counters and decides for every pair of the group, in fp32,
+// in upstream's form  1 - count / (n0 + n1) > depth_confidence.
+__global__ __launch_bounds__(256) void k_lg_depth_conf(const _Float16* __restrict__ x, const int* __restrict__ lens, int NP, int np,
+                                                       const float* __restrict__ tw, float tb, float thr, float dconf, int layer,
+                                                       LgDepth dep) {
+  __shared__ int s_cnt, s_last, s_live;
+  __shared__ int s_run[256];
+  const int tpp = (2 * NP) >> 6;
+  const int p = blockIdx.x / tpp, c0 = (blockIdx.x - p * tpp) * 64;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  if (threadIdx.x == 0) s_cnt = 0;
+  __syncthreads();
+  if (dep.layers_run[p] == 9) {  // running (a pair that stopped earlier is not counted again)
+    const float4 w = *reinterpret_cast<const float4*>(tw + lane * 4);
+    bool mine = false;
+#pragma unroll 4
+    for (int t = 0; t < 16; ++t) {
+      const int tok = c0 + wave * 16 + t;  // [0, NP): image 0, [NP, 2 NP): image 1
+      const int img = tok >= NP ? 1 : 0, n = tok - img * NP;
+      const h4_t v = *reinterpret_cast<const h4_t*>(x + ((size_t)2 * p * NP + tok) * 256 + lane * 4);
+      const float z = wave_sum((float)v[0] * w.x + (float)v[1] * w.y + (float)v[2] * w.z + (float)v[3] * w.w) + tb;
+      const float conf = 1.0f / (1.0f + expf(-z));
+      if (lane == t) mine = n < lens[2 * p + img] && conf < thr;
+    }
+    const int c = __popcll(__ballot(mine));
+    if (lane == 0 && c) atomicAdd(&s_cnt, c);
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    if (s_cnt) atomicAdd(dep.cnt + p * 8 + layer, s_cnt);
+    __threadfence();
+    s_last = atomicAdd(dep.ticket, 1u) == gridDim.x - 1 ? 1 : 0;
+    s_live = 0;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  __threadfence();
+  for (int base = 0; base < np; base += 256) {
+    const int q = base + (int)threadIdx.x;
+    int run = 0;
+    if (q < np) {
+      if (__hip_atomic_load(dep.layers_run + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 9) {
+        const int n = lens[2 * q] + lens[2 * q + 1];
+        const int cq = __hip_atomic_load(dep.cnt + q * 8 + layer, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool stop = n > 0 && 1.0f - (float)cq / (float)n > dconf;  // n0 + n1 = 0: never stops
+        if (stop) dep.layers_run[q] = layer + 1;
+        run = stop ? 0 : 1;
+      }
+      dep.lens_live[2 * q] = run ? lens[2 * q] : 0;
+      dep.lens_live[2 * q + 1] = run ? lens[2 * q + 1] : 0;
+    }
+    s_run[threadIdx.x] = run;
+    __syncthreads();
+    if (threadIdx.x == 0) {  // compaction in pair order
+      int k = s_live;
+      for (int t = 0; t < 256 && base + t < np; ++t)
+        if (s_run[t]) dep.live[1 + k++] = base + t;
+      s_live = k;
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    dep.live[0] = s_live;
+    *dep.ticket = 0u;  // ready for the next layer's launch
+  }
+}
+void launch_lg_depth_conf(const _Float16* x, const int* lens, int NP, int np, const float* tw, float tb, float thr, float depth_conf,
+                          int layer, LgDepth dep, hipStream_t s) {
+  hipLaunchKernelGGL(k_lg_depth_conf, dim3(np * (2 * NP / 64)), dim3(256), 0, s, x, lens, NP, np, tw, tb, thr, depth_conf, layer, dep);
+}
+
+// One workgroup = 32 tokens of one pair; nothing to do for a pair that ran all nine layers (the last block's fused tail wrote its
+// md / logsig).  Thread o computes output channel o of final_proj[h] for the 32 tokens: the x tile sits in LDS as fp32 (every read is a
+// broadcast), the weights are read transposed ([k][o]: one coalesced KB per k), fp32 accumulation, fp16 rows as the fused tail stores them.
+__global__ __launch_bounds__(256) void k_lg_exit_head(const _Float16* __restrict__ x, int NP, const int* __restrict__ layers_run,
+                                                      const float* __restrict__ wt, const float* __restrict__ bias,
+                                                      const float* __restrict__ mw, const float* __restrict__ mb,
+                                                      _Float16* __restrict__ md, float* __restrict__ logsig) {
+  __shared__ __attribute__((aligned(16))) float s_x[32][260];
+  const int tpp = (2 * NP) >> 5;
+  const int p = blockIdx.x / tpp;
+  const int lr = layers_run[p];
+  if (lr >= 9 || lr < 1) return;
+  const int h = lr - 1;
+  const size_t t0 = (size_t)2 * p * NP + (size_t)(blockIdx.x - p * tpp) * 32;
+  for (int i = threadIdx.x; i < 32 * 64; i += 256) {
+    const int t = i >> 6, c = (i & 63) * 4;
+    const h4_t v = *reinterpret_cast<const h4_t*>(x + (t0 + t) * 256 + c);
+    *reinterpret_cast<float4*>(&s_x[t][c]) = make_float4((float)v[0], (float)v[1], (float)v[2], (float)v[3]);
+  }
+  __syncthreads();
+  const int o = threadIdx.x;
+  const float* W = wt + (size_t)h * 65536 + o;
+  float acc[32];
+#pragma unroll
+  for (int t = 0; t < 32; ++t) acc[t] = 0.f;
+#pragma unroll 2
+  for (int k = 0; k < 256; k += 4) {
+    const float w0 = W[(k + 0) * 256], w1 = W[(k + 1) * 256], w2 = W[(k + 2) * 256], w3 = W[(k + 3) * 256];
+#pragma unroll
+    for (int t = 0; t < 32; ++t) {
+      const float4 xv = *reinterpret_cast<const float4*>(&s_x[t][k]);
+      acc[t] = fmaf(xv.w, w3, fmaf(xv.z, w2, fmaf(xv.y, w1, fmaf(xv.x, w0, acc[t]))));
+    }
+  }
+  const float b = bias[h * 256 + o];
+#pragma unroll
+  for (int t = 0; t < 32; ++t) md[(t0 + t) * 256 + o] = (_Float16)(acc[t] + b);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float4 m = *reinterpret_cast<const float4*>(mw + h * 256 + lane * 4);
+  for (int tk = wave * 8; tk < wave * 8 + 8; ++tk) {
+    const float4 xv = *reinterpret_cast<const float4*>(&s_x[tk][lane * 4]);
+    const float z = wave_sum(xv.x * m.x + xv.y * m.y + xv.z * m.z + xv.w * m.w) + mb[h];
+    if (lane == 0) logsig[t0 + tk] = fminf(z, 0.f) - log1pf(expf(-fabsf(z)));
+  }
+}
+void launch_lg_exit_head(const _Float16* x, int NP, int pairs, const int* layers_run, const float* wt, const float* bias, const float* mw,
+                         const float* mb, _Float16* md, float* logsig, hipStream_t s) {
+  hipLaunchKernelGGL(k_lg_exit_head, dim3(pairs * (2 * NP / 32)), dim3(256), 0, s, x, NP, layers_run, wt, bias, mw, mb, md, logsig);
 }
 
 }  // namespace sship

@@ -47,8 +47,11 @@ class LightGlueEngine:
 
 
 class LightGlue:
-    def __init__(self, engine, image_width: int, image_height: int, max_keypoints: int = 1024, max_pairs: int = 1):
+    def __init__(self, engine, image_width: int, image_height: int, max_keypoints: int = 1024, max_pairs: int = 1,
+                 depth_confidence: float = -1.0):
         self._engine_arg = engine
+        # adaptive depth (upstream LightGlue's depth_confidence, include/sship.h): <= 0 = off, the reference's setting
+        self.depth_confidence = float(depth_confidence)
         self.image_width, self.image_height = int(image_width), int(image_height)
         self.max_keypoints, self.max_pairs = int(max_keypoints), int(max_pairs)
         self._engine = engine if isinstance(engine, LightGlueEngine) else None
@@ -63,6 +66,8 @@ class LightGlue:
             _lib.check(_lib.lib().sship_lg_create(self._engine._h, self.image_width, self.image_height,
                                                   self.max_keypoints, self.max_pairs, C.byref(h)))
             self._h = h
+            if self.depth_confidence > 0:
+                _lib.check(_lib.lib().sship_lg_set_depth_confidence(h, C.c_float(self.depth_confidence)))
             return True
         except _lib.SshipError as e:
             self.last_error = str(e)
@@ -119,6 +124,18 @@ class LightGlue:
         d = np.zeros(n0, np.float32)
         k = L.sship_filter_matches(m0.ctypes.data, ms0.ctypes.data, n0, q.ctypes.data, t.ctypes.data, d.ctypes.data)
         return MatchResult(q[:k], t[:k], d[:k], m0, ms0)
+
+    def set_depth_confidence(self, depth_confidence: float) -> None:
+        """Adaptive depth for the calls after this one: d in (0, 1] on, <= 0 off.  Raises SshipError for NaN, d > 1, or weights
+        without the token-confidence / early assignment heads (the setting is then unchanged)."""
+        _lib.check(_lib.lib().sship_lg_set_depth_confidence(self._h, C.c_float(float(depth_confidence))))
+        self.depth_confidence = float(depth_confidence)
+
+    def layers_run(self, pairs: int = 1) -> np.ndarray:
+        """Layers each of the first `pairs` pairs of the last call ran (upstream's `stop`): int32 [pairs]."""
+        out = np.zeros(int(pairs), np.int32)
+        _lib.check(_lib.lib().sship_lg_layers_run(self._h, out.ctypes.data, int(pairs)))
+        return out
 
     def descriptors_to_host(self, d: DeviceDescriptors) -> np.ndarray:
         """src/LightGlue.cc:460-475: fp16 slot -> float32 [count, dim]; empty handle -> empty array."""

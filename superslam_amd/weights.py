@@ -113,6 +113,25 @@ def make_lightglue_weights(seed: int = 1, residual_gain: float = 0.05, assign_ga
     return sd
 
 
+def add_token_confidence_heads(sd: dict, seed: int = 3, weight_gain: float = 0.0, biases=0.0) -> dict:
+    """A copy of the LightGlue state dict ``sd`` with upstream's token-confidence heads added (adaptive depth, include/sship.h):
+    ``token_confidence.{i}.token.0.weight`` [1, 256] and ``.bias`` [1] for i = 0..7.  Every other tensor is the same object.
+
+    The weights are he-style rows times ``weight_gain`` (0: every token of a layer gets the same confidence sigmoid(bias));
+    ``biases`` is one number or eight.  make_lightglue_weights() itself is unchanged: fixtures regenerate from it."""
+    d = LG_DIM
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    b = [float(biases)] * (LG_LAYERS - 1) if isinstance(biases, (int, float)) else [float(v) for v in biases]
+    if len(b) != LG_LAYERS - 1:
+        raise ValueError(f"biases: one value or {LG_LAYERS - 1}, got {len(b)}")
+    out = dict(sd)
+    for i in range(LG_LAYERS - 1):
+        w = torch.randn((1, d), generator=g, dtype=torch.float32) * (weight_gain * math.sqrt(1.0 / d))
+        out[f"token_confidence.{i}.token.0.weight"] = w.contiguous()
+        out[f"token_confidence.{i}.token.0.bias"] = torch.tensor([b[i]], dtype=torch.float32)
+    return out
+
+
 def normalize_lightglue_keys(sd: dict) -> dict:
     """Raw upstream checkpoint names -> module names: ``self_attn.{i}.*`` -> ``transformers.{i}.self_attn.*`` (and
     cross_attn), optional ``matcher.`` prefix dropped - the rename upstream's LightGlue.__init__ applies at load time
