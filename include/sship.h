@@ -255,6 +255,27 @@ int sship_lg_match_batch_device(sship_lg* lg, const float* kp_dev, const int* n_
  *   otherwise; upstream's `stop`), device-synchronising like sship_lg_debug_read.  With the option off every pair reports the layers run. */
 int sship_lg_set_depth_confidence(sship_lg* lg, float depth_confidence);
 int sship_lg_layers_run(sship_lg* lg, int* out_host, int pairs);
+/* Adaptive width (upstream LightGlue's width_confidence / get_pruning_mask; the reference has no counterpart: its ONNX export turns it off).
+ * Per handle, OFF by default; it applies to every call enqueued after it returns, through every entry point, like adaptive depth above.
+ * With width_confidence = w in (0, 1] and min_keypoints = K >= 0, after layer i (i = 0..7, never after the last layer), for every pair
+ * that is still running after the depth decision of layer i (a pair that stops at layer i is matched on the tokens it had during layer i),
+ * and for each of its two images on its own:
+ *   the image is pruned at this layer only if its live count is > K (upstream's pruning_th, an explicit argument here; 0 = always);
+ *   s_t = sigmoid(log_assignment.{i}.matchability(x_t)) for every live token, x = the residual stream after layer i;
+ *   keep_t = s_t > 1 - w (fp32, this form); with adaptive depth also on, keep_t |= c_t <= thr_i with the c and thr_i above (tokens of low
+ *   confidence are never pruned); with depth off there is no second term;
+ *   the kept tokens, in their original order, are the image's tokens for layers i + 1 ..; prune[t] += 1 for every kept token (prune
+ *   starts at 1: upstream's prune0 / prune1);
+ *   if either image of a pair has no token left the pair is finished: matches0 = -1, mscores0 = 0, layers_run = i + 1.
+ * The assignment (log_assignment[layers_run - 1], the unchanged filter) runs on the live sets and is mapped back to keypoint indices;
+ * pruned keypoints get -1 / 0, rows >= n stay -1 / 0.  A pair's result does not depend on the other pairs of the call.
+ * sship_lg_set_width_confidence: w <= 0 turns it off (today's path, bit for bit); NaN, w > 1 or K < 0 -> SSHIP_ERR_INVALID; w > 0 with
+ *   weights that lack any log_assignment.{0..7}.matchability -> SSHIP_ERR_INVALID (the handle keeps its previous setting).  The
+ *   token-confidence heads are needed only when adaptive depth is on.
+ * sship_lg_prune_counts: prune0[0 .. n0) / prune1[0 .. n1) of pair `pair` of the last call, device-synchronising like
+ *   sship_lg_layers_run.  With the option off every keypoint reports 9 (as upstream does). */
+int sship_lg_set_width_confidence(sship_lg* lg, float width_confidence, int min_keypoints);
+int sship_lg_prune_counts(sship_lg* lg, int pair, int32_t* prune0, int n0, int32_t* prune1, int n1);
 /* Test-only introspection of the matcher (no reference counterpart; used by the parity suite to compare the internals
  * with the oracle layer by layer - the product never calls these).
  * sship_lg_debug_set_layers: the NEXT match call on this handle (one-shot) runs only the first n_layers (1..9) transformer
@@ -263,8 +284,10 @@ int sship_lg_layers_run(sship_lg* lg, int* out_host, int pairs);
  *   SSHIP_LG_DEBUG_X    residual stream of sequence `index` (2p = set 0, 2p+1 = set 1 of pair p): out[rows][256]
  *   SSHIP_LG_DEBUG_SIM  assignment similarity md0 md1^T of pair `index`: out[rows][cols]
  *   SSHIP_LG_DEBUG_KPTS normalised keypoints of sequence `index` (src/LightGlue.cc:241-251 on the device): out[rows][2]
- *   SSHIP_LG_DEBUG_ROPE rotary table of sequence `index`: out[rows][64] = 32 (cos, sin) pairs */
-enum { SSHIP_LG_DEBUG_X = 0, SSHIP_LG_DEBUG_SIM = 1, SSHIP_LG_DEBUG_KPTS = 2, SSHIP_LG_DEBUG_ROPE = 3 };
+ *   SSHIP_LG_DEBUG_ROPE rotary table of sequence `index`: out[rows][64] = 32 (cos, sin) pairs
+ *   SSHIP_LG_DEBUG_IND  original keypoint index of each live row of sequence `index`: out[rows][1] (0, 1, 2 .. with adaptive width off)
+ * With adaptive width on, SSHIP_LG_DEBUG_X and SSHIP_LG_DEBUG_ROPE return the COMPACTED stream: row a is keypoint IND[a], rows past the live count are padding. */
+enum { SSHIP_LG_DEBUG_X = 0, SSHIP_LG_DEBUG_SIM = 1, SSHIP_LG_DEBUG_KPTS = 2, SSHIP_LG_DEBUG_ROPE = 3, SSHIP_LG_DEBUG_IND = 4 };
 int sship_lg_debug_set_layers(sship_lg* lg, int n_layers);
 int sship_lg_debug_read(sship_lg* lg, int what, int index, int rows, int cols, float* out);
 /* Test-only: copy one encoder activation of the extractor's LAST call to the host as raw fp16 (channels-last [batch][h_l][w_l][c_l]),

@@ -282,6 +282,9 @@ public:
     if (depth_confidence_ > 0.f && sship_lg_set_depth_confidence(lg_, depth_confidence_) != SSHIP_OK) {
       last_error_ = sship_last_error(); sship_lg_destroy(lg_); lg_ = nullptr; return false;
     }
+    if (width_confidence_ > 0.f && sship_lg_set_width_confidence(lg_, width_confidence_, prune_min_keypoints_) != SSHIP_OK) {
+      last_error_ = sship_last_error(); sship_lg_destroy(lg_); lg_ = nullptr; return false;
+    }
     return true;
   }
   std::shared_ptr<LightGlueEngine> shared_engine() const { return engine_; }
@@ -300,6 +303,28 @@ public:
     int n = 0;
     if (!lg_ || sship_lg_layers_run(lg_, &n, 1) != SSHIP_OK) return 0;
     return n;
+  }
+
+  // Adaptive width (upstream LightGlue's width_confidence, prune_min_keypoints = its pruning_th; include/sship.h): <= 0 off (the
+  // default), (0, 1] on.  Before initialize() the values are kept and applied there; after it, they apply to the next match.  false
+  // (last_error()) for NaN, > 1, a negative prune_min_keypoints, or weights without the early matchability heads.
+  bool set_width_confidence(float width_confidence, int prune_min_keypoints = 0) {
+    if (lg_ && sship_lg_set_width_confidence(lg_, width_confidence, prune_min_keypoints) != SSHIP_OK) { last_error_ = sship_last_error(); return false; }
+    if (!lg_ && (!(width_confidence <= 1.f) || prune_min_keypoints < 0)) {
+      last_error_ = "set_width_confidence: width_confidence must be <= 1 and prune_min_keypoints >= 0"; return false;
+    }
+    width_confidence_ = width_confidence;
+    prune_min_keypoints_ = prune_min_keypoints;
+    return true;
+  }
+  // upstream's prune0 / prune1 of the last match: 1 + the pruning steps each of the n0 / n1 keypoints survived (9 with the option off)
+  bool prune_counts(int n0, int n1, std::vector<int32_t>& prune0, std::vector<int32_t>& prune1) {
+    prune0.assign(n0 > 0 ? n0 : 0, 0); prune1.assign(n1 > 0 ? n1 : 0, 0);
+    if (!lg_ || sship_lg_prune_counts(lg_, 0, prune0.data(), (int)prune0.size(), prune1.data(), (int)prune1.size()) != SSHIP_OK) {
+      if (lg_) last_error_ = sship_last_error();
+      return false;
+    }
+    return true;
   }
 
   // 5-argument form (src/LightGlue.cc:285-324): false for an uninitialised matcher or an empty set.
@@ -359,6 +384,8 @@ private:
   std::shared_ptr<LightGlueEngine> engine_;
   sship_lg* lg_ = nullptr;
   float depth_confidence_ = -1.f;
+  float width_confidence_ = -1.f;
+  int prune_min_keypoints_ = 0;
   std::string last_error_;
 };
 typedef std::shared_ptr<LightGlue> LightGluePtr;

@@ -35,6 +35,16 @@ public:
     return ok;
   }
   int layers_run() { return impl_.layers_run(); }
+  // Upstream LightGlue's adaptive width (point pruning; no counterpart in the TensorRT runner either): <= 0 off (default), (0, 1] on;
+  // an image is pruned only while it has more than prune_min_keypoints live keypoints.
+  bool set_width_confidence(float width_confidence, int prune_min_keypoints = 0) {
+    const bool ok = impl_.set_width_confidence(width_confidence, prune_min_keypoints);
+    if (!ok) SLOG_ERROR("LightGlue(HIP): {}", impl_.last_error());
+    return ok;
+  }
+  bool prune_counts(int n0, int n1, std::vector<int32_t>& prune0, std::vector<int32_t>& prune1) {
+    return impl_.prune_counts(n0, n1, prune0, prune1);
+  }
 
   bool match(const std::vector<cv::KeyPoint>& kp0, const cv::Mat& d0, const std::vector<cv::KeyPoint>& kp1,
              const cv::Mat& d1, MatchResult& result) {

@@ -91,6 +91,8 @@ _SIGS = {
     "sship_lg_match_batch_device": (ip, [vp, vp, vp, vp, ip, vp, vp, vp]),
     "sship_lg_set_depth_confidence": (ip, [vp, fp]),
     "sship_lg_layers_run": (ip, [vp, vp, ip]),
+    "sship_lg_set_width_confidence": (ip, [vp, fp, ip]),
+    "sship_lg_prune_counts": (ip, [vp, ip, vp, ip, vp, ip]),
     "sship_lg_debug_set_layers": (ip, [vp, ip]),
     "sship_lg_debug_read": (ip, [vp, ip, ip, ip, ip, vp]),
     "sship_filter_matches": (ip, [vp, vp, ip, vp, vp, vp]),

@@ -1298,6 +1298,10 @@ struct sship_lg_weights {
   float* head_b = nullptr;     // [9][256], scaled likewise
   float* head_mw = nullptr;    // [9][256] matchability weights
   float* head_mb = nullptr;    // [9]
+  // adaptive width (sship_lg_set_width_confidence) needs log_assignment.{0..7}.matchability only: head_mw / head_mb are uploaded when the
+  // file holds those, whether or not the rest of the depth heads is there
+  bool has_width = false;
+  std::string width_missing;
 };
 static void lg_weights_free(sship_lg_weights* w) {
   for (int i = 0; i < kLgLayers; ++i) {
@@ -1481,7 +1485,25 @@ extern "C" int sship_lg_weights_load(const char* path, sship_lg_weights** out) {
           (rc = upload_floats(hmb.data(), hmb.size(), &w->head_mb)))
         return bail(rc, g_err);
       w->has_depth = true;
+      w->has_width = true;
       w->depth_missing.clear();
+    } else {
+      // adaptive width alone: the eight matchability heads
+      bool okw = true;
+      for (int i = 0; i < kLgLayers - 1 && okw; ++i) {
+        const std::string pa = "log_assignment." + std::to_string(i) + ".matchability.";
+        auto iw = sd.find(pa + "weight"), ib = sd.find(pa + "bias");
+        if (iw == sd.end() || iw->second.shape != std::vector<int64_t>({1, 256})) { w->width_missing = pa + "weight"; okw = false; break; }
+        if (ib == sd.end() || ib->second.shape != std::vector<int64_t>({1})) { w->width_missing = pa + "bias"; okw = false; break; }
+        memcpy(hmw.data() + i * 256, iw->second.data.data(), 256 * 4);
+        hmb[i] = ib->second.data[0];
+      }
+      if (okw) {
+        int rc = 0;
+        if ((rc = upload_floats(hmw.data(), hmw.size(), &w->head_mw)) || (rc = upload_floats(hmb.data(), hmb.size(), &w->head_mb)))
+          return bail(rc, g_err);
+        w->has_width = true;
+      }
     }
   }
   *out = w;
@@ -1516,6 +1538,12 @@ struct sship_lg {
   bool last_adaptive = false;
   int last_layers = kLgLayers;
   DevBuf dep;
+  // adaptive width (sship_lg_set_width_confidence): <= 0 = off.  wid: the per-call state of kernels.h LgWidth for every pair;
+  // m0c / ms0c: the matches of the live sets before they are mapped back through ind
+  float width_conf = -1.f;
+  int width_min_kp = 0;
+  bool last_width = false;
+  DevBuf wid, m0c, ms0c;
   PinBuf h_kp, h_lens, h_m0, h_ms0, h_desc;
   // throughput batches run their transformer layers as two half-batches on two streams (lg_forward): the second stream and the
   // fork / join events
@@ -1526,6 +1554,10 @@ struct sship_lg {
 
 // Adaptive depth state layout in sship_lg::dep (ints): cnt [P][8] | layers_run [P] | lens_live [2P] | live [P + kAux + 1] | tickets [kAux + 1]
 static size_t lg_dep_ints(int P) { return (size_t)P * 8 + P + 2 * (size_t)P + P + sship_lg::kAux + 1 + sship_lg::kAux + 1; }
+// Adaptive width state layout in sship_lg::wid (ints): wlen [2P] | chg [2P] | ind [2P][NP] | prune [2P][NP] | tiles | rtiles, the tile lists
+// sized for 32-token tiles: [P * 2 NP / 32 + kAux + 1] each (a count in front of every launch group's list)
+static size_t lg_wid_list_ints(int P, int NP) { return (size_t)P * (2 * NP / 32) + sship_lg::kAux + 1; }
+static size_t lg_wid_ints(int P, int NP) { return 4 * (size_t)P + 4 * (size_t)P * NP + 2 * lg_wid_list_ints(P, NP); }
 extern "C" int sship_lg_create(sship_lg_weights* w, int image_w, int image_h, int max_kp, int max_pairs, sship_lg** out) {
   bind_thread();
   if (!w || !out || image_w <= 0 || image_h <= 0) return fail(SSHIP_ERR_INVALID, "lg_create: bad arguments");
@@ -1560,6 +1592,9 @@ extern "C" int sship_lg_create(sship_lg_weights* w, int image_w, int image_h, in
   SSHIP_HIP_CHECK(lg->h_ms0.ensure((size_t)max_kp * 4));
   SSHIP_HIP_CHECK(lg->h_desc.ensure(2 * (size_t)max_kp * 256 * 2));
   SSHIP_HIP_CHECK(lg->dep.ensure(lg_dep_ints(max_pairs) * 4));
+  SSHIP_HIP_CHECK(lg->wid.ensure(lg_wid_ints(max_pairs, lg->NP) * 4));
+  SSHIP_HIP_CHECK(lg->m0c.ensure((size_t)max_pairs * max_kp * 4));
+  SSHIP_HIP_CHECK(lg->ms0c.ensure((size_t)max_pairs * max_kp * 4));
   // q/k/vt/ctx of padded tokens must stay finite: start from zeros (prep rewrites x every call).
   SSHIP_HIP_CHECK(hipMemset(lg->q.p, 0, lg->q.bytes));
   SSHIP_HIP_CHECK(hipMemset(lg->k.p, 0, lg->k.bytes));
@@ -1641,6 +1676,17 @@ extern "C" int sship_lg_debug_read(sship_lg* lg, int what, int index, int rows, 
       SSHIP_HIP_CHECK(hipMemcpy(out, lg->rope.as<float>() + (size_t)index * NP * 64, (size_t)rows * 256, hipMemcpyDeviceToHost));
       return SSHIP_OK;
     }
+    case SSHIP_LG_DEBUG_IND: {  // original keypoint index of the rows of sequence `index` (identity when adaptive width was off)
+      if (index >= S || cols != 1) return fail(SSHIP_ERR_INVALID, "lg_debug_read(IND): index/cols");
+      if (!lg->last_width) {
+        for (int i = 0; i < rows; ++i) out[i] = (float)i;
+        return SSHIP_OK;
+      }
+      std::vector<int> tmp((size_t)rows);
+      SSHIP_HIP_CHECK(hipMemcpy(tmp.data(), lg->wid.as<int>() + 4 * (size_t)lg->max_pairs + (size_t)index * NP, tmp.size() * 4, hipMemcpyDeviceToHost));
+      for (int i = 0; i < rows; ++i) out[i] = (float)tmp[i];
+      return SSHIP_OK;
+    }
     default: return fail(SSHIP_ERR_INVALID, "lg_debug_read: unknown selector");
   }
 }
@@ -1686,6 +1732,52 @@ extern "C" int sship_lg_layers_run(sship_lg* lg, int* out_host, int pairs) {
   return SSHIP_OK;
 }
 
+// the width state of launch group `part` (pairs [p0, p0 + np))
+static LgWidth lg_width_state(sship_lg* lg, int p0, int part) {
+  const size_t P = lg->max_pairs, NP = lg->NP;
+  int* b = lg->wid.as<int>();
+  int* wlen = b;
+  int* chg = wlen + 2 * P;
+  int* ind = chg + 2 * P;
+  int* prune = ind + 2 * P * NP;
+  int* tiles = prune + 2 * P * NP;
+  int* rtiles = tiles + lg_wid_list_ints((int)P, (int)NP);
+  // tile lists of consecutive groups never overlap: a group's list holds at most np * 2 NP / 32 tiles behind its count
+  const size_t lo = (size_t)p0 * (2 * NP / 32) + part;
+  return LgWidth{wlen + 2 * (size_t)p0, chg + 2 * (size_t)p0, ind + 2 * (size_t)p0 * NP, prune + 2 * (size_t)p0 * NP, tiles + lo, rtiles + lo};
+}
+extern "C" int sship_lg_set_width_confidence(sship_lg* lg, float width_confidence, int min_keypoints) {
+  bind_thread();
+  if (!lg) return fail(SSHIP_ERR_INVALID, "lg_set_width_confidence: null handle");
+  if (std::isnan(width_confidence) || width_confidence > 1.f || min_keypoints < 0)
+    return fail(SSHIP_ERR_INVALID, "lg_set_width_confidence: width_confidence must be <= 1 (<= 0 turns adaptive width off) and min_keypoints >= 0");
+  if (width_confidence > 0.f && !lg->w->has_width)
+    return fail(SSHIP_ERR_INVALID, "lg_set_width_confidence: the weights hold no early matchability heads (missing '" +
+                                       (lg->w->width_missing.empty() ? lg->w->depth_missing : lg->w->width_missing) +
+                                       "'); adaptive width needs log_assignment.{0..7}.matchability");
+  lg->width_conf = width_confidence > 0.f ? width_confidence : -1.f;
+  lg->width_min_kp = min_keypoints;
+  return SSHIP_OK;
+}
+extern "C" int sship_lg_prune_counts(sship_lg* lg, int pair, int32_t* prune0, int n0, int32_t* prune1, int n1) {
+  bind_thread();
+  if (!lg || pair < 0 || n0 < 0 || n1 < 0 || (n0 > 0 && !prune0) || (n1 > 0 && !prune1))
+    return fail(SSHIP_ERR_INVALID, "lg_prune_counts: bad arguments");
+  if (pair >= lg->last_pairs) return fail(SSHIP_ERR_INVALID, "lg_prune_counts: pair exceeds the pairs of the last call");
+  if (n0 > lg->max_kp || n1 > lg->max_kp) return fail(SSHIP_ERR_INVALID, "lg_prune_counts: n exceeds max_keypoints");
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());
+  if (!lg->last_width) {  // upstream reports n_layers for every keypoint when it does not prune
+    for (int i = 0; i < n0; ++i) prune0[i] = kLgLayers;
+    for (int i = 0; i < n1; ++i) prune1[i] = kLgLayers;
+    return SSHIP_OK;
+  }
+  const size_t P = lg->max_pairs, NP = lg->NP;
+  const int* pr = lg->wid.as<int>() + 4 * P + 2 * P * NP;
+  if (n0 > 0) SSHIP_HIP_CHECK(hipMemcpy(prune0, pr + (size_t)(2 * pair) * NP, (size_t)n0 * 4, hipMemcpyDeviceToHost));
+  if (n1 > 0) SSHIP_HIP_CHECK(hipMemcpy(prune1, pr + (size_t)(2 * pair + 1) * NP, (size_t)n1 * 4, hipMemcpyDeviceToHost));
+  return SSHIP_OK;
+}
+
 // The matcher proper: `pairs` problems, everything on the device.  9 x (SelfBlock x2 images, CrossBlock), then
 // log_assignment[8] + filter_matches.
 static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_stride, const int* lens,
@@ -1704,13 +1796,20 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
   lg->last_pairs = pairs;
   // adaptive depth: layer i's token confidence after its CrossBlock, the running set for layers i + 1 ..; the exit head after the join
   const bool adaptive = lg->depth_conf > 0.f;
+  // adaptive width: after the depth decision of layer i the running pairs drop their unmatchable tokens; layers i + 1 .. run on the rest
+  const bool width = lg->width_conf > 0.f;
+  const float keep_thr = 1.0f - lg->width_conf;
 #if SSHIP_DEV_SWITCHES
   // the developer kernels that do not know the running set: refuse rather than ignore the setting
   if (adaptive && ((dev_env("SUPERSLAM_HIP_FFN") && atoi(dev_env("SUPERSLAM_HIP_FFN")) == 16) ||
                    (dev_env("SUPERSLAM_HIP_ATTN") && std::string(dev_env("SUPERSLAM_HIP_ATTN")) == "res")))
     return fail(SSHIP_ERR_INVALID, "lightglue: adaptive depth is not supported by the 16-wave FFN or the LDS-resident-key attention");
+  if (width && ((dev_env("SUPERSLAM_HIP_FFN") && atoi(dev_env("SUPERSLAM_HIP_FFN")) == 16) ||
+                (dev_env("SUPERSLAM_HIP_ATTN") && std::string(dev_env("SUPERSLAM_HIP_ATTN")) == "res")))
+    return fail(SSHIP_ERR_INVALID, "lightglue: adaptive width is not supported by the 16-wave FFN or the LDS-resident-key attention");
 #endif
-  lg->last_adaptive = adaptive;
+  lg->last_adaptive = adaptive || width;  // layers_run comes from the device in both modes
+  lg->last_width = width;
   lg->last_layers = lg->debug_layers;
   // 3 launches per block: [projection fused into the previous FFN's tail] -> attention -> FFN(+ next projection).
   static const bool igemm_qkv0 = dev_env("SUPERSLAM_HIP_LG_QKV0") && std::string(dev_env("SUPERSLAM_HIP_LG_QKV0")) == "igemm";  // A/B
@@ -1719,11 +1818,14 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
   auto layers = [&](int p0, int np, hipStream_t st, bool shared_gpu, int part) -> int {
     const LgDims ds{2 * np, lg->NP};
     const LgDepth dep = lg_depth_state(lg, p0, part);
+    const LgWidth wd = lg_width_state(lg, p0, part);
     const size_t tok = (size_t)2 * p0 * lg->NP;
     _Float16 *xs = x + tok * 256, *qs = q + tok * 256, *ks = k + tok * 256, *vs = vt + tok * 256, *cs = ctx + tok * 256;
-    const float* rs = rope + tok * 64;
+    float* rs = rope + tok * 64;
     const int* ls = lens + 2 * p0;
-    if (adaptive) launch_lg_depth_init(ls, np, dep, st);
+    if (adaptive || width) launch_lg_depth_init(ls, np, dep, st);
+    if (width) launch_lg_width_init(ls, lg->NP, np, wd, st);
+    const int tile_tokens = lg_ffn_tile_tokens(ds.S * ds.NP);
     // what each FFN launch streams (w0, w3, the fused projection): handed to the launch BEFORE it as a prefetch hint (latency mode)
     auto self_w = [&](int i, const ConvW** o) { o[0] = &w->ffn0_s[i]; o[1] = &w->ffn3_s[i]; o[2] = &w->cqkv_t[i]; };
     auto cross_w = [&](int i, const ConvW** o) { o[0] = &w->ffn0_c[i]; o[1] = &w->ffn3_c[i]; o[2] = i + 1 < kLgLayers ? &w->qkv_t[i + 1] : &w->final_t; };
@@ -1737,25 +1839,36 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
     for (int i = 0; i < n_layers; ++i) {
       // adaptive depth, layers >= 1: the attention launches see the counts of running pairs only (0 for stopped ones: their
       // workgroups return at once), the FFN launches walk the tiles of running pairs only.  Layer 0 runs as without it.
-      const int* la = adaptive && i > 0 ? dep.lens_live : ls;
-      const int* live = adaptive && i > 0 ? dep.live : nullptr;
+      // adaptive width, layers >= 1: lens_live holds the LIVE counts of running pairs, and the FFN launches walk the list of live tiles
+      const int* la = (adaptive || width) && i > 0 ? dep.lens_live : ls;
+      const int* live = i > 0 ? (width ? wd.tiles : adaptive ? dep.live : nullptr) : nullptr;
+      const int lm = width ? 2 : 1;
       // SelfBlock (both images of every pair in one launch); its FFN also emits CrossBlock's [to_qk | to_v]
       launch_lg_attention(qs, ks, vs, la, ds, false, cs, st, shared_gpu);
       cross_w(i, pf);
       launch_lg_ffn(w->ffn0_s[i], w->ffn3_s[i], w->ln_g_s[i], w->ln_b_s[i], cs, xs, ds, &w->cqkv_t[i], true, /*rope_segs=*/0,
-                    /*t_seg=*/1, rs, qs, ks, vs, nullptr, nullptr, 0.f, nullptr, st, pf, live);
+                    /*t_seg=*/1, rs, qs, ks, vs, nullptr, nullptr, 0.f, nullptr, st, pf, live, lm);
       // CrossBlock (qk shared by both directions; sequence s attends to s^1); its FFN emits the next layer's Wqkv,
       // or final_proj + matchability after the last layer
       launch_lg_attention(qs, qs, vs, la, ds, true, cs, st, shared_gpu);
       if (i + 1 < kLgLayers) {
         self_w(i + 1, pf);
         launch_lg_ffn(w->ffn0_c[i], w->ffn3_c[i], w->ln_g_c[i], w->ln_b_c[i], cs, xs, ds, &w->qkv_t[i + 1], true, 2, 2, rs, qs, ks,
-                      vs, nullptr, nullptr, 0.f, nullptr, st, pf, live);
-        if (adaptive)  // token confidence of layer i and the stop rule (reads x after layer i)
-          launch_lg_depth_conf(xs, ls, lg->NP, np, w->tc_w + i * 256, w->tc_b[i], lg_depth_threshold(i), lg->depth_conf, i, dep, st);
+                      vs, nullptr, nullptr, 0.f, nullptr, st, pf, live, lm);
+        if (adaptive)  // token confidence of layer i and the stop rule (reads x after layer i; with width on, of the live tokens)
+          launch_lg_depth_conf(xs, width ? wd.wlen : ls, lg->NP, np, w->tc_w + i * 256, w->tc_b[i], lg_depth_threshold(i), lg->depth_conf, i, dep, st);
+        if (width) {
+          // the pruning step of layer i for the pairs still running, then the counts / tile lists of layer i + 1.  The FFN above
+          // projected layer i + 1's Q / K / V from the rows as they were: the sequences that lost tokens are projected again.
+          launch_lg_width_prune(xs, rs, lg->NP, np, w->head_mw + i * 256, w->head_mb + i, keep_thr, lg->width_min_kp,
+                                adaptive ? w->tc_w + i * 256 : nullptr, w->tc_b[i], lg_depth_threshold(i), dep, wd, st);
+          launch_lg_width_publish(lg->NP, np, tile_tokens, i, dep, wd, st);
+          if (i + 1 < n_layers)
+            SSHIP_HIP_CHECK(launch_lg_proj_heads(w->qkv_t[i + 1], xs, ds, 2, 2, rs, qs, ks, vs, st, nullptr, wd.rtiles));
+        }
       } else
         launch_lg_ffn(w->ffn0_c[i], w->ffn3_c[i], w->ln_g_c[i], w->ln_b_c[i], cs, xs, ds, &w->final_t, false, 0, 0, rs, qs, ks, vs,
-                      lg->md.as<_Float16>() + tok * 256, w->match_w, w->match_b, lg->logsig.as<float>() + tok, st, nullptr, live);
+                      lg->md.as<_Float16>() + tok * 256, w->match_w, w->match_b, lg->logsig.as<float>() + tok, st, nullptr, live, lm);
     }
     SSHIP_HIP_CHECK(hipGetLastError());
     return SSHIP_OK;
@@ -1807,6 +1920,18 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
   if (adaptive)  // md / logsig of the pairs that stopped early, from the assignment head of the layer they stopped after
     launch_lg_exit_head(x, lg->NP, pairs, lg->dep.as<int>() + (size_t)lg->max_pairs * 8, w->head_wt, w->head_b, w->head_mw, w->head_mb,
                         lg->md.as<_Float16>(), lg->logsig.as<float>(), s);
+  if (width) {
+    // the assignment of the live sets (row a = the a-th surviving keypoint), then back to keypoint indices through ind
+    const int* wlen = lg->wid.as<int>();
+    launch_lg_assign(lg->md.as<_Float16>(), lg->logsig.as<float>(), wlen, d, lg->ws.as<float>(), lg->sim.as<float>(), lg->max_kp,
+                     lg->m0c.as<int32_t>(), lg->ms0c.as<float>(), 0.1f /* filter_threshold */, 0, s);
+    SSHIP_HIP_CHECK(hipMemsetAsync(m0, 0xff, (size_t)pairs * lg->max_kp * 4, s));
+    SSHIP_HIP_CHECK(hipMemsetAsync(ms0, 0, (size_t)pairs * lg->max_kp * 4, s));
+    launch_lg_width_scatter(wlen, wlen + 4 * (size_t)lg->max_pairs, lg->NP, pairs, lg->max_kp, lg->m0c.as<int32_t>(), lg->ms0c.as<float>(), m0, ms0, s);
+    SSHIP_HIP_CHECK(hipGetLastError());
+    g_timer.mark("fe_lg_stereo_match:assign_filter", s);
+    return SSHIP_OK;
+  }
   // log-assignment + mutual filter straight from md (lg_kernels.hip: k_assign_stream); lg->sim is the partials' scratch
   launch_lg_assign(lg->md.as<_Float16>(), lg->logsig.as<float>(), lens, d, lg->ws.as<float>(), lg->sim.as<float>(), lg->max_kp, m0, ms0,
                    0.1f /* filter_threshold */, 0, s);

@@ -129,11 +129,13 @@ void launch_lg_attention_res(const _Float16* q, const _Float16* k, const _Float1
                              _Float16* ctx, hipStream_t s);
 // prefetch (both launches below): up to three packed layers the NEXT FFN launch streams; latency mode pulls them into L2 with surplus workgroups
 hipError_t launch_lg_proj_heads(const ConvW& next, _Float16* x, LgDims d, int rope_segs, int t_seg, const float* rope, _Float16* q,
-                                _Float16* k, _Float16* vt, hipStream_t s, const ConvW* const* prefetch = nullptr);
+                                _Float16* k, _Float16* vt, hipStream_t s, const ConvW* const* prefetch = nullptr, const int* tiles = nullptr);
 void launch_lg_ffn(const ConvW& w0, const ConvW& w3, const float* gamma, const float* beta, const _Float16* ctx,
                    _Float16* x, LgDims d, const ConvW* next, bool heads, int rope_segs, int t_seg, const float* rope,
                    _Float16* q, _Float16* k, _Float16* vt, _Float16* out, const float* match_w, float match_b,
-                   float* logsig, hipStream_t s, const ConvW* const* prefetch = nullptr, const int* live = nullptr);
+                   float* logsig, hipStream_t s, const ConvW* const* prefetch = nullptr, const int* live = nullptr, int live_mode = 1);
+// tokens per tile (32 | 64) of the FFN / projection launch over `tokens` tokens: the unit of a tile list handed to it (live_mode 2, `tiles`)
+int lg_ffn_tile_tokens(int tokens);
 // Adaptive depth (sship_lg_set_depth_confidence).  State of the pairs [p0, p0 + np) of one launch group, every pointer offset to p0:
 struct LgDepth {
   int* cnt;         // [np][8]: valid tokens with confidence < thr_i after layer i (integer atomics: exact, order-independent)
@@ -150,6 +152,26 @@ void launch_lg_depth_conf(const _Float16* x, const int* lens, int NP, int np, co
 // wt [9][256 in][256 out] fp32, bias [9][256], mw [9][256], mb [9]
 void launch_lg_exit_head(const _Float16* x, int NP, int pairs, const int* layers_run, const float* wt, const float* bias, const float* mw,
                          const float* mb, _Float16* md, float* logsig, hipStream_t s);
+// Adaptive width (sship_lg_set_width_confidence).  State of the pairs [p0, p0 + np) of one launch group, every pointer offset to p0:
+struct LgWidth {
+  int* wlen;    // [2 np]: live tokens of every sequence (a stopped or emptied pair keeps the counts it was matched on)
+  int* chg;     // [2 np]: 1 if the sequence lost tokens at the last prune launch (its next-layer Q/K/V are projected again)
+  int* ind;     // [2 np][NP]: original keypoint index of every live row
+  int* prune;   // [2 np][NP], by original index: 1 + the pruning steps the keypoint survived (upstream's prune0 / prune1)
+  int* tiles;   // [1 + tiles]: count, then the tiles that hold live tokens of running pairs (what the FFN launches walk)
+  int* rtiles;  // [1 + tiles]: count, then the tiles of the sequences with chg = 1 (what the re-projection walks)
+};
+void launch_lg_width_init(const int* lens, int NP, int np, LgWidth wd, hipStream_t s);
+// the pruning step of one layer for every running pair: one workgroup per sequence decides, compacts x / rope / ind in place (forward
+// moves only) and zeroes the vacated rows.  keep = sigmoid(mw . x + mb) > keep_thr, or (tcw != null: depth on) sigmoid(tcw . x + tcb) <= thr
+void launch_lg_width_prune(_Float16* x, float* rope, int NP, int np, const float* mw, const float* mb, float keep_thr, int min_kp,
+                           const float* tcw, float tcb, float thr, LgDepth dep, LgWidth wd, hipStream_t s);
+// after the prune launch of layer `layer`: a pair with an emptied image is finished (layers_run = layer + 1); lens_live (0 for pairs
+// that are not running), the two tile lists in tiles of `tile_tokens` tokens
+void launch_lg_width_publish(int NP, int np, int tile_tokens, int layer, LgDepth dep, LgWidth wd, hipStream_t s);
+// matches of the live sets (mc / msc, [pairs][max_kp]) -> the caller's arrays through ind: pruned keypoints and rows >= n get -1 / 0
+void launch_lg_width_scatter(const int* wlen, const int* ind, int NP, int pairs, int max_kp, const int32_t* mc, const float* msc,
+                             int32_t* matches0, float* mscores0, hipStream_t s);
 void launch_lg_sim(const _Float16* md, const int* lens, LgDims d, float* sim, hipStream_t s);
 void launch_lg_assign(const _Float16* md, const float* logsig, const int* lens, LgDims d, float* ws, float* pcol, int max_kp,
                       int32_t* matches0, float* mscores0, float thr, int stage, hipStream_t s);

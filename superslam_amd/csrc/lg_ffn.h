@@ -43,6 +43,7 @@ struct FfnTail {
   int pf_bytes[3];
   // adaptive depth (the AD instantiations only): live[0] = pairs of this launch still running, live[1 ..] their indices relative
   // to the launch; a pair's tiles_per_pair tiles are consecutive.  Written by k_lg_depth_conf, complete at the kernel boundary.
+  // adaptive width (the AD = 2 instantiations): live[0] = tiles to walk, live[1 ..] their indices (k_lg_width_publish); tiles_per_pair unused.
   const int* live;
   int tiles_per_pair;
 };

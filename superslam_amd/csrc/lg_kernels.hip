@@ -615,18 +615,22 @@ void launch_lg_attention(const _Float16* q, const _Float16* k, const _Float16* v
 // (barrier, residual operand) are not address-path time (tail MFMA 5.1 -> 4.25 k / 9.3 -> 7.6 k, residual unchanged), and barriers
 // that wait for LDS traffic only (__syncthreads() drains vmcnt too and would stall every wave on its own prefetch).
 __device__ __forceinline__ void ffn_bar_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-// adaptive depth (AD instantiations): a launch walks only the tiles of its running pairs.  li = index among those tiles.
-template <bool AD>
+// adaptive depth (AD = 1 instantiations): a launch walks only the tiles of its running pairs.  li = index among those tiles.
+// adaptive width (AD = 2 instantiations): a launch walks a tile list built on the device (k_lg_width_publish): live[0] tiles, live[1 ..]
+// their indices in this launch's tile size.  AD = 0: every tile.
+template <int AD>
 __device__ __forceinline__ int ffn_live_tiles(const FfnTail& t) {
-  if constexpr (AD) return t.live[0] * t.tiles_per_pair;
+  if constexpr (AD == 1) return t.live[0] * t.tiles_per_pair;
+  else if constexpr (AD == 2) return t.live[0];
   else return t.ntiles;
 }
-template <bool AD>
+template <int AD>
 __device__ __forceinline__ int ffn_tile_of(const FfnTail& t, int li) {
-  if constexpr (AD) return t.live[1 + li / t.tiles_per_pair] * t.tiles_per_pair + li % t.tiles_per_pair;
+  if constexpr (AD == 1) return t.live[1 + li / t.tiles_per_pair] * t.tiles_per_pair + li % t.tiles_per_pair;
+  else if constexpr (AD == 2) return t.live[1 + li];
   else return li;
 }
-template <int NEXT_MT, bool HEADS, int NT, bool PROJ, bool AD = false>
+template <int NEXT_MT, bool HEADS, int NT, bool PROJ, int AD = 0>
 __global__ __launch_bounds__(512, 2) void k_lg_ffn(const _Float16* __restrict__ ctx, const _Float16* __restrict__ w0p,
                                                 const float* __restrict__ b0, const float* __restrict__ gamma,
                                                 const float* __restrict__ beta, const _Float16* __restrict__ w3p,
@@ -1074,7 +1078,7 @@ __global__ __launch_bounds__(512, 2) void k_lg_ffn(const _Float16* __restrict__ 
   stamp(10);
   }  // tile loop
 }
-template <int NEXT_MT, bool HEADS, int NT, bool PROJ, bool AD = false, typename... A>
+template <int NEXT_MT, bool HEADS, int NT, bool PROJ, int AD = 0, typename... A>
 static hipError_t launch_ffn_nt(int tokens, int extra_wg, hipStream_t s, A... args) {
   constexpr size_t smem = (size_t)(NT <= 2 ? 2 : 1) * NT * 32 * kFfnLd * 2 + 16 * NT * 32 * 4 + 1792 * 4;
   static_assert(smem <= 163840, "LDS budget");
@@ -1105,7 +1109,7 @@ static void ffn_trace_report(unsigned long long* dev, int nwg, int next_mt, hipS
   for (int i = 0; i < 10; ++i) { fprintf(stderr, " %s=%.0f", names[i], sum[i] / cnt); tot += sum[i] / cnt; }
   fprintf(stderr, " | tile=%.0f clk\n", tot);
 }
-template <int NEXT_MT, bool HEADS, bool AD = false, typename... A>
+template <int NEXT_MT, bool HEADS, int AD = 0, typename... A>
 static hipError_t launch_ffn(int nt, int tokens, int extra_wg, hipStream_t s, A... args) {
   // 64-token tiles for throughput, 32-token tiles when the launch cannot even give half of the CUs a workgroup (a few
   // pairs: twice the workgroups in flight, half the MFMA work per weight stream).  128 tokens measured 9 % slower end to
@@ -1156,7 +1160,7 @@ __device__ __forceinline__ f16x_t mfma32_abl(h8_t a, h8_t b, f16x_t c) {
     return mfma32(a, b, c);
   }
 }
-template <int NEXT_MT, bool HEADS, bool PROJ, bool AD = false>
+template <int NEXT_MT, bool HEADS, bool PROJ, int AD = 0>
 __global__ __launch_bounds__(256, 2) void k_lg_ffn4(const _Float16* __restrict__ ctx, const _Float16* __restrict__ w0p,
                                                     const float* __restrict__ b0, const float* __restrict__ gamma,
                                                     const float* __restrict__ beta, const _Float16* __restrict__ w3p,
@@ -1596,7 +1600,7 @@ __global__ __launch_bounds__(256, 2) void k_lg_ffn4(const _Float16* __restrict__
   stamp(11);
   }  // tile loop
 }
-template <int NEXT_MT, bool HEADS, bool PROJ, bool AD = false, typename... A>
+template <int NEXT_MT, bool HEADS, bool PROJ, int AD = 0, typename... A>
 static hipError_t launch_ffn4(int tokens, hipStream_t s, A... args) {
   constexpr size_t smem = (size_t)64 * kFfnLd * 2 + 8 * 64 * 4 + (1792 + 768 + 512) * 4;  // 80,896 B: two workgroups per CU
   static_assert(2 * smem <= 163840, "two workgroups must fit the CU's LDS");
@@ -1667,14 +1671,20 @@ static int ffn_prefetch_setup(FfnTail& t, int n_main, const ConvW* const* pf) {
   return kPfWg;
 }
 
+// 32-token N-tiles per workgroup tile of the 8-wave kernel: 2 for throughput, 1 when the launch cannot give half of the CUs a workgroup
+static int ffn_nt(int tokens) {
+  static const int nt_env = dev_env("SUPERSLAM_HIP_FFN_NT") ? atoi(dev_env("SUPERSLAM_HIP_FFN_NT")) : 0;  // A/B: 1 | 2
+  return nt_env == 1 || nt_env == 2 ? nt_env : (tokens / 64 < cu_count() / 2 ? 1 : 2);
+}
+// tokens per tile of the FFN launch over `tokens` tokens (what a tile list for it counts in)
+int lg_ffn_tile_tokens(int tokens) { return use_ffn4(tokens) ? 64 : ffn_nt(tokens) * 32; }
 void launch_lg_ffn(const ConvW& w0, const ConvW& w3, const float* gamma, const float* beta, const _Float16* ctx,
                    _Float16* x, LgDims d, const ConvW* next, bool heads, int rope_segs, int t_seg, const float* rope,
                    _Float16* q, _Float16* k, _Float16* vt, _Float16* out, const float* match_w, float match_b,
-                   float* logsig, hipStream_t s, const ConvW* const* prefetch, const int* live) {
+                   float* logsig, hipStream_t s, const ConvW* const* prefetch, const int* live, int live_mode) {
   const int tokens = d.S * d.NP;
   FfnTail t{};
-  static const int nt_env = dev_env("SUPERSLAM_HIP_FFN_NT") ? atoi(dev_env("SUPERSLAM_HIP_FFN_NT")) : 0;  // A/B: 1 | 2
-  const int nt = nt_env == 1 || nt_env == 2 ? nt_env : (tokens / 64 < cu_count() / 2 ? 1 : 2);  // 32-token N-tiles per workgroup tile
+  const int nt = ffn_nt(tokens);  // 32-token N-tiles per workgroup tile
   t.ntiles = tokens / (nt * 32);
   static const bool trace_on = dev_env("SSHIP_FFN_TRACE") != nullptr;
   static unsigned long long* trace_buf = nullptr;
@@ -1702,39 +1712,43 @@ void launch_lg_ffn(const ConvW& w0, const ConvW& w3, const float* gamma, const f
     return;
   }
 #endif
-  // live != null (adaptive depth): the AD instantiations, which walk the tiles of the running pairs only (same tile math)
+  // live != null: the AD instantiations (same tile math).  live_mode 1 (adaptive depth): the tiles of the running pairs;
+  // live_mode 2 (adaptive width): the tile list of k_lg_width_publish, in the tile size lg_ffn_tile_tokens() reports for this launch
   t.live = live;
+  const int ad = live ? live_mode : 0;
   if (use_ffn4(tokens) && !trace_on_is8()) {
     t.ntiles = tokens / 64;
     t.tiles_per_pair = 2 * d.NP / 64;
-    auto go4 = [&](auto ad) {
-      constexpr bool AD = decltype(ad)::value;
+    auto go4 = [&](auto ad_c) {
+      constexpr int AD = decltype(ad_c)::value;
       if (heads && mt == 3) (void)launch_ffn4<3, true, false, AD>(tokens, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
       else if (heads && mt == 2) (void)launch_ffn4<2, true, false, AD>(tokens, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
       else (void)launch_ffn4<1, false, false, AD>(tokens, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
     };
-    if (live) go4(std::true_type{});
-    else go4(std::false_type{});
+    if (ad == 2) go4(std::integral_constant<int, 2>{});
+    else if (ad == 1) go4(std::integral_constant<int, 1>{});
+    else go4(std::integral_constant<int, 0>{});
     if (trace_on) ffn4_trace_report(trace_buf, t.ntiles < 2 * cu_count() ? t.ntiles : 2 * cu_count(), mt, s);
     return;
   }
   t.tiles_per_pair = 2 * d.NP / (nt * 32);
   const int extra = ffn_prefetch_setup(t, trace_wg, prefetch);  // trace_wg = the workgroups that walk the tiles
-  auto go = [&](auto ad) {
-    constexpr bool AD = decltype(ad)::value;
+  auto go = [&](auto ad_c) {
+    constexpr int AD = decltype(ad_c)::value;
     if (heads && mt == 3) (void)launch_ffn<3, true, AD>(nt, tokens, extra, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
     else if (heads && mt == 2) (void)launch_ffn<2, true, AD>(nt, tokens, extra, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
     else (void)launch_ffn<1, false, AD>(nt, tokens, extra, s, ctx, w0.w, w0.bias, gamma, beta, w3.w, w3.bias, x, t);
   };
-  if (live) go(std::true_type{});
-  else go(std::false_type{});
+  if (ad == 2) go(std::integral_constant<int, 2>{});
+  else if (ad == 1) go(std::integral_constant<int, 1>{});
+  else go(std::integral_constant<int, 0>{});
   if (trace_on) ffn_trace_report(trace_buf, trace_wg, mt, s);
 }
 
 // The first SelfBlock's Wqkv (no FFN in front of it): the FFN kernel's fused projection on its own - same persistent
 // tile loop, LDS-DMA staging, prefetched weight stream and tile-interleaved rows as the other 17 projections.
 hipError_t launch_lg_proj_heads(const ConvW& next, _Float16* x, LgDims d, int rope_segs, int t_seg, const float* rope, _Float16* q,
-                                _Float16* k, _Float16* vt, hipStream_t s, const ConvW* const* prefetch) {
+                                _Float16* k, _Float16* vt, hipStream_t s, const ConvW* const* prefetch, const int* tiles) {
   if (next.cout != 768) return hipErrorInvalidValue;
   const int tokens = d.S * d.NP;
   FfnTail t{};
@@ -1745,6 +1759,15 @@ hipError_t launch_lg_proj_heads(const ConvW& next, _Float16* x, LgDims d, int ro
   t.proj.flags = rope_segs | (t_seg << 4); t.proj.ostride = 256;
   const _Float16* nh = nullptr;
   const float* nf = nullptr;
+  if (tiles) {  // adaptive width: the projection of the listed tiles only (the sequences that lost tokens at this layer)
+    t.live = tiles;
+    if (use_ffn4(tokens)) {
+      t.ntiles = tokens / 64;
+      return launch_ffn4<3, true, true, 2>(tokens, s, (const _Float16*)x, nh, nf, nf, nf, nh, nf, x, t);
+    }
+    return ffn_nt(tokens) == 1 ? launch_ffn_nt<3, true, 1, true, 2>(tokens, 0, s, (const _Float16*)x, nh, nf, nf, nf, nh, nf, x, t)
+                               : launch_ffn_nt<3, true, 2, true, 2>(tokens, 0, s, (const _Float16*)x, nh, nf, nf, nf, nh, nf, x, t);
+  }
   if (use_ffn4(tokens)) {
     t.ntiles = tokens / 64;
     return launch_ffn4<3, true, true>(tokens, s, (const _Float16*)x, nh, nf, nf, nf, nh, nf, x, t);
@@ -2324,6 +2347,210 @@ __global__ __launch_bounds__(256) void k_lg_exit_head(const _Float16* __restrict
 void launch_lg_exit_head(const _Float16* x, int NP, int pairs, const int* layers_run, const float* wt, const float* bias, const float* mw,
                          const float* mb, _Float16* md, float* logsig, hipStream_t s) {
   hipLaunchKernelGGL(k_lg_exit_head, dim3(pairs * (2 * NP / 32)), dim3(256), 0, s, x, NP, layers_run, wt, bias, mw, mb, md, logsig);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Adaptive width (upstream LightGlue's width_confidence; include/sship.h "Adaptive width").  Off by default: none of the
+// launches below is made.  On, per launch group of pairs (lg_forward):
+//   depth init + width init -> layer 0 -> [depth conf(0)] -> prune(0) -> publish(0) -> re-projection of the changed sequences -> layer 1 ...
+//   after the join: [exit head] -> assignment on the live counts -> scatter through ind.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_lg_width_init(const int* __restrict__ lens, int NP, LgWidth wd) {
+  const int sq = blockIdx.x;
+  for (int t = threadIdx.x; t < NP; t += 256) {
+    wd.ind[(size_t)sq * NP + t] = t;
+    wd.prune[(size_t)sq * NP + t] = 1;
+  }
+  if (threadIdx.x == 0) { wd.wlen[sq] = lens[sq]; wd.chg[sq] = 0; }
+}
+void launch_lg_width_init(const int* lens, int NP, int np, LgWidth wd, hipStream_t s) {
+  hipLaunchKernelGGL(k_lg_width_init, dim3(2 * np), dim3(256), 0, s, lens, NP, wd);
+}
+
+// One workgroup (16 waves) = one sequence; a pair that is not running (stopped by the depth rule of this or an earlier layer, or emptied)
+// is left as it is, and so is an image with at most min_kp live tokens.  Otherwise:
+//   1. four tokens per wave and step (their rows are requested together): the matchability logit (and, with depth on, the token-confidence
+//      logit) as a 64-lane dot product of the fp16 x row with fp32 weights, the sigmoid in the form k_lg_depth_conf uses, the flag into LDS;
+//   2. wave 0: exclusive prefix sum of the flags by ballot + popcount, 64 tokens per step (integers: the same on every run);
+//   3. chunks of 64 source rows in ascending order: every wave reads its 4 rows (x 512 B, rope 256 B, ind) into registers, barrier,
+//      writes the kept ones at their new positions, barrier.  A destination is never behind its source, so a row is always read in the
+//      chunk it is overwritten in or an earlier one;
+//   4. rows [new count, old count) become padding again: x = 0, rope = (1, 0), as k_lg_prep writes padding.
+// prune[original index] += 1 for every kept token, also when nothing was dropped.  An image left without tokens ends its pair: that is
+// k_lg_width_publish's decision, which sees both images.
+__global__ __launch_bounds__(1024) void k_lg_width_prune(_Float16* __restrict__ x, float* __restrict__ rope, int NP,
+                                                        const float* __restrict__ mw, const float* __restrict__ mb, float keep_thr,
+                                                        int min_kp, const float* __restrict__ tcw, float tcb, float thr,
+                                                        LgDepth dep, LgWidth wd) {
+  __shared__ unsigned char s_keep[kMaxKp + 64];
+  __shared__ int s_pos[kMaxKp + 64];
+  __shared__ int s_new;
+  const int sq = blockIdx.x, p = sq >> 1;
+  if (dep.layers_run[p] != 9) return;  // uniform over the workgroup
+  const int n = min(max(wd.wlen[sq], 0), NP);
+  if (n <= min_kp) {
+    if (threadIdx.x == 0) wd.chg[sq] = 0;
+    return;
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const float4 m = *reinterpret_cast<const float4*>(mw + lane * 4);
+  const float bias = mb[0];
+  float4 tc = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (tcw) tc = *reinterpret_cast<const float4*>(tcw + lane * 4);
+  _Float16* xs = x + (size_t)sq * NP * 256;
+  float* rs = rope + (size_t)sq * NP * 64;
+  int* ind = wd.ind + (size_t)sq * NP;
+  int* prn = wd.prune + (size_t)sq * NP;
+  for (int base = 0; base < n; base += 64) {
+    h4_t v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int t = min(base + wave * 4 + j, n - 1);
+      v[j] = *reinterpret_cast<const h4_t*>(xs + (size_t)t * 256 + lane * 4);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int t = base + wave * 4 + j;
+      const float z = wave_sum((float)v[j][0] * m.x + (float)v[j][1] * m.y + (float)v[j][2] * m.z + (float)v[j][3] * m.w) + bias;
+      bool keep = 1.0f / (1.0f + expf(-z)) > keep_thr;
+      if (tcw) {
+        const float zc = wave_sum((float)v[j][0] * tc.x + (float)v[j][1] * tc.y + (float)v[j][2] * tc.z + (float)v[j][3] * tc.w) + tcb;
+        keep = keep || 1.0f / (1.0f + expf(-zc)) <= thr;
+      }
+      if (lane == 0 && t < n) s_keep[t] = keep ? 1 : 0;
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {
+    int run = 0;
+    for (int base = 0; base < n; base += 64) {
+      const bool k = base + lane < n && s_keep[base + lane];
+      const unsigned long long bal = __ballot(k);
+      s_pos[base + lane] = run + __popcll(bal & ((1ull << lane) - 1ull));
+      run += __popcll(bal);
+    }
+    if (lane == 0) s_new = run;
+  }
+  __syncthreads();
+  const int nn = s_new;
+  if (nn < n) {
+    for (int base = 0; base < n; base += 64) {
+      h4_t xv[4];
+      float rv[4];
+      int iv[4];
+      bool kp[4];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int t = base + wave * 4 + j;
+        kp[j] = t < n && s_keep[t];
+        if (kp[j]) {
+          xv[j] = *reinterpret_cast<const h4_t*>(xs + (size_t)t * 256 + lane * 4);
+          rv[j] = rs[(size_t)t * 64 + lane];
+          iv[j] = ind[t];
+        }
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the chunk is in registers before any wave overwrites a row of it
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (!kp[j]) continue;
+        const int dst = s_pos[base + wave * 4 + j];
+        *reinterpret_cast<h4_t*>(xs + (size_t)dst * 256 + lane * 4) = xv[j];
+        rs[(size_t)dst * 64 + lane] = rv[j];
+        if (lane == 0) { ind[dst] = iv[j]; prn[iv[j]] += 1; }
+      }
+      __syncthreads();
+    }
+    for (int t = nn + wave; t < n; t += 16) {
+      *reinterpret_cast<h4_t*>(xs + (size_t)t * 256 + lane * 4) = to_h4(0.f, 0.f, 0.f, 0.f);
+      rs[(size_t)t * 64 + lane] = (lane & 1) ? 0.f : 1.f;
+    }
+  } else {
+    for (int t = threadIdx.x; t < n; t += 1024) prn[ind[t]] += 1;
+  }
+  if (threadIdx.x == 0) { wd.wlen[sq] = nn; wd.chg[sq] = nn < n ? 1 : 0; }
+}
+void launch_lg_width_prune(_Float16* x, float* rope, int NP, int np, const float* mw, const float* mb, float keep_thr, int min_kp,
+                           const float* tcw, float tcb, float thr, LgDepth dep, LgWidth wd, hipStream_t s) {
+  hipLaunchKernelGGL(k_lg_width_prune, dim3(2 * np), dim3(1024), 0, s, x, rope, NP, mw, mb, keep_thr, min_kp, tcw, tcb, thr, dep, wd);
+}
+
+// One workgroup for the launch group.  Thread q takes pair q: a running pair with an image left without tokens is finished (upstream
+// returns empty matches: it reports the layers it ran and takes no further part); then the pair's counts as the attention launches of
+// the next layer read them (0 when the pair is not running), and its tiles.  With tiles of TS tokens the pair's tokens are [0, n0) and [NP, NP + n1) of its 2 NP rows; a tile
+// that straddles the two images is listed once.  The lists are in pair order, tiles ascending: the same on every run.
+__device__ __forceinline__ int width_pair_tiles(int n0, int n1, int NP, int TS, int tile_base, int* out) {
+  const int a1 = (n0 + TS - 1) / TS;                                  // tiles [0, a1) hold image 0's live rows
+  const int b0 = n1 > 0 ? NP / TS : 0, b1 = n1 > 0 ? (NP + n1 + TS - 1) / TS : 0;  // tiles [b0, b1) image 1's
+  int k = 0;
+  for (int t = 0; t < a1; ++t, ++k) if (out) out[k] = tile_base + t;
+  for (int t = max(b0, a1); t < b1; ++t, ++k) if (out) out[k] = tile_base + t;
+  return k;
+}
+__global__ __launch_bounds__(256) void k_lg_width_publish(int NP, int np, int TS, int layer, LgDepth dep, LgWidth wd) {
+  __shared__ int s_a[256], s_b[256];
+  __shared__ int s_ta, s_tb;
+  if (threadIdx.x == 0) { s_ta = 0; s_tb = 0; }
+  __syncthreads();
+  const int tpp = 2 * NP / TS;
+  for (int base = 0; base < np; base += 256) {
+    const int q = base + (int)threadIdx.x;
+    int n0 = 0, n1 = 0, c0 = 0, c1 = 0;
+    if (q < np) {
+      bool run = dep.layers_run[q] == 9;
+      n0 = run ? min(max(wd.wlen[2 * q], 0), NP) : 0;
+      n1 = run ? min(max(wd.wlen[2 * q + 1], 0), NP) : 0;
+      if (run && (n0 == 0 || n1 == 0)) {
+        dep.layers_run[q] = layer + 1;
+        run = false;
+        n0 = n1 = 0;
+      }
+      c0 = run && wd.chg[2 * q] ? n0 : 0;
+      c1 = run && wd.chg[2 * q + 1] ? n1 : 0;
+      dep.lens_live[2 * q] = n0;
+      dep.lens_live[2 * q + 1] = n1;
+    }
+    s_a[threadIdx.x] = width_pair_tiles(n0, n1, NP, TS, 0, nullptr);
+    s_b[threadIdx.x] = width_pair_tiles(c0, c1, NP, TS, 0, nullptr);
+    __syncthreads();
+    if (threadIdx.x == 0) {  // exclusive prefix sums in pair order
+      int a = s_ta, b = s_tb;
+      for (int t = 0; t < 256; ++t) {
+        const int ca = s_a[t], cb = s_b[t];
+        s_a[t] = a; s_b[t] = b;
+        a += ca; b += cb;
+      }
+      s_ta = a; s_tb = b;
+    }
+    __syncthreads();
+    if (q < np) {
+      width_pair_tiles(n0, n1, NP, TS, q * tpp, wd.tiles + 1 + s_a[threadIdx.x]);
+      width_pair_tiles(c0, c1, NP, TS, q * tpp, wd.rtiles + 1 + s_b[threadIdx.x]);
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { wd.tiles[0] = s_ta; wd.rtiles[0] = s_tb; }
+}
+void launch_lg_width_publish(int NP, int np, int tile_tokens, int layer, LgDepth dep, LgWidth wd, hipStream_t s) {
+  hipLaunchKernelGGL(k_lg_width_publish, dim3(1), dim3(256), 0, s, NP, np, tile_tokens, layer, dep, wd);
+}
+
+// matches0 / mscores0 were preset to -1 / 0; live row a of image 0 is keypoint ind0[a], its match m a live row of image 1 = keypoint ind1[m]
+__global__ __launch_bounds__(256) void k_lg_width_scatter(const int* __restrict__ wlen, const int* __restrict__ ind, int NP, int max_kp,
+                                                          const int32_t* __restrict__ mc, const float* __restrict__ msc,
+                                                          int32_t* __restrict__ matches0, float* __restrict__ mscores0) {
+  const int pair = blockIdx.y, a = blockIdx.x * blockDim.x + threadIdx.x;
+  const int n0 = min(max(wlen[2 * pair], 0), max_kp), n1 = min(max(wlen[2 * pair + 1], 0), max_kp);
+  if (a >= n0 || n1 == 0) return;
+  const int i = ind[(size_t)(2 * pair) * NP + a];
+  if ((unsigned)i >= (unsigned)max_kp) return;
+  const int mj = mc[(size_t)pair * max_kp + a];
+  matches0[(size_t)pair * max_kp + i] = (unsigned)mj < (unsigned)n1 ? ind[(size_t)(2 * pair + 1) * NP + mj] : -1;
+  mscores0[(size_t)pair * max_kp + i] = msc[(size_t)pair * max_kp + a];
+}
+void launch_lg_width_scatter(const int* wlen, const int* ind, int NP, int pairs, int max_kp, const int32_t* mc, const float* msc,
+                             int32_t* matches0, float* mscores0, hipStream_t s) {
+  hipLaunchKernelGGL(k_lg_width_scatter, dim3((max_kp + 255) / 256, pairs), dim3(256), 0, s, wlen, ind, NP, max_kp, mc, msc, matches0, mscores0);
 }
 
 }  // namespace sship

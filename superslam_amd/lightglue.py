@@ -48,8 +48,11 @@ class LightGlueEngine:
 
 class LightGlue:
     def __init__(self, engine, image_width: int, image_height: int, max_keypoints: int = 1024, max_pairs: int = 1,
-                 depth_confidence: float = -1.0):
+                 depth_confidence: float = -1.0, width_confidence: float = -1.0, prune_min_keypoints: int = 0):
         self._engine_arg = engine
+        # adaptive width (upstream's width_confidence; prune_min_keypoints = its pruning_th): <= 0 = off, the reference's setting
+        self.width_confidence = float(width_confidence)
+        self.prune_min_keypoints = int(prune_min_keypoints)
         # adaptive depth (upstream LightGlue's depth_confidence, include/sship.h): <= 0 = off, the reference's setting
         self.depth_confidence = float(depth_confidence)
         self.image_width, self.image_height = int(image_width), int(image_height)
@@ -68,6 +71,8 @@ class LightGlue:
             self._h = h
             if self.depth_confidence > 0:
                 _lib.check(_lib.lib().sship_lg_set_depth_confidence(h, C.c_float(self.depth_confidence)))
+            if self.width_confidence > 0:
+                _lib.check(_lib.lib().sship_lg_set_width_confidence(h, C.c_float(self.width_confidence), self.prune_min_keypoints))
             return True
         except _lib.SshipError as e:
             self.last_error = str(e)
@@ -137,6 +142,20 @@ class LightGlue:
         _lib.check(_lib.lib().sship_lg_layers_run(self._h, out.ctypes.data, int(pairs)))
         return out
 
+    def set_width_confidence(self, width_confidence: float, prune_min_keypoints: int = 0) -> None:
+        """Adaptive width for the calls after this one: w in (0, 1] on, <= 0 off; an image is pruned only while it has more than
+        prune_min_keypoints live keypoints.  Raises SshipError for NaN, w > 1, a negative prune_min_keypoints, or weights without
+        the early matchability heads (the setting is then unchanged)."""
+        _lib.check(_lib.lib().sship_lg_set_width_confidence(self._h, C.c_float(float(width_confidence)), int(prune_min_keypoints)))
+        self.width_confidence, self.prune_min_keypoints = float(width_confidence), int(prune_min_keypoints)
+
+    def prune_counts(self, n0: int, n1: int, pair: int = 0):
+        """(prune0 int32 [n0], prune1 int32 [n1]) of pair `pair` of the last call: 1 + the pruning steps each keypoint survived
+        (upstream's prune0 / prune1; 9 everywhere with adaptive width off)."""
+        p0, p1 = np.zeros(int(n0), np.int32), np.zeros(int(n1), np.int32)
+        _lib.check(_lib.lib().sship_lg_prune_counts(self._h, int(pair), p0.ctypes.data, int(n0), p1.ctypes.data, int(n1)))
+        return p0, p1
+
     def descriptors_to_host(self, d: DeviceDescriptors) -> np.ndarray:
         """src/LightGlue.cc:460-475: fp16 slot -> float32 [count, dim]; empty handle -> empty array."""
         if d.empty():
@@ -146,7 +165,7 @@ class LightGlue:
         return out
 
     # ---- test-only introspection (include/sship.h sship_lg_debug_*): the parity suite compares internals with the oracle
-    DEBUG_X, DEBUG_SIM, DEBUG_KPTS, DEBUG_ROPE = 0, 1, 2, 3
+    DEBUG_X, DEBUG_SIM, DEBUG_KPTS, DEBUG_ROPE, DEBUG_IND = 0, 1, 2, 3, 4
 
     def debug_set_layers(self, n_layers: int) -> None:
         _lib.check(_lib.lib().sship_lg_debug_set_layers(self._h, int(n_layers)))

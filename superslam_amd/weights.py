@@ -132,6 +132,29 @@ def add_token_confidence_heads(sd: dict, seed: int = 3, weight_gain: float = 0.0
     return out
 
 
+def set_matchability_heads(sd: dict, directions, gain: float = 1.0, biases=0.0) -> dict:
+    """A copy of the LightGlue state dict ``sd`` whose per-layer matchability heads (adaptive width, include/sship.h) are chosen:
+    ``log_assignment.{i}.matchability.weight`` = ``gain`` * direction_i [1, 256] and ``.bias`` = biases[i] for i = 0..7.  Every other
+    tensor, the final head ``log_assignment.8`` included, is the same object.
+
+    ``directions`` is one vector [256] for all eight layers or eight of them [8, 256]; ``biases`` is one number or eight."""
+    d = LG_DIM
+    n = LG_LAYERS - 1
+    v = torch.as_tensor(directions, dtype=torch.float32)
+    if v.shape == (d,):
+        v = v[None].expand(n, d)
+    if tuple(v.shape) != (n, d):
+        raise ValueError(f"directions: [{d}] or [{n}, {d}], got {tuple(v.shape)}")
+    b = [float(biases)] * n if isinstance(biases, (int, float)) else [float(t) for t in biases]
+    if len(b) != n:
+        raise ValueError(f"biases: one value or {n}, got {len(b)}")
+    out = dict(sd)
+    for i in range(n):
+        out[f"log_assignment.{i}.matchability.weight"] = (float(gain) * v[i])[None].contiguous().clone()
+        out[f"log_assignment.{i}.matchability.bias"] = torch.tensor([b[i]], dtype=torch.float32)
+    return out
+
+
 def normalize_lightglue_keys(sd: dict) -> dict:
     """Raw upstream checkpoint names -> module names: ``self_attn.{i}.*`` -> ``transformers.{i}.self_attn.*`` (and
     cross_attn), optional ``matcher.`` prefix dropped - the rename upstream's LightGlue.__init__ applies at load time
