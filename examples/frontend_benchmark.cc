@@ -20,7 +20,9 @@
 // build:  g++ -std=c++17 -O2 -Iinclude examples/frontend_benchmark.cc -o frontend_benchmark
 //             -Lsuperslam_amd/lib -lsuperslam_hip -Wl,-rpath,$PWD/superslam_amd/lib -Wl,-rpath,/opt/rocm/lib -lpthread -lz
 // run:    ./frontend_benchmark --sp sp.safetensors --lg lg.safetensors (--sequence DIR | --synthetic 200) [--keyframe-match]
-//                              [--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline]
+//                              [--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear]
+//
+// --bilinear: descriptors by upstream SuperPoint's bilinear sampling (SSHIP_DESC_BILINEAR) instead of the reference's nearest-cell gather.
 //
 // Cross-frame pipelining (default with the ring; --no-pipeline turns it off): as soon as frame t's extraction has returned, frame
 // t+1's extraction is ENQUEUED on the extractor's stream (sship_sp_ring_submit) - before frame t's LightGlue match - so the next
@@ -116,7 +118,7 @@ int main(int argc, char** argv) {
   Source src;
   int max_kp = 600, border = 4;
   double thr = 0.005;
-  bool keyframe = false, use_ring = true, pipeline = true;
+  bool keyframe = false, use_ring = true, pipeline = true, bilinear = false;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -130,11 +132,12 @@ int main(int argc, char** argv) {
     else if (a == "--keyframe-match") keyframe = true;
     else if (a == "--no-ring") use_ring = false;
     else if (a == "--no-pipeline") pipeline = false;
+    else if (a == "--bilinear") bilinear = true;
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
   if (sp_path.empty() || lg_path.empty() || (src.sequence.empty() && src.synthetic <= 0)) {
     std::fprintf(stderr, "usage: %s --sp W.safetensors --lg W.safetensors (--sequence DIR | --synthetic N) [--keyframe-match] "
-                         "[--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline]\n", argv[0]);
+                         "[--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear]\n", argv[0]);
     return 2;
   }
 
@@ -155,6 +158,7 @@ int main(int argc, char** argv) {
   }
   sh::SuperPoint extractor(sp_path, max_kp, thr, border);
   sh::LightGlue matcher(lg_path, cols, rows, max_kp);
+  if (bilinear) extractor.set_descriptor_sampling(SSHIP_DESC_BILINEAR);  // kept, applied by initialize()
   if (!extractor.initialize() || !matcher.initialize()) {
     std::fprintf(stderr, "initialisation failed: %s\n", sship_last_error());
     return 1;

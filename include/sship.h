@@ -104,6 +104,23 @@ int sship_gather_normalize_hwc(const void* grid_fp16_dev, int channels, int grid
                                const int* cell_h_dev, const int* cell_w_dev, int num_keypoints,
                                void* out_fp16_dev, void* stream);
 
+/* Bilinear descriptor sampling at keypoint pixels: the stage twin of SSHIP_DESC_BILINEAR below (upstream cvg/LightGlue superpoint.py
+ * sample_descriptors; the reference has no counterpart).  kp_xy_dev is a device array of num_keypoints x (x, y) fp32 SCORE-MAP pixels
+ * (the grid covers 8*grid_w x 8*grid_h of them); out is [num_keypoints, channels] fp16.  For each keypoint, with D the grid:
+ *   gx = (x - 3.5) / (8*grid_w - 4.5) * (grid_w - 1)        gy = (y - 3.5) / (8*grid_h - 4.5) * (grid_h - 1)
+ *   x0 = floor(gx), fx = gx - x0                            y0 = floor(gy), fy = gy - y0
+ *   v[c] = (1-fy)(1-fx) D[c,y0,x0] + (1-fy)fx D[c,y0,x0+1] + fy(1-fx) D[c,y0+1,x0] + fy fx D[c,y0+1,x0+1]
+ *   out[c] = fp16( v[c] / max(||v||_2, 1e-12) )
+ * i.e. grid_sample(mode = bilinear, align_corners = True, padding_mode = zeros) + F.normalize: a corner outside the grid contributes
+ * zero (only for x < 3.5 or y < 3.5); grid_w == 1 or grid_h == 1 gives g = 0 on that axis.  Weights, blend, sum of squares and division
+ * are fp32.  channels in [1, 256]; num_keypoints <= 0 is a no-op.  sship_sample_descriptors_bilinear reads a CHW grid
+ * [channels, grid_h, grid_w] (the reference engine's layout, what sship_sp_dense returns), the _hwc variant a channels-last grid
+ * [grid_h, grid_w, channels] (channels a multiple of 4). */
+int sship_sample_descriptors_bilinear(const void* grid_fp16_dev, int channels, int grid_h, int grid_w,
+                                      const float* kp_xy_dev, int num_keypoints, void* out_fp16_dev, void* stream);
+int sship_sample_descriptors_bilinear_hwc(const void* grid_fp16_dev, int channels, int grid_h, int grid_w,
+                                          const float* kp_xy_dev, int num_keypoints, void* out_fp16_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Detector post-processing stages (exposed so each can be parity-tested bit-exactly)
  * ---------------------------------------------------------------------------------------------- */
@@ -147,6 +164,22 @@ int sship_sp_create(const sship_sp_config* cfg, sship_sp** out); /* ctor + initi
 void sship_sp_destroy(sship_sp* sp);
 sship_pool* sship_sp_pool(sship_sp* sp);
 int sship_sp_max_keypoints(const sship_sp* sp);
+/* How the descriptor of a keypoint is read from the descriptor map.  Per handle; it applies to every call made after it returns, through
+ * every entry point that yields per-keypoint descriptors: sship_sp_extract, _extract_stereo, _extract_stereo_ring, _ring_submit,
+ * _infer_host, _extract_batch_device and sship_frontend_batch_device (and sship_sp_bench_layer(14) times the head the mode selects).
+ *   SSHIP_DESC_NEAREST (default): the reference's rule, the cell the keypoint falls in (cell = coord / 8, src/DescriptorGather.cu),
+ *     renormalised - today's path, bit for bit, with the launches it always made.
+ *   SSHIP_DESC_BILINEAR: upstream SuperPoint's sample_descriptors, which the reference's export replaced by the nearest-cell gather and
+ *     which the published LightGlue weights were trained on: the rule stated at sship_sample_descriptors_bilinear above, with D = the
+ *     fp16 dense descriptor map (what sship_sp_dense returns) and (x, y) = the keypoint's integer score-map pixel (w, h) BEFORE the
+ *     rescale to input pixels.  The map is not materialised: convDa / convDb run at the four corner cells of every keypoint.
+ * The mode changes descriptors ONLY: keypoints, scores and counts do not depend on it.
+ * Any other mode or a NULL handle -> SSHIP_ERR_INVALID, the mode unchanged; also SSHIP_ERR_INVALID while a sship_sp_ring_submit is
+ * pending (collect it first).  In the developer build, SUPERSLAM_HIP_DESC=dense has no bilinear form: the setter refuses
+ * SSHIP_DESC_BILINEAR there with SSHIP_ERR_INVALID. */
+enum { SSHIP_DESC_NEAREST = 0, SSHIP_DESC_BILINEAR = 1 };
+int sship_sp_set_descriptor_sampling(sship_sp* sp, int mode);
+int sship_sp_descriptor_sampling(const sship_sp* sp);
 
 /* SuperPoint::extract (src/SuperPoint.cc:895-899 -> infer_device :597-676): host u8 image, 1 or 3 (BGR)
  * channels, row stride in bytes.  Synchronous. */
@@ -390,7 +423,7 @@ int sship_get_stage_timings(const char** labels, float* ms, int max_stages);
  * 11 convDb.  *macs receives the layer's multiply-accumulate count for that shape. */
 int sship_sp_bench_layer(sship_sp* sp, int layer, int batch, int h, int w, int iters, float* avg_ms, double* macs);
 /* (layer ids 12-14 are the memory-bound stages of the same handle: 12 = softmax + depth-to-space + NMS + threshold +
- * candidate compaction, 13 = top-k, 14 = descriptor head at the selected keypoints; *macs = 0 for them.
+ * candidate compaction, 13 = top-k, 14 = descriptor head at the selected keypoints (nearest or bilinear, as the handle is set); *macs = 0 for them.
  * 15 = conv2a + conv2b + pool as the ONE launch throughput batches run instead of layers 2 and 3 (csrc/conv_fuse2.hip; *macs = both layers').)
  *
  * Same for one stage of the matcher, over the state the last match call left on this handle, timed with hipEvents on the

@@ -152,9 +152,25 @@ public:
     cfg.pool_slots = descriptor_pool_slots;
     cfg.max_batch = 2;
     if (sship_sp_create(&cfg, &sp_) != SSHIP_OK) { last_error_ = sship_last_error(); sp_ = nullptr; return false; }
+    if (descriptor_sampling_ != SSHIP_DESC_NEAREST && sship_sp_set_descriptor_sampling(sp_, descriptor_sampling_) != SSHIP_OK) {
+      last_error_ = sship_last_error(); sship_sp_destroy(sp_); sp_ = nullptr; return false;
+    }
     pool_.reset(new DescriptorPool(sship_sp_pool(sp_), max_keypoints_, descriptor_dim));
     return true;
   }
+  // How a keypoint's descriptor is read from the descriptor map (include/sship.h): SSHIP_DESC_NEAREST (default, the reference's
+  // nearest-cell gather) or SSHIP_DESC_BILINEAR (upstream SuperPoint's sample_descriptors).  Descriptors only: keypoints, scores and
+  // counts do not change.  Before initialize() the mode is validated, kept and applied by initialize(); afterwards it applies to the
+  // calls after this one.  false + last_error() for any other mode or while a ring submission is pending (the mode is unchanged).
+  bool set_descriptor_sampling(int mode) {
+    if (sp_ && sship_sp_set_descriptor_sampling(sp_, mode) != SSHIP_OK) { last_error_ = sship_last_error(); return false; }
+    if (!sp_ && mode != SSHIP_DESC_NEAREST && mode != SSHIP_DESC_BILINEAR) {
+      last_error_ = "set_descriptor_sampling: mode must be 0 (nearest) or 1 (bilinear)"; return false;
+    }
+    descriptor_sampling_ = mode;
+    return true;
+  }
+  int descriptor_sampling() const { return descriptor_sampling_; }
   // Host path (src/SuperPoint.cc:322-348): keypoints + CV_32F [N,256] descriptors.
   bool infer(const Image& image, std::vector<KeyPoint>& keypoints, HostDescriptors& descriptors) {
     keypoints.clear();
@@ -246,6 +262,7 @@ private:
   int max_keypoints_;
   double keypoint_threshold_;
   int remove_borders_;
+  int descriptor_sampling_ = SSHIP_DESC_NEAREST;
   sship_sp* sp_ = nullptr;
   std::unique_ptr<DescriptorPool> pool_;
   std::string last_error_;

@@ -70,6 +70,14 @@ public:
     if (!ok) SLOG_ERROR("SuperPoint(HIP): {}", impl_.last_error());
     return ok;
   }
+  // Upstream SuperPoint's bilinear descriptor sampling (include/sship.h: SSHIP_DESC_BILINEAR); no counterpart in the reference, whose
+  // export gathers the nearest cell.  Off (SSHIP_DESC_NEAREST) unless called; kept before initialize() and applied by it.
+  bool set_descriptor_sampling(int mode) {
+    const bool ok = impl_.set_descriptor_sampling(mode);
+    if (!ok) SLOG_ERROR("SuperPoint(HIP): {}", impl_.last_error());
+    return ok;
+  }
+  int descriptor_sampling() const { return impl_.descriptor_sampling(); }
   bool infer(const cv::Mat& image, std::vector<cv::KeyPoint>& keypoints, cv::Mat& descriptors) {
     cv::Mat keep;
     std::vector<superslam_hip::KeyPoint> kp;

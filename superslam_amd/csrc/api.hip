@@ -540,6 +540,26 @@ extern "C" int sship_gather_normalize_hwc(const void* grid, int channels, int gh
   SSHIP_HIP_CHECK(hipGetLastError());
   return SSHIP_OK;
 }
+static int sample_bilinear(bool hwc, const void* grid, int channels, int gh, int gw, const float* kp_xy, int n, void* out, void* stream) {
+  bind_thread();
+  if (n <= 0) return SSHIP_OK;
+  if (!grid || !kp_xy || !out) return fail(SSHIP_ERR_INVALID, "sample_descriptors_bilinear: null argument");
+  if (channels <= 0 || channels > 256 || (hwc && channels % 4)) return fail(SSHIP_ERR_INVALID, "sample_descriptors_bilinear: channels must be in [1, 256] (a multiple of 4 for the channels-last grid)");
+  if (gh <= 0 || gw <= 0) return fail(SSHIP_ERR_INVALID, "sample_descriptors_bilinear: empty grid");
+  if (int rc = require_device()) return rc;
+  if (hwc) launch_sample_bilinear_hwc(static_cast<const _Float16*>(grid), channels, gh, gw, kp_xy, n, static_cast<_Float16*>(out), static_cast<hipStream_t>(stream));
+  else launch_sample_bilinear_chw(static_cast<const _Float16*>(grid), channels, gh, gw, kp_xy, n, static_cast<_Float16*>(out), static_cast<hipStream_t>(stream));
+  SSHIP_HIP_CHECK(hipGetLastError());
+  return SSHIP_OK;
+}
+extern "C" int sship_sample_descriptors_bilinear(const void* grid, int channels, int gh, int gw, const float* kp_xy, int n, void* out,
+                                                 void* stream) {
+  return sample_bilinear(false, grid, channels, gh, gw, kp_xy, n, out, stream);
+}
+extern "C" int sship_sample_descriptors_bilinear_hwc(const void* grid, int channels, int gh, int gw, const float* kp_xy, int n, void* out,
+                                                     void* stream) {
+  return sample_bilinear(true, grid, channels, gh, gw, kp_xy, n, out, stream);
+}
 extern "C" int sship_nms(const float* scores, int batch, int h, int w, int radius, float* out, void* stream) {
   bind_thread();
   if (!scores || !out || batch <= 0 || h <= 0 || w <= 0) return fail(SSHIP_ERR_INVALID, "nms: bad arguments");
@@ -599,6 +619,8 @@ struct sship_sp {
   const void* cand_zero_ptr = nullptr; int cand_zero_n = 0;  // cand_count[0 .. cand_zero_n) of this allocation are known to be zero (sp_select) ...
   hipStream_t cand_zero_stream = nullptr;                      // ... for work ordered after the last k_topk on THIS stream
   DevBuf kp, cell_h, cell_w, n_dev, desc_stage, gray_in;
+  int desc_sampling = SSHIP_DESC_NEAREST;  // sship_sp_set_descriptor_sampling
+  DevBuf pix;                              // [B, max_kp] score-map pixels of the keypoints (h << 16 | w): written by k_topk in bilinear mode only
   PinBuf h_kp, h_n, h_img;
   int cap = 0;
   float thr_f = 0.f;
@@ -648,6 +670,7 @@ static int sp_ensure(sship_sp* sp, int B, int H, int W) {
   SSHIP_HIP_CHECK(sp->kp.ensure((size_t)B * mk * 3 * 4));
   SSHIP_HIP_CHECK(sp->cell_h.ensure((size_t)B * mk * 4));
   SSHIP_HIP_CHECK(sp->cell_w.ensure((size_t)B * mk * 4));
+  SSHIP_HIP_CHECK(sp->pix.ensure((size_t)B * mk * 4));
   SSHIP_HIP_CHECK(sp->n_dev.ensure((size_t)B * 4));
   SSHIP_HIP_CHECK(sp->h_kp.ensure((size_t)B * mk * 3 * 4));
   SSHIP_HIP_CHECK(sp->h_n.ensure((size_t)B * 4));
@@ -702,10 +725,13 @@ static bool desc_dense_mode() {
   static const bool v = [] { const char* e = dev_env("SUPERSLAM_HIP_DESC"); return e && std::string(e) == "dense"; }();
   return v;
 }
-// descriptor rows of the selected keypoints of `B` images (cells / counts at the given pointers)
+// descriptor rows of the selected keypoints of `B` images (cells / counts at the given pointers; the cells are the handle's, from image img0 on)
 static hipError_t desc_head(sship_sp* sp, int img0, int Hc, int Wc, const int* cell_h, const int* cell_w, const int* n_dev, int B,
                             _Float16* out, size_t out_img_stride, hipStream_t s) {
   const int mk = sp->cfg.max_keypoints;
+  if (sp->desc_sampling == SSHIP_DESC_BILINEAR)  // the corner variant of the sparse head, at the pixels the same k_topk launch left in sp->pix
+    return launch_desc_head_sparse_bilinear(sp->cDa, sp->cDb32, sp->a4b.as<_Float16>() + (size_t)img0 * Hc * Wc * 128, Hc, Wc,
+                                            sp->pix.as<int>() + (cell_h - sp->cell_h.as<int>()), n_dev, mk, B, out, out_img_stride, s);
   if (desc_dense_mode()) {
     launch_desc_head_gather(sp->cDb32, sp->aDa.as<_Float16>() + (size_t)img0 * Hc * Wc * 256, Hc, Wc, cell_h, cell_w, n_dev, mk, B, out,
                             out_img_stride, s);
@@ -780,6 +806,7 @@ static int sp_select(sship_sp* sp, int B, int H, int W, float* scores_out, float
   t.scale_y = static_cast<float>(H) / (Hc * 8);
   t.desc_h = Hc; t.desc_w = Wc; t.kp_xys = kp_out; t.cell_h = sp->cell_h.as<int>(); t.cell_w = sp->cell_w.as<int>();
   t.n_out = n_out; t.n_cand_out = nullptr; t.reset_count = a.cand_count;
+  t.pix = sp->desc_sampling == SSHIP_DESC_BILINEAR ? sp->pix.as<int>() : nullptr;
   launch_topk(t, B, s);
   SSHIP_HIP_CHECK(hipGetLastError());
   sp->cand_zero_n = B;
@@ -911,6 +938,20 @@ extern "C" int sship_sp_debug_activation(sship_sp* sp, int layer, void* out_host
 extern "C" sship_pool* sship_sp_pool(sship_sp* sp) {
   bind_thread(); return sp ? sp->pool : nullptr; }
 extern "C" int sship_sp_max_keypoints(const sship_sp* sp) { return sp ? sp->cfg.max_keypoints : 0; }
+extern "C" int sship_sp_set_descriptor_sampling(sship_sp* sp, int mode) {
+  if (!sp) return fail(SSHIP_ERR_INVALID, "sp_set_descriptor_sampling: null handle");
+  if (mode != SSHIP_DESC_NEAREST && mode != SSHIP_DESC_BILINEAR)
+    return fail(SSHIP_ERR_INVALID, "sp_set_descriptor_sampling: mode must be 0 (nearest) or 1 (bilinear)");
+  for (const auto& pd : sp->ring.pending)
+    if (pd.active) return fail(SSHIP_ERR_INVALID, "sp_set_descriptor_sampling: a ring submission is pending (collect it with sship_sp_extract_stereo_ring first)");
+#if SSHIP_DEV_SWITCHES
+  // developer build: the dense-branch A/B path (SUPERSLAM_HIP_DESC=dense) has no bilinear form
+  if (mode == SSHIP_DESC_BILINEAR && desc_dense_mode()) return fail(SSHIP_ERR_INVALID, "sp_set_descriptor_sampling: bilinear sampling is not available under SUPERSLAM_HIP_DESC=dense");
+#endif
+  sp->desc_sampling = mode;
+  return SSHIP_OK;
+}
+extern "C" int sship_sp_descriptor_sampling(const sship_sp* sp) { return sp ? sp->desc_sampling : SSHIP_DESC_NEAREST; }
 
 extern "C" int sship_sp_extract_batch_device(sship_sp* sp, const uint8_t* imgs, int batch, int h, int w, void* desc_out,
                                              float* kp_out, int* n_out, void* stream) {
@@ -1016,6 +1057,7 @@ extern "C" int sship_sp_bench_layer(sship_sp* sp, int layer, int batch, int h, i
         t.scale_x = static_cast<float>(w) / (Wc * 8); t.scale_y = static_cast<float>(h) / (Hc * 8);
         t.desc_h = Hc; t.desc_w = Wc; t.kp_xys = sp->kp.as<float>(); t.cell_h = sp->cell_h.as<int>(); t.cell_w = sp->cell_w.as<int>();
         t.n_out = sp->n_dev.as<int>(); t.n_cand_out = nullptr;
+        t.pix = sp->desc_sampling == SSHIP_DESC_BILINEAR ? sp->pix.as<int>() : nullptr;
         launch_topk(t, batch, s);
         return hipGetLastError();
       }

@@ -40,6 +40,7 @@ struct TopkArgs {
   int* cell_w;                     // [B, max_kp]
   int* n_out;                      // [B]
   int* n_cand_out;                 // [B] or null
+  int* pix;                        // [B, max_kp] or null: the keypoint's score-map pixel (h << 16 | w), what the bilinear descriptor head samples at
 };
 void launch_topk(const TopkArgs& a, int B, hipStream_t s);
 void launch_threshold_scan(const float* scores, int H, int W, float thr_f, int border, unsigned long long* cand,
@@ -49,6 +50,22 @@ void launch_gather_hwc(bool raw, const _Float16* grid, int C, int gh, int gw, si
                        hipStream_t s);
 void launch_gather_chw(const _Float16* grid, int C, int gh, int gw, const int* cell_h, const int* cell_w, int n,
                        _Float16* out, hipStream_t s);
+// Bilinear descriptor sampling (include/sship.h, sship_sp_set_descriptor_sampling): upstream SuperPoint's sample_descriptors =
+// grid_sample(align_corners = True, zero padding) at score-map pixel (x, y) of a gh x gw cell grid.  (x0, y0) = the top-left corner cell
+// (-1 when the pixel lies left of / above the first cell centre), (fx, fy) the fractions; corner q = 2 dy + dx has weight
+// bilinear_weight(q) and counts only where it lies inside the grid.  fp32; the coordinates are clamped so that no input can index outside.
+__device__ __forceinline__ void bilinear_corner(float x, float y, int gh, int gw, int& x0, int& y0, float& fx, float& fy) {
+  float gx = (x - 3.5f) / (8.f * (float)gw - 4.5f) * (float)(gw - 1);
+  float gy = (y - 3.5f) / (8.f * (float)gh - 4.5f) * (float)(gh - 1);
+  gx = fminf(fmaxf(gx, -1.f), (float)gw);
+  gy = fminf(fmaxf(gy, -1.f), (float)gh);
+  const float flx = floorf(gx), fly = floorf(gy);
+  x0 = (int)flx; y0 = (int)fly; fx = gx - flx; fy = gy - fly;
+}
+__device__ __forceinline__ float bilinear_weight(int q, float fx, float fy) { return ((q & 2) ? fy : 1.f - fy) * ((q & 1) ? fx : 1.f - fx); }
+// kp_xy [n][2] fp32 score-map pixels -> out [n][C] fp16, C <= 256 (hwc: a multiple of 4)
+void launch_sample_bilinear_chw(const _Float16* grid, int C, int gh, int gw, const float* kp_xy, int n, _Float16* out, hipStream_t s);
+void launch_sample_bilinear_hwc(const _Float16* grid, int C, int gh, int gw, const float* kp_xy, int n, _Float16* out, hipStream_t s);
 void launch_desc_dense_chw(const _Float16* raw, int cells_per_img, int B, _Float16* out, hipStream_t s);
 void launch_logits_chw(const float* in, int ls, int cells_per_img, int B, float* out, hipStream_t s);
 void launch_bgr2gray(const uint8_t* in, int n, uint8_t* out, hipStream_t s);
@@ -91,6 +108,9 @@ hipError_t mfma_probe(bool random_operands, float* tflops);
 hipError_t launch_desc_head_sparse(const ConvW& da32, const ConvW& db32, const _Float16* a4b, int Hc, int Wc, const int* cell_h,
                                    const int* cell_w, const int* n_dev, int max_kp, int B, _Float16* out, size_t out_img_stride,
                                    hipStream_t s);
+// bilinear mode: rows are corners (four per keypoint), `pix` = k_topk's packed score-map pixels
+hipError_t launch_desc_head_sparse_bilinear(const ConvW& da32, const ConvW& db32, const _Float16* a4b, int Hc, int Wc, const int* pix,
+                                            const int* n_dev, int max_kp, int B, _Float16* out, size_t out_img_stride, hipStream_t s);
 void launch_desc_head_gather(const ConvW& db32, const _Float16* da, int Hc, int Wc, const int* cell_h, const int* cell_w,
                              const int* n_dev, int max_kp, int B, _Float16* out, size_t out_img_stride, hipStream_t s);
 hipError_t sp_conv1x1_f32(const ConvW& w, const _Float16* in, float* out, int ostride, int B, int H, int W,

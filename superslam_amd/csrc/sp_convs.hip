@@ -235,7 +235,15 @@ __global__ __launch_bounds__(512) void k_desc_head_gather(const _Float16* __rest
 constexpr int kDsPatchLd = 584;  // halfs per keypoint and 64-channel chunk: 9 taps x 64 + 8 (1168 B: conflict-free b128 reads)
 // NN = 32-keypoint N-tiles per workgroup: 2 for batches, 1 when that would leave most CUs without a workgroup (a stereo pair: 20 -> 40 workgroups,
 // half the MFMAs and half the patch gather per workgroup; the per-keypoint arithmetic is the same, so the two are bit-identical)
-template <int NN>
+//
+// BIL (sship_sp_set_descriptor_sampling(SSHIP_DESC_BILINEAR)): upstream SuperPoint's bilinear sample_descriptors instead of the reference's
+// nearest-cell gather.  The rows of the tile are CORNERS: row 4k + q is corner q = 2 dy + dx of keypoint k, so a workgroup serves 8 NN
+// keypoints; `cell_h` holds k_topk's packed score-map pixels (h << 16 | w) and `cell_w` is unused.  Patch gather, both MFMA chains and
+// F.normalize (the fp16 dense descriptor of the corner cell) are the code below, unchanged; a corner outside the grid is an empty row
+// (cell -1, zero patch) with weight 0 - grid_sample's zero padding.  The four corner rows of a keypoint sit in four adjacent lanes of a
+// half-wave, so the blend is two __shfl_xor steps on the weighted values ((c0 + c1) + (c2 + c3) in every lane: addition commutes, the
+// four lanes hold the same bits, and NN does not enter), row_sum_sq gives |v|^2, and lane q stores channel group q of the row.
+template <int NN, bool BIL = false>
 __global__ __launch_bounds__(512) void k_desc_head_sparse(const _Float16* __restrict__ a4b, int Hc, int Wc,
                                                           const int* __restrict__ cell_h, const int* __restrict__ cell_w,
                                                           const int* __restrict__ n_dev, int max_kp,
@@ -248,12 +256,31 @@ __global__ __launch_bounds__(512) void k_desc_head_sparse(const _Float16* __rest
   _Float16* s_x = s_p + NK * kDsPatchLd;                      // [NK][kDhLd] convDa output (convDb input)
   float (*s_red)[64] = reinterpret_cast<float (*)[64]>(s_x + NK * kDhLd);
   int* s_cell = reinterpret_cast<int*>(s_red + 8);            // [64] (cell_h << 16 | cell_w), -1 = no keypoint
-  const int b = blockIdx.y, i0 = blockIdx.x * NK;
+  float* s_wt = reinterpret_cast<float*>(s_cell + 64);        // [64] BIL: the corner's bilinear weight (the launch adds these 256 bytes)
+  const int b = blockIdx.y, i0 = blockIdx.x * (BIL ? NK / 4 : NK);
   const int n = min(max(n_dev[b], 0), max_kp);
   if (i0 >= n) return;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, j = lane & 31, hh = lane >> 5;
-  if (tid < NK)
-    s_cell[tid] = i0 + tid < n ? (cell_h[(size_t)b * max_kp + i0 + tid] << 16) | cell_w[(size_t)b * max_kp + i0 + tid] : -1;
+  if constexpr (BIL) {
+    if (tid < NK) {
+      const int i = i0 + (tid >> 2), q = tid & 3;
+      int c = -1;
+      float wq = 0.f;
+      if (i < n) {
+        const int px = cell_h[(size_t)b * max_kp + i];
+        int x0, y0;
+        float fx, fy;
+        bilinear_corner((float)(px & 0xffff), (float)(px >> 16), Hc, Wc, x0, y0, fx, fy);
+        const int cy = y0 + (q >> 1), cx = x0 + (q & 1);
+        if (cy >= 0 && cy < Hc && cx >= 0 && cx < Wc) { c = (cy << 16) | cx; wq = bilinear_weight(q, fx, fy); }
+      }
+      s_cell[tid] = c;
+      s_wt[tid] = wq;
+    }
+  } else {
+    if (tid < NK)
+      s_cell[tid] = i0 + tid < n ? (cell_h[(size_t)b * max_kp + i0 + tid] << 16) | cell_w[(size_t)b * max_kp + i0 + tid] : -1;
+  }
   const _Float16* img = a4b + (size_t)b * Hc * Wc * 128;
   // ---- convDa at the keypoints ----
   f16x_t acc[NN];  // start from the bias, as the dense ping-pong kernel does (conv_pp.hip: same fp32 summation order)
@@ -377,6 +404,34 @@ __global__ __launch_bounds__(512) void k_desc_head_sparse(const _Float16* __rest
 #pragma unroll
     for (int r = 0; r < 16; ++r) v[nn][r] = (float)(_Float16)(v[nn][r] / denom);  // the fp16 dense descriptor
   }
+  if constexpr (BIL) {
+    // blend the four corner rows of a keypoint (lanes j = 4k .. 4k + 3 of this half-wave), then F.normalize the blend
+#pragma unroll
+    for (int nn = 0; nn < NN; ++nn) {
+      const float wq = s_wt[nn * 32 + j];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        float t = v[nn][r] * wq;
+        t += __shfl_xor(t, 1, 64);
+        t += __shfl_xor(t, 2, 64);
+        v[nn][r] = t;
+      }
+    }
+    row_sum_sq(tot);
+#pragma unroll
+    for (int nn = 0; nn < NN; ++nn) {
+      const int i = i0 + ((nn * 32 + j) >> 2), q = j & 3;
+      if (i >= n) continue;
+      const float denom = fmaxf(sqrtf(tot[nn]), 1e-12f);  // F.normalize(p=2, dim=1, eps=1e-12)
+      _Float16* orow = out + (size_t)b * out_img_stride + (size_t)i * 256 + wave * 32 + hh * 4;
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        if (q == g)
+          *reinterpret_cast<h4_t*>(orow + g * 8) =
+              to_h4(v[nn][4 * g] / denom, v[nn][4 * g + 1] / denom, v[nn][4 * g + 2] / denom, v[nn][4 * g + 3] / denom);
+    }
+    return;
+  }
   row_sum_sq(tot);
 #pragma unroll
   for (int nn = 0; nn < NN; ++nn) {
@@ -389,6 +444,28 @@ __global__ __launch_bounds__(512) void k_desc_head_sparse(const _Float16* __rest
       *reinterpret_cast<h4_t*>(orow + g * 8) =
           to_h4(v[nn][4 * g] * inv, v[nn][4 * g + 1] * inv, v[nn][4 * g + 2] * inv, v[nn][4 * g + 3] * inv);
   }
+}
+
+// bilinear mode: four corner rows per keypoint, so a workgroup serves 8 NN keypoints and the grid is four times the nearest-cell one
+hipError_t launch_desc_head_sparse_bilinear(const ConvW& da32, const ConvW& db32, const _Float16* a4b, int Hc, int Wc, const int* pix,
+                                            const int* n_dev, int max_kp, int B, _Float16* out, size_t out_img_stride, hipStream_t s) {
+  if (da32.cin != 128 || da32.cout != 256 || da32.ct != 32 || da32.ks != 3) return hipErrorInvalidValue;
+  if (Hc > 4095 || Wc > 8191) return hipErrorInvalidValue;  // the packed (h << 16 | w) pixel word
+  constexpr size_t smem = (size_t)64 * kDsPatchLd * 2 + (size_t)64 * kDhLd * 2 + 8 * 64 * 4 + 64 * 4 + 64 * 4;  // + the corner weights
+  static const hipError_t attr_rc = [] {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_desc_head_sparse<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(k_desc_head_sparse<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  }();
+  if (attr_rc != hipSuccess) return attr_rc;
+  // latency mode by the nearest-cell launch's rule, on this launch's own workgroup count
+  if (B * ((max_kp + 15) / 16) * 2 <= cu_count())
+    hipLaunchKernelGGL((k_desc_head_sparse<1, true>), dim3((max_kp + 7) / 8, B), dim3(512), smem, s, a4b, Hc, Wc, pix, nullptr, n_dev,
+                       max_kp, da32.w, da32.bias, db32.w, db32.bias, out, out_img_stride);
+  else
+    hipLaunchKernelGGL((k_desc_head_sparse<2, true>), dim3((max_kp + 15) / 16, B), dim3(512), smem, s, a4b, Hc, Wc, pix, nullptr, n_dev,
+                       max_kp, da32.w, da32.bias, db32.w, db32.bias, out, out_img_stride);
+  return hipGetLastError();
 }
 
 hipError_t launch_desc_head_sparse(const ConvW& da32, const ConvW& db32, const _Float16* a4b, int Hc, int Wc, const int* cell_h,

@@ -526,6 +526,7 @@ __global__ __launch_bounds__(1024) void k_topk(TopkArgs a) {
     kp[2] = score;
     a.cell_h[(size_t)b * a.max_kp + i] = min(h / 8, a.desc_h - 1);
     a.cell_w[(size_t)b * a.max_kp + i] = min(w / 8, a.desc_w - 1);
+    if (a.pix) a.pix[(size_t)b * a.max_kp + i] = (h << 16) | w;
   }
 }
 
@@ -647,6 +648,75 @@ void launch_gather_chw(const _Float16* grid, int C, int gh, int gw, const int* c
                        _Float16* out, hipStream_t s) {
   if (n <= 0) return;
   hipLaunchKernelGGL(k_gather_chw, dim3((n + 3) / 4), dim3(256), 0, s, grid, C, gh, gw, cell_h, cell_w, n, out);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Bilinear sampling of a descriptor grid at keypoint pixels (sship_sample_descriptors_bilinear*; the stage twin of the bilinear
+// descriptor head in sp_convs.hip).  upstream: cvg/LightGlue superpoint.py sample_descriptors.  A wave owns a keypoint: four corner rows
+// (channels-last: four contiguous 2C-byte rows, 8 B per lane; CHW: 2-byte loads a plane apart, as k_gather_chw) blended in fp32,
+// one wave reduction for the norm, F.normalize (eps 1e-12), fp16.  A corner outside the grid is skipped (zero padding): wave-uniform.
+// ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_sample_bilinear_hwc(const _Float16* __restrict__ grid, int C, int gh, int gw,
+                                                             const float* __restrict__ kp_xy, int n, _Float16* __restrict__ out) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (i >= n) return;
+  int x0, y0;
+  float fx, fy;
+  bilinear_corner(kp_xy[2 * (size_t)i], kp_xy[2 * (size_t)i + 1], gh, gw, x0, y0, fx, fy);
+  const int c = lane * 4;
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int cy = y0 + (q >> 1), cx = x0 + (q & 1);
+    if (cy < 0 || cy >= gh || cx < 0 || cx >= gw) continue;
+    const float wq = bilinear_weight(q, fx, fy);
+    float t[4] = {0.f, 0.f, 0.f, 0.f};
+    if (c < C) load4(grid + ((size_t)cy * gw + cx) * C + c, t);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] += wq * t[e];
+  }
+  const float ss = wave_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
+  const float denom = fmaxf(sqrtf(ss), 1e-12f);  // F.normalize(p=2, dim=1, eps=1e-12)
+  if (c < C) *reinterpret_cast<h4_t*>(out + (size_t)i * C + c) = to_h4(v[0] / denom, v[1] / denom, v[2] / denom, v[3] / denom);
+}
+__global__ __launch_bounds__(256) void k_sample_bilinear_chw(const _Float16* __restrict__ grid, int C, int gh, int gw,
+                                                             const float* __restrict__ kp_xy, int n, _Float16* __restrict__ out) {
+  const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (i >= n) return;
+  int x0, y0;
+  float fx, fy;
+  bilinear_corner(kp_xy[2 * (size_t)i], kp_xy[2 * (size_t)i + 1], gh, gw, x0, y0, fx, fy);
+  const size_t plane = (size_t)gh * gw;
+  float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int cy = y0 + (q >> 1), cx = x0 + (q & 1);
+    if (cy < 0 || cy >= gh || cx < 0 || cx >= gw) continue;
+    const float wq = bilinear_weight(q, fx, fy);
+    const size_t base = (size_t)cy * gw + cx;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int c = e * 64 + lane;  // lanes walk adjacent channel planes
+      if (c < C) v[e] += wq * (float)grid[c * plane + base];
+    }
+  }
+  const float ss = wave_sum(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
+  const float denom = fmaxf(sqrtf(ss), 1e-12f);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int c = e * 64 + lane;
+    if (c < C) out[(size_t)i * C + c] = (_Float16)(v[e] / denom);
+  }
+}
+void launch_sample_bilinear_chw(const _Float16* grid, int C, int gh, int gw, const float* kp_xy, int n, _Float16* out, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_sample_bilinear_chw, dim3((n + 3) / 4), dim3(256), 0, s, grid, C, gh, gw, kp_xy, n, out);
+}
+void launch_sample_bilinear_hwc(const _Float16* grid, int C, int gh, int gw, const float* kp_xy, int n, _Float16* out, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_sample_bilinear_hwc, dim3((n + 3) / 4), dim3(256), 0, s, grid, C, gh, gw, kp_xy, n, out);
 }
 
 // ---------------------------------------------------------------------------------------------------

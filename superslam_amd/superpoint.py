@@ -27,11 +27,45 @@ class Features:
     descriptors: DeviceDescriptors = field(default_factory=DeviceDescriptors)
 
 
+DESCRIPTOR_SAMPLING = {"nearest": 0, "bilinear": 1}   # SSHIP_DESC_NEAREST / SSHIP_DESC_BILINEAR (include/sship.h)
+
+
+def _sampling_mode(name) -> int:
+    if name not in DESCRIPTOR_SAMPLING:
+        raise ValueError(f"descriptor_sampling must be one of {sorted(DESCRIPTOR_SAMPLING)}, not {name!r}")
+    return DESCRIPTOR_SAMPLING[name]
+
+
+def sample_descriptors_bilinear(grid, kp_xy, layout: str = "chw", stream=None):
+    """Upstream SuperPoint's sample_descriptors on a given grid (include/sship.h: sship_sample_descriptors_bilinear[_hwc]).
+    grid: torch fp16 CUDA tensor, [C,Hc,Wc] (layout "chw") or [Hc,Wc,C] ("hwc"); kp_xy: fp32 CUDA tensor [n,2] of (x, y) score-map
+    pixels.  Returns fp16 [n,C], each row the L2-normalised bilinear blend of the four surrounding cells."""
+    import torch
+
+    if layout not in ("chw", "hwc"):
+        raise ValueError("layout must be 'chw' or 'hwc'")
+    if grid.dtype != torch.float16 or grid.dim() != 3 or not grid.is_contiguous():
+        raise ValueError("grid must be a contiguous fp16 tensor of three dimensions")
+    kp_xy = kp_xy.reshape(-1, 2)
+    if kp_xy.dtype != torch.float32 or not kp_xy.is_contiguous():
+        raise ValueError("kp_xy must be a contiguous fp32 tensor [n, 2]")
+    (c, gh, gw) = grid.shape if layout == "chw" else (grid.shape[2], grid.shape[0], grid.shape[1])
+    n = kp_xy.shape[0]
+    out = torch.empty((n, c), dtype=torch.float16, device=grid.device)
+    fn = _lib.lib().sship_sample_descriptors_bilinear if layout == "chw" else _lib.lib().sship_sample_descriptors_bilinear_hwc
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    _lib.check(fn(grid.data_ptr(), c, gh, gw, kp_xy.data_ptr() if n else None, n, out.data_ptr() if n else None, s))
+    return out
+
+
 class SuperPoint:
     descriptor_dim = 256
 
     def __init__(self, engine_file: str, max_keypoints: int, keypoint_threshold: float, remove_borders: int,
-                 nms_radius: int = 4, pool_slots: int = 8, max_batch: int = 2):
+                 nms_radius: int = 4, pool_slots: int = 8, max_batch: int = 2, descriptor_sampling: str = "nearest"):
+        # "nearest": the reference's nearest-cell gather (default); "bilinear": upstream SuperPoint's sample_descriptors
+        _sampling_mode(descriptor_sampling)
+        self._descriptor_sampling = descriptor_sampling
         self.engine_file = engine_file
         self.max_keypoints = int(max_keypoints)
         self.keypoint_threshold = float(keypoint_threshold)
@@ -51,6 +85,12 @@ class SuperPoint:
                                 self.remove_borders, self.nms_radius, self.pool_slots, self.max_batch)
             h = C.c_void_p()
             _lib.check(_lib.lib().sship_sp_create(C.byref(cfg), C.byref(h)))
+            if self._descriptor_sampling != "nearest":
+                rc = _lib.lib().sship_sp_set_descriptor_sampling(h, _sampling_mode(self._descriptor_sampling))
+                if rc != _lib.OK:
+                    self.last_error = (_lib.lib().sship_last_error() or b"").decode()
+                    _lib.lib().sship_sp_destroy(h)
+                    return False
             self._h = h
             return True
         except _lib.SshipError as e:
@@ -67,6 +107,19 @@ class SuperPoint:
             self.close()
         except Exception:
             pass
+
+    @property
+    def descriptor_sampling(self) -> str:
+        return self._descriptor_sampling
+
+    def set_descriptor_sampling(self, mode: str) -> None:
+        """"nearest" | "bilinear" for the calls after this one (descriptors only: keypoints, scores and counts do not change).  Before
+        initialize() the mode is kept and applied by it.  Raises ValueError for any other name and SshipError if the library refuses
+        (a ring submission is pending); the mode is then unchanged."""
+        m = _sampling_mode(mode)
+        if self._h is not None:
+            _lib.check(_lib.lib().sship_sp_set_descriptor_sampling(self._h, m))
+        self._descriptor_sampling = mode
 
     @property
     def pool_handle(self):
