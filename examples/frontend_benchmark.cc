@@ -20,8 +20,10 @@
 // build:  g++ -std=c++17 -O2 -Iinclude examples/frontend_benchmark.cc -o frontend_benchmark
 //             -Lsuperslam_amd/lib -lsuperslam_hip -Wl,-rpath,$PWD/superslam_amd/lib -Wl,-rpath,/opt/rocm/lib -lpthread -lz
 // run:    ./frontend_benchmark --sp sp.safetensors --lg lg.safetensors (--sequence DIR | --synthetic 200) [--keyframe-match]
-//                              [--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear]
+//                              [--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--matcher lightglue|nn]
 //
+// --matcher nn: the mutual nearest-neighbour matcher (superslam_hip::NNMatcher, hloc's NN-mutual) in LightGlue's place - same
+// IFeatureMatcher calls, no --lg needed.  Default: lightglue.
 // --bilinear: descriptors by upstream SuperPoint's bilinear sampling (SSHIP_DESC_BILINEAR) instead of the reference's nearest-cell gather.
 //
 // Cross-frame pipelining (default with the ring; --no-pipeline turns it off): as soon as frame t's extraction has returned, frame
@@ -42,6 +44,7 @@
 
 #include "superslam_hip/frontend.hpp"
 #include "superslam_hip/image_io.hpp"
+#include "superslam_hip/nn_matcher.hpp"
 
 namespace sh = superslam_hip;
 
@@ -114,7 +117,7 @@ struct Source {
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string sp_path, lg_path;
+  std::string sp_path, lg_path, matcher_name = "lightglue";
   Source src;
   int max_kp = 600, border = 4;
   double thr = 0.005;
@@ -133,11 +136,13 @@ int main(int argc, char** argv) {
     else if (a == "--no-ring") use_ring = false;
     else if (a == "--no-pipeline") pipeline = false;
     else if (a == "--bilinear") bilinear = true;
+    else if (a == "--matcher") matcher_name = next();
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
-  if (sp_path.empty() || lg_path.empty() || (src.sequence.empty() && src.synthetic <= 0)) {
+  const bool use_nn = matcher_name == "nn";
+  if (sp_path.empty() || (!use_nn && (lg_path.empty() || matcher_name != "lightglue")) || (src.sequence.empty() && src.synthetic <= 0)) {
     std::fprintf(stderr, "usage: %s --sp W.safetensors --lg W.safetensors (--sequence DIR | --synthetic N) [--keyframe-match] "
-                         "[--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear]\n", argv[0]);
+                         "[--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--matcher lightglue|nn]\n", argv[0]);
     return 2;
   }
 
@@ -157,9 +162,11 @@ int main(int argc, char** argv) {
     }
   }
   sh::SuperPoint extractor(sp_path, max_kp, thr, border);
-  sh::LightGlue matcher(lg_path, cols, rows, max_kp);
+  sh::LightGlue lightglue(lg_path, cols, rows, max_kp);
+  sh::NNMatcher nn(max_kp);
+  sh::IFeatureMatcher& matcher = use_nn ? static_cast<sh::IFeatureMatcher&>(nn) : lightglue;
   if (bilinear) extractor.set_descriptor_sampling(SSHIP_DESC_BILINEAR);  // kept, applied by initialize()
-  if (!extractor.initialize() || !matcher.initialize()) {
+  if (!extractor.initialize() || !(use_nn ? nn.initialize() : lightglue.initialize())) {
     std::fprintf(stderr, "initialisation failed: %s\n", sship_last_error());
     return 1;
   }
@@ -242,6 +249,7 @@ int main(int argc, char** argv) {
   std::printf("source           : %s, %dx%d, %s%s\n", src.synthetic > 0 ? "synthetic" : (src.ext == "png" ? "PNG sequence" : "PGM sequence"), cols, rows,
               use_ring ? "pinned upload ring" : "copying host API", ts.empty() ? "" : ", times.txt");
   std::printf("frames           : %zu\n", ms.size());
+  if (use_nn) std::printf("matcher          : nn (mutual nearest neighbour)\n");
   if (use_ring) std::printf("pipelined        : %s (%ld of %zu extractions enqueued one frame ahead)\n", pipeline ? "yes" : "no", submitted_ahead, ms.size());
   std::printf("per-frame ms      mean=%.2f p50=%.2f p95=%.2f max=%.2f\n", mean, percentile(ms, 0.50), percentile(ms, 0.95), percentile(ms, 1.0));
   std::printf("throughput        : %.2f fps over %.1fs wall\n", wall > 0 ? ms.size() / wall : 0.0, wall);

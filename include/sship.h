@@ -338,6 +338,47 @@ int sship_filter_matches(const int32_t* matches0, const float* mscores0, int n0,
 int sship_desc_to_host(const void* desc_dev, int count, int dim, float* out_f32);
 
 /* ------------------------------------------------------------------------------------------------
+ * Nearest-neighbour matcher - a second superslam::IFeatureMatcher ("Pluggable feature matcher", include/InferenceInterfaces.h) next to
+ * LightGlue: hloc's NN-mutual / NN-ratio / NN-superpoint (hloc/matchers/nearest_neighbor.py) and the reference's own cosineMatch
+ * (tests/test_superpoint_cosine_matching.cc).  No weights, no image size.  About 200 times less arithmetic than the LightGlue stack: a
+ * cheap pre-verification of loop candidates, a fallback without LightGlue weights, and the baseline LightGlue is judged against.
+ * Inputs are two descriptor sets d0 [n0, 256] and d1 [n1, 256], fp16 row-major (the pool-slot layout).  Per handle: ratio_threshold r,
+ * distance_threshold t, mutual_check.  The rule:
+ *   sim_ij = sum_k d0[i,k] d1[j,k], fp16 operands, fp32 accumulation; rows are NOT renormalised.
+ *   For row i over j < n1:  j1 = the smallest j attaining the maximum, s1 = that maximum, s2 = max_{j != j1} sim_ij (a duplicate of the best
+ *     gives s2 == s1; s2 is absent when n1 == 1);  e1 = 2 (1 - s1), e2 = 2 (1 - s2) in fp32 (the squared L2 distances of unit rows).
+ *   pass_i = (r <= 0 or s2 absent or e1 <= (r r) e2) and (t <= 0 or e1 <= t t);   fwd_i = pass_i ? j1 : -1.
+ *   bwd_j is the same rule on columns, over i < n0 (n0 == 1 is the absent case).
+ *   matches0_i = fwd_i if fwd_i >= 0 and (!mutual_check or bwd[fwd_i] == i), else -1;  mscores0_i = s1 when matched, else 0.
+ *   Rows >= n are -1 / 0.  A pair's result does not depend on the other pairs of the call.
+ * This is hloc's find_nn + mutual_check (ratio and distance tests on 2 (1 - sim), the backward direction filtered before the mutual
+ * check) with two stated differences: the score is the cosine itself and zero for unmatched rows, so that sship_filter_matches yields
+ * distance = 1 - cosine, what the reference's cosineMatch writes (hloc reports (sim + 1) / 2 and does not zero it); and n1 == 1 passes
+ * the ratio test (hloc's topk(2) raises there).
+ * Defaults: r = 0 (off), t = 0 (off), mutual_check on = hloc's NN-mutual.  (r = 0.8: NN-ratio; t = 0.7: NN-superpoint.)
+ * sship_nn_set_params: r <= 0 / t <= 0 turn that test off; NaN r, r > 1 or NaN t -> SSHIP_ERR_INVALID (the handle keeps its setting).
+ * Bad arguments are refused before any device is touched.  Workspaces are sized once at create (max_keypoints 1..4096; max_pairs <= 0 -> 1).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sship_nn sship_nn;
+int sship_nn_create(int max_keypoints, int max_pairs, sship_nn** out);
+void sship_nn_destroy(sship_nn* nn);
+int sship_nn_set_params(sship_nn* nn, float ratio_threshold, float distance_threshold, int mutual_check);
+int sship_nn_get_params(const sship_nn* nn, float* ratio_threshold, float* distance_threshold, int* mutual_check); /* any output may be NULL */
+/* Per-frame calls, synchronous on the handle's own stream, outputs on the host (matches0 [n0], mscores0 [n0]) - like
+ * sship_lg_match_device / _match_host without keypoints.  n0 == 0 or n1 == 0, or n > max_keypoints -> SSHIP_ERR_INVALID. */
+int sship_nn_match_device(sship_nn* nn, int n0, const void* desc0_dev, int n1, const void* desc1_dev, int32_t* matches0, float* mscores0);
+int sship_nn_match_host(sship_nn* nn, int n0, const float* desc0_f32, int n1, const float* desc1_f32, int32_t* matches0, float* mscores0);
+/* Throughput path: the layouts of sship_lg_match_batch_device without kp - n_dev [2*pairs], desc_dev [2*pairs, max_kp, 256] f16 (image 2p
+ * is set 0, 2p+1 set 1 of pair p: what sship_sp_extract_batch_device writes), outputs [pairs, max_kp].  Asynchronous on `stream`, no host
+ * synchronisation inside.  Counts are read on the device and clamped to [0, max_keypoints]; a pair with a zero count is all -1 / 0.
+ * Rows >= n of desc_dev are never used, whatever they hold (NaN, Inf), and every entry of the outputs is written. */
+int sship_nn_match_batch_device(sship_nn* nn, const int* n_dev, const void* desc_dev, int pairs, int32_t* matches0_dev, float* mscores0_dev,
+                                void* stream);
+/* Measurement hook: re-run the launches of the last match call on this handle `iters` times (over the same buffers, which the caller of a
+ * batch call keeps alive), timed with hipEvents on the handle's stream; *avg_ms = mean duration of one call's launches. */
+int sship_nn_bench(sship_nn* nn, int iters, float* avg_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * EigenPlaces place recogniser - include/EigenPlaces.h:19-40, src/EigenPlaces.cc
  * ResNet-18 trunk + L2Norm / GeM / Linear(512, 512) / L2Norm (utils/convert_eigenplaces_to_onnx.py:54-60), used once per
  * keyframe by the loop-closure thread.  weights_path: safetensors of the hub model's state_dict (keys backbone.*,

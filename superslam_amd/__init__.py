@@ -7,8 +7,9 @@ from . import _lib  # noqa: F401
 from .eigenplaces import EigenPlaces  # noqa: F401
 from .frontend import FrontEndBatch, process_stereo  # noqa: F401
 from .lightglue import LightGlue, LightGlueEngine, MatchResult  # noqa: F401
+from .nn_matcher import NNMatcher  # noqa: F401
 from .pool import DescriptorPool, DeviceDescriptors  # noqa: F401
 from .superpoint import Features, SuperPoint  # noqa: F401
 
 __all__ = ["SuperPoint", "LightGlue", "LightGlueEngine", "MatchResult", "Features", "DescriptorPool",
-           "DeviceDescriptors", "FrontEndBatch", "process_stereo", "EigenPlaces"]
+           "DeviceDescriptors", "FrontEndBatch", "process_stereo", "EigenPlaces", "NNMatcher"]

@@ -100,6 +100,14 @@ _SIGS = {
     "sship_lg_debug_set_layers": (ip, [vp, ip]),
     "sship_lg_debug_read": (ip, [vp, ip, ip, ip, ip, vp]),
     "sship_filter_matches": (ip, [vp, vp, ip, vp, vp, vp]),
+    "sship_nn_create": (ip, [ip, ip, C.POINTER(vp)]),
+    "sship_nn_destroy": (None, [vp]),
+    "sship_nn_set_params": (ip, [vp, fp, fp, ip]),
+    "sship_nn_get_params": (ip, [vp, C.POINTER(fp), C.POINTER(fp), C.POINTER(ip)]),
+    "sship_nn_match_device": (ip, [vp, ip, vp, ip, vp, vp, vp]),
+    "sship_nn_match_host": (ip, [vp, ip, vp, ip, vp, vp, vp]),
+    "sship_nn_match_batch_device": (ip, [vp, vp, vp, ip, vp, vp, vp]),
+    "sship_nn_bench": (ip, [vp, ip, C.POINTER(fp)]),
     "sship_ep_create": (ip, [C.c_char_p, ip, ip, C.POINTER(vp)]),
     "sship_ep_destroy": (None, [vp]),
     "sship_ep_descriptor_dim": (ip, [vp]),

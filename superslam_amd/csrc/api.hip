@@ -2117,6 +2117,148 @@ extern "C" int sship_filter_matches(const int32_t* matches0, const float* mscore
 }
 
 // ====================================================================================================
+// Mutual nearest-neighbour matcher (include/sship.h "Nearest-neighbour matcher"; csrc/nn_kernels.hip)
+// ====================================================================================================
+struct sship_nn {
+  int max_kp = 0, max_pairs = 0;
+  float ratio = 0.f, dist = 0.f;
+  int mutual = 1;
+  hipStream_t stream = nullptr;
+  DevBuf ws, desc_stage, lens, m0, ms0;
+  PinBuf h_lens, h_m0, h_ms0, h_desc;
+  // the last call's launch arguments (sship_nn_bench re-runs them; the caller keeps a batch call's buffers alive until then)
+  const int* last_n = nullptr;
+  const _Float16* last_desc = nullptr;
+  int32_t* last_m0 = nullptr;
+  float* last_ms0 = nullptr;
+  int last_pairs = 0;
+};
+extern "C" int sship_nn_create(int max_kp, int max_pairs, sship_nn** out) {
+  if (!out) return fail(SSHIP_ERR_INVALID, "nn_create: null argument");
+  if (max_kp <= 0 || max_kp > kMaxKp) return fail(SSHIP_ERR_INVALID, "nn_create: max_keypoints must be in [1, 4096]");
+  if (max_pairs <= 0) max_pairs = 1;  // as sship_lg_create
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  std::unique_ptr<sship_nn, void (*)(sship_nn*)> nn(new sship_nn(), sship_nn_destroy);
+  nn->max_kp = max_kp; nn->max_pairs = max_pairs;
+  SSHIP_HIP_CHECK(nn->ws.ensure(nn_workspace_floats(max_kp, max_pairs) * 4));
+  SSHIP_HIP_CHECK(nn->desc_stage.ensure(2 * (size_t)max_kp * 256 * 2));
+  SSHIP_HIP_CHECK(nn->lens.ensure(2 * 4));
+  SSHIP_HIP_CHECK(nn->m0.ensure((size_t)max_kp * 4));
+  SSHIP_HIP_CHECK(nn->ms0.ensure((size_t)max_kp * 4));
+  SSHIP_HIP_CHECK(nn->h_lens.ensure(2 * 4));
+  SSHIP_HIP_CHECK(nn->h_m0.ensure((size_t)max_kp * 4));
+  SSHIP_HIP_CHECK(nn->h_ms0.ensure((size_t)max_kp * 4));
+  SSHIP_HIP_CHECK(nn->h_desc.ensure(2 * (size_t)max_kp * 256 * 2));
+  SSHIP_HIP_CHECK(hipMemset(nn->desc_stage.p, 0, nn->desc_stage.bytes));
+  SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&nn->stream, hipStreamDefault));
+  *out = nn.release();
+  return SSHIP_OK;
+}
+extern "C" void sship_nn_destroy(sship_nn* nn) {
+  if (!nn) return;
+  bind_thread();
+  (void)hipDeviceSynchronize();
+  if (nn->stream) (void)hipStreamDestroy(nn->stream);
+  delete nn;
+}
+extern "C" int sship_nn_set_params(sship_nn* nn, float ratio_threshold, float distance_threshold, int mutual_check) {
+  if (!nn) return fail(SSHIP_ERR_INVALID, "nn_set_params: null handle");
+  if (std::isnan(ratio_threshold) || ratio_threshold > 1.f) return fail(SSHIP_ERR_INVALID, "nn_set_params: ratio_threshold must be <= 1");
+  if (std::isnan(distance_threshold)) return fail(SSHIP_ERR_INVALID, "nn_set_params: distance_threshold is NaN");
+  nn->ratio = ratio_threshold; nn->dist = distance_threshold; nn->mutual = mutual_check ? 1 : 0;
+  return SSHIP_OK;
+}
+extern "C" int sship_nn_get_params(const sship_nn* nn, float* ratio_threshold, float* distance_threshold, int* mutual_check) {
+  if (!nn) return fail(SSHIP_ERR_INVALID, "nn_get_params: null handle");
+  if (ratio_threshold) *ratio_threshold = nn->ratio;
+  if (distance_threshold) *distance_threshold = nn->dist;
+  if (mutual_check) *mutual_check = nn->mutual;
+  return SSHIP_OK;
+}
+static int nn_launch(sship_nn* nn, const int* n, const _Float16* desc, int pairs, int32_t* m0, float* ms0, hipStream_t s) {
+  launch_nn_match(desc, n, nn->max_kp, pairs, nn->ws.as<float>(), nn->ratio, nn->dist, nn->mutual, m0, ms0, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  nn->last_n = n; nn->last_desc = desc; nn->last_m0 = m0; nn->last_ms0 = ms0; nn->last_pairs = pairs;
+  return SSHIP_OK;
+}
+extern "C" int sship_nn_match_batch_device(sship_nn* nn, const int* n, const void* desc, int pairs, int32_t* m0, float* ms0, void* stream) {
+  if (!nn || !n || !desc || !m0 || !ms0) return fail(SSHIP_ERR_INVALID, "nn_match_batch_device: null argument");
+  if (pairs <= 0 || pairs > nn->max_pairs) return fail(SSHIP_ERR_INVALID, "nn_match_batch_device: pairs exceeds max_pairs");
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = legacy default stream: ordered after an extractor call made with NULL
+  g_timer.begin_if_idle(s);
+  if (int rc = nn_launch(nn, n, static_cast<const _Float16*>(desc), pairs, m0, ms0, s)) return rc;
+  g_timer.mark("nn_match:stream_final", s);
+  return SSHIP_OK;
+}
+// one pair out of the handle's own staging buffers (descriptors already enqueued into desc_stage on the handle's stream)
+static int nn_match_common(sship_nn* nn, int n0, int n1, int32_t* matches0, float* mscores0) {
+  hipStream_t s = nn->stream;
+  nn->h_lens.as<int>()[0] = n0; nn->h_lens.as<int>()[1] = n1;
+  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->lens.p, nn->h_lens.p, 8, hipMemcpyHostToDevice, s));
+  if (int rc = nn_launch(nn, nn->lens.as<int>(), nn->desc_stage.as<_Float16>(), 1, nn->m0.as<int32_t>(), nn->ms0.as<float>(), s)) return rc;
+  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->h_m0.p, nn->m0.p, (size_t)n0 * 4, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->h_ms0.p, nn->ms0.p, (size_t)n0 * 4, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipStreamSynchronize(s));
+  memcpy(matches0, nn->h_m0.p, (size_t)n0 * 4);
+  memcpy(mscores0, nn->h_ms0.p, (size_t)n0 * 4);
+  return SSHIP_OK;
+}
+static int nn_check_pair(const sship_nn* nn, int n0, const void* d0, int n1, const void* d1, const void* m0, const void* ms0, const char* who) {
+  if (!nn || !d0 || !d1 || !m0 || !ms0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  if (n0 <= 0 || n1 <= 0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": empty descriptor set");
+  if (n0 > nn->max_kp || n1 > nn->max_kp) return fail(SSHIP_ERR_INVALID, std::string(who) + ": n exceeds max_keypoints");
+  return SSHIP_OK;
+}
+extern "C" int sship_nn_match_device(sship_nn* nn, int n0, const void* desc0, int n1, const void* desc1, int32_t* matches0, float* mscores0) {
+  if (int rc = nn_check_pair(nn, n0, desc0, n1, desc1, matches0, mscores0, "nn_match_device")) return rc;
+  bind_thread();
+  hipStream_t s = nn->stream;
+  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->desc_stage.p, desc0, (size_t)n0 * 512, hipMemcpyDeviceToDevice, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->desc_stage.as<_Float16>() + (size_t)nn->max_kp * 256, desc1, (size_t)n1 * 512, hipMemcpyDeviceToDevice, s));
+  return nn_match_common(nn, n0, n1, matches0, mscores0);
+}
+extern "C" int sship_nn_match_host(sship_nn* nn, int n0, const float* desc0, int n1, const float* desc1, int32_t* matches0, float* mscores0) {
+  if (int rc = nn_check_pair(nn, n0, desc0, n1, desc1, matches0, mscores0, "nn_match_host")) return rc;
+  bind_thread();
+  hipStream_t s = nn->stream;
+  _Float16* hd = nn->h_desc.as<_Float16>();  // CV_32F -> fp16 on the host, as sship_lg_match_host
+  for (size_t i = 0; i < (size_t)n0 * 256; ++i) hd[i] = (_Float16)desc0[i];
+  for (size_t i = 0; i < (size_t)n1 * 256; ++i) hd[(size_t)nn->max_kp * 256 + i] = (_Float16)desc1[i];
+  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->desc_stage.p, hd, (size_t)n0 * 512, hipMemcpyHostToDevice, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->desc_stage.as<_Float16>() + (size_t)nn->max_kp * 256, hd + (size_t)nn->max_kp * 256, (size_t)n1 * 512,
+                                 hipMemcpyHostToDevice, s));
+  return nn_match_common(nn, n0, n1, matches0, mscores0);
+}
+// Measurement hook (include/sship.h): the last call's two launches re-run `iters` times on the handle's stream.
+extern "C" int sship_nn_bench(sship_nn* nn, int iters, float* avg_ms) {
+  if (!nn || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "nn_bench: bad arguments");
+  if (nn->last_pairs <= 0) return fail(SSHIP_ERR_INVALID, "nn_bench: run a match on this handle first");
+  bind_thread();
+  hipStream_t s = nn->stream;
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
+  auto run = [&]() -> hipError_t {
+    launch_nn_match(nn->last_desc, nn->last_n, nn->max_kp, nn->last_pairs, nn->ws.as<float>(), nn->ratio, nn->dist, nn->mutual, nn->last_m0,
+                    nn->last_ms0, s);
+    return hipGetLastError();
+  };
+  SSHIP_HIP_CHECK(run());  // warm
+  hipEvent_t e0, e1;
+  SSHIP_HIP_CHECK(hipEventCreate(&e0));
+  SSHIP_HIP_CHECK(hipEventCreate(&e1));
+  SSHIP_HIP_CHECK(hipEventRecord(e0, s));
+  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
+  SSHIP_HIP_CHECK(hipEventRecord(e1, s));
+  SSHIP_HIP_CHECK(hipEventSynchronize(e1));
+  float ms = 0.f;
+  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  *avg_ms = ms / iters;
+  return SSHIP_OK;
+}
+
+// ====================================================================================================
 // EigenPlaces place recogniser: include/EigenPlaces.h:19-40, src/EigenPlaces.cc:47-174
 // ====================================================================================================
 struct sship_ep {

@@ -196,4 +196,11 @@ void launch_lg_sim(const _Float16* md, const int* lens, LgDims d, float* sim, hi
 void launch_lg_assign(const _Float16* md, const float* logsig, const int* lens, LgDims d, float* ws, float* pcol, int max_kp,
                       int32_t* matches0, float* mscores0, float thr, int stage, hipStream_t s);
 
+// ---- nn_kernels.hip : mutual nearest-neighbour matcher (sship_nn_*) ----
+// desc [2 pairs][max_kp][256] fp16, lens [2 pairs] (device, clamped to [0, max_kp] by the kernels); ws: nn_workspace_floats(max_kp, max_pairs)
+// floats of top-2 partials; ratio / dist <= 0 turn that test off; outputs [pairs][max_kp], every entry written
+size_t nn_workspace_floats(int max_kp, int max_pairs);
+void launch_nn_match(const _Float16* desc, const int* lens, int max_kp, int pairs, float* ws, float ratio, float dist, int mutual,
+                     int32_t* matches0, float* mscores0, hipStream_t s);
+
 }  // namespace sship
