@@ -20,11 +20,14 @@
 // build:  g++ -std=c++17 -O2 -Iinclude examples/frontend_benchmark.cc -o frontend_benchmark
 //             -Lsuperslam_amd/lib -lsuperslam_hip -Wl,-rpath,$PWD/superslam_amd/lib -Wl,-rpath,/opt/rocm/lib -lpthread -lz
 // run:    ./frontend_benchmark --sp sp.safetensors --lg lg.safetensors (--sequence DIR | --synthetic 200) [--keyframe-match]
-//                              [--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--matcher lightglue|nn]
+//                              [--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--subpixel] [--matcher lightglue|nn]
+//                              [--dump-keypoints FILE]
 //
 // --matcher nn: the mutual nearest-neighbour matcher (superslam_hip::NNMatcher, hloc's NN-mutual) in LightGlue's place - same
 // IFeatureMatcher calls, no --lg needed.  Default: lightglue.
 // --bilinear: descriptors by upstream SuperPoint's bilinear sampling (SSHIP_DESC_BILINEAR) instead of the reference's nearest-cell gather.
+// --subpixel: keypoints refined by the log-parabola peak fit (SSHIP_KP_SUBPIXEL) instead of the reference's integer score-map pixels.
+// --dump-keypoints FILE: the first frame's keypoints as int32 n_left, n_right | f32 [n_left][3] (x, y, score) | f32 [n_right][3].
 //
 // Cross-frame pipelining (default with the ring; --no-pipeline turns it off): as soon as frame t's extraction has returned, frame
 // t+1's extraction is ENQUEUED on the extractor's stream (sship_sp_ring_submit) - before frame t's LightGlue match - so the next
@@ -117,11 +120,11 @@ struct Source {
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string sp_path, lg_path, matcher_name = "lightglue";
+  std::string sp_path, lg_path, matcher_name = "lightglue", dump_path;
   Source src;
   int max_kp = 600, border = 4;
   double thr = 0.005;
-  bool keyframe = false, use_ring = true, pipeline = true, bilinear = false;
+  bool keyframe = false, use_ring = true, pipeline = true, bilinear = false, subpixel = false;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -136,13 +139,16 @@ int main(int argc, char** argv) {
     else if (a == "--no-ring") use_ring = false;
     else if (a == "--no-pipeline") pipeline = false;
     else if (a == "--bilinear") bilinear = true;
+    else if (a == "--subpixel") subpixel = true;
+    else if (a == "--dump-keypoints") dump_path = next();
     else if (a == "--matcher") matcher_name = next();
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
   const bool use_nn = matcher_name == "nn";
   if (sp_path.empty() || (!use_nn && (lg_path.empty() || matcher_name != "lightglue")) || (src.sequence.empty() && src.synthetic <= 0)) {
     std::fprintf(stderr, "usage: %s --sp W.safetensors --lg W.safetensors (--sequence DIR | --synthetic N) [--keyframe-match] "
-                         "[--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--matcher lightglue|nn]\n", argv[0]);
+                         "[--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--subpixel] [--matcher lightglue|nn] "
+                         "[--dump-keypoints FILE]\n", argv[0]);
     return 2;
   }
 
@@ -166,6 +172,7 @@ int main(int argc, char** argv) {
   sh::NNMatcher nn(max_kp);
   sh::IFeatureMatcher& matcher = use_nn ? static_cast<sh::IFeatureMatcher&>(nn) : lightglue;
   if (bilinear) extractor.set_descriptor_sampling(SSHIP_DESC_BILINEAR);  // kept, applied by initialize()
+  if (subpixel) extractor.set_keypoint_refinement(SSHIP_KP_SUBPIXEL);
   if (!extractor.initialize() || !(use_nn ? nn.initialize() : lightglue.initialize())) {
     std::fprintf(stderr, "initialisation failed: %s\n", sship_last_error());
     return 1;
@@ -223,6 +230,17 @@ int main(int argc, char** argv) {
         if (have_next && extractor.ring_submit((ni + 1) % kDepth)) ++submitted_ahead;
       }
     } else feats = extractor.extract_stereo(sh::Image{plain[2 * slot].data(), rows, cols, 1, 0}, sh::Image{plain[2 * slot + 1].data(), rows, cols, 1, 0});
+    if (ni == 0 && !dump_path.empty()) {
+      std::FILE* o = std::fopen(dump_path.c_str(), "wb");
+      if (!o) std::fprintf(stderr, "cannot write %s\n", dump_path.c_str());  // the run goes on: the decoder thread is live
+      else {
+        const int32_t n[2] = {(int32_t)feats.first.keypoints.size(), (int32_t)feats.second.keypoints.size()};
+        std::fwrite(n, 4, 2, o);
+        for (const sh::Features* ft : {&feats.first, &feats.second})
+          for (const sh::KeyPoint& k : ft->keypoints) { const float v[3] = {k.x, k.y, k.response}; std::fwrite(v, 4, 3, o); }
+        std::fclose(o);
+      }
+    }
     sh::MatchResult lr = matcher.match(feats.first.keypoints, feats.first.descriptors, feats.second.keypoints, feats.second.descriptors);
     for (const sh::DMatch& m : lr.matches) {  // StereoFrontEnd's gate
       const sh::KeyPoint &kl = feats.first.keypoints[m.queryIdx], &kr = feats.second.keypoints[m.trainIdx];
@@ -250,6 +268,7 @@ int main(int argc, char** argv) {
               use_ring ? "pinned upload ring" : "copying host API", ts.empty() ? "" : ", times.txt");
   std::printf("frames           : %zu\n", ms.size());
   if (use_nn) std::printf("matcher          : nn (mutual nearest neighbour)\n");
+  if (subpixel) std::printf("keypoints        : sub-pixel (SSHIP_KP_SUBPIXEL)\n");
   if (use_ring) std::printf("pipelined        : %s (%ld of %zu extractions enqueued one frame ahead)\n", pipeline ? "yes" : "no", submitted_ahead, ms.size());
   std::printf("per-frame ms      mean=%.2f p50=%.2f p95=%.2f max=%.2f\n", mean, percentile(ms, 0.50), percentile(ms, 0.95), percentile(ms, 1.0));
   std::printf("throughput        : %.2f fps over %.1fs wall\n", wall > 0 ? ms.size() / wall : 0.0, wall);

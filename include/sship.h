@@ -121,6 +121,29 @@ int sship_sample_descriptors_bilinear(const void* grid_fp16_dev, int channels, i
 int sship_sample_descriptors_bilinear_hwc(const void* grid_fp16_dev, int channels, int grid_h, int grid_w,
                                           const float* kp_xy_dev, int num_keypoints, void* out_fp16_dev, void* stream);
 
+/* Sub-pixel keypoint refinement: the stage twin of SSHIP_KP_SUBPIXEL below (the reference has no counterpart).  The three-point
+ * Gaussian (log-parabola) peak fit, per axis, on the PRE-NMS log-probabilities of a Hc x Wc grid of 65-logit cells:
+ *   L[h, w] = logit[cell(h, w), pos(h, w)] - logsumexp(all 65 logits of that cell)      cell = (h / 8, w / 8), pos = 8 (h % 8) + (w % 8)
+ * the log of the softmax score the NMS compared (the dustbin, logit 64, is part of the normaliser).  For a keypoint at the integer
+ * score-map pixel (h, w), on the x axis:
+ *   a = L[h, w-1], b = L[h, w], c = L[h, w+1], den = 2b - a - c
+ *   dx = clamp(0.5 (c - a) / den, -0.5, 0.5)  if both neighbours are inside the 8Hc x 8Wc map and den > 0, else dx = 0
+ * and dy the same with L[h-1, w] and L[h+1, w].  Neighbours inside an extractor's remove_borders band are inside the map and are used.
+ * All of it is fp32 (log-scores as (v - max) - log(sum of exponentials)).
+ *   - A keypoint is a 9x9 maximum of the score, so b >= a and b >= c and |dx| <= 0.5 holds without the clamp, which only guards rounding.
+ *   - Refined keypoints therefore stay at least nms_radius pixels apart.
+ *   - A neighbour may lie in another cell and have another normaliser: that is why L is used and not the raw logit.
+ *   - Scores that are samples of a Gaussian inside one cell return its mean exactly.
+ * pix_dev: num_keypoints packed pixels (h << 16) | w, the packing k_topk writes; a pixel outside the map is clamped into it.
+ * offsets_dev: [num_keypoints, 2] fp32 = (dx, dy).  num_keypoints <= 0 is a no-op before any other check; otherwise NULL pointers or
+ * Hc, Wc < 1 (or > 8191) -> SSHIP_ERR_INVALID.  No input can make a lane read outside the buffer.
+ * sship_refine_keypoints reads CHW logits [65, Hc, Wc] (what sship_sp_dense returns), the _hwc variant cell-major rows
+ * [Hc, Wc, row_stride] with row_stride >= 65 (the extractor's own buffer has 68: 16-byte aligned rows are read 16 bytes at a time). */
+int sship_refine_keypoints(const float* logits_chw_dev, int Hc, int Wc, const int* pix_dev, int num_keypoints, float* offsets_dev,
+                           void* stream);
+int sship_refine_keypoints_hwc(const float* logits_dev, int row_stride, int Hc, int Wc, const int* pix_dev, int num_keypoints,
+                               float* offsets_dev, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Detector post-processing stages (exposed so each can be parity-tested bit-exactly)
  * ---------------------------------------------------------------------------------------------- */
@@ -180,6 +203,22 @@ int sship_sp_max_keypoints(const sship_sp* sp);
 enum { SSHIP_DESC_NEAREST = 0, SSHIP_DESC_BILINEAR = 1 };
 int sship_sp_set_descriptor_sampling(sship_sp* sp, int mode);
 int sship_sp_descriptor_sampling(const sship_sp* sp);
+/* Where a keypoint is reported.  Per handle; it applies to every call made after it returns, through every entry point that yields
+ * keypoints: sship_sp_extract, _extract_stereo, _extract_stereo_ring, _ring_submit, _infer_host, _extract_batch_device and
+ * sship_frontend_batch_device (LightGlue then receives the refined coordinates).
+ *   SSHIP_KP_INTEGER (default): the reference's rule, x = w * scale_x, y = h * scale_y at the integer score-map pixel (h, w)
+ *     (src/SuperPoint.cc:711-719) - today's path, bit for bit, with the launches it always made.
+ *   SSHIP_KP_SUBPIXEL: x = ((float)w + dx) * scale_x, y = ((float)h + dy) * scale_y with the same fp32 scales and (dx, dy) from the rule
+ *     stated at sship_refine_keypoints below, evaluated on the detector logits of the same call.  One more launch (k_kp_refine), in
+ *     this mode only.  The reference has no counterpart.
+ * The mode changes x and y ONLY: counts, order, the score kp[2], the cells and the descriptors are the same bits as with the mode off.
+ * In both descriptor-sampling modes the descriptors keep reading the integer pixel; the two modes are independent.
+ * Any other mode or a NULL handle -> SSHIP_ERR_INVALID, the mode unchanged; also SSHIP_ERR_INVALID while a sship_sp_ring_submit is
+ * pending (collect it first).  In the developer build the setter would refuse SSHIP_KP_SUBPIXEL under a SUPERSLAM_HIP_CONVPB* /
+ * _CONV* switch that does not leave the fp32 logits in device memory; every switch there is today leaves them. */
+enum { SSHIP_KP_INTEGER = 0, SSHIP_KP_SUBPIXEL = 1 };
+int sship_sp_set_keypoint_refinement(sship_sp* sp, int mode);
+int sship_sp_keypoint_refinement(const sship_sp* sp);   /* NULL -> SSHIP_KP_INTEGER */
 
 /* SuperPoint::extract (src/SuperPoint.cc:895-899 -> infer_device :597-676): host u8 image, 1 or 3 (BGR)
  * channels, row stride in bytes.  Synchronous. */
@@ -465,7 +504,8 @@ int sship_get_stage_timings(const char** labels, float* ms, int max_stages);
 int sship_sp_bench_layer(sship_sp* sp, int layer, int batch, int h, int w, int iters, float* avg_ms, double* macs);
 /* (layer ids 12-14 are the memory-bound stages of the same handle: 12 = softmax + depth-to-space + NMS + threshold +
  * candidate compaction, 13 = top-k, 14 = descriptor head at the selected keypoints (nearest or bilinear, as the handle is set); *macs = 0 for them.
- * 15 = conv2a + conv2b + pool as the ONE launch throughput batches run instead of layers 2 and 3 (csrc/conv_fuse2.hip; *macs = both layers').)
+ * 15 = conv2a + conv2b + pool as the ONE launch throughput batches run instead of layers 2 and 3 (csrc/conv_fuse2.hip; *macs = both layers').
+ * 16 = the sub-pixel refinement of the selected keypoints (k_kp_refine), timed whatever mode the handle is in; *macs = 0.)
  *
  * Same for one stage of the matcher, over the state the last match call left on this handle, timed with hipEvents on the
  * handle's stream: 0 first Wqkv projection, 1 self attention, 2 cross attention (both directions), 3 SelfBlock FFN + the

@@ -155,9 +155,25 @@ public:
     if (descriptor_sampling_ != SSHIP_DESC_NEAREST && sship_sp_set_descriptor_sampling(sp_, descriptor_sampling_) != SSHIP_OK) {
       last_error_ = sship_last_error(); sship_sp_destroy(sp_); sp_ = nullptr; return false;
     }
+    if (keypoint_refinement_ != SSHIP_KP_INTEGER && sship_sp_set_keypoint_refinement(sp_, keypoint_refinement_) != SSHIP_OK) {
+      last_error_ = sship_last_error(); sship_sp_destroy(sp_); sp_ = nullptr; return false;
+    }
     pool_.reset(new DescriptorPool(sship_sp_pool(sp_), max_keypoints_, descriptor_dim));
     return true;
   }
+  // Where a keypoint is reported (include/sship.h): SSHIP_KP_INTEGER (default, the reference's integer score-map pixel) or
+  // SSHIP_KP_SUBPIXEL (the log-parabola peak fit on the detector's log-scores).  x and y only: counts, order, scores and descriptors do
+  // not change.  Before initialize() the mode is validated, kept and applied by initialize(); afterwards it applies to the calls after
+  // this one.  false + last_error() for any other mode or while a ring submission is pending (the mode is unchanged).
+  bool set_keypoint_refinement(int mode) {
+    if (sp_ && sship_sp_set_keypoint_refinement(sp_, mode) != SSHIP_OK) { last_error_ = sship_last_error(); return false; }
+    if (!sp_ && mode != SSHIP_KP_INTEGER && mode != SSHIP_KP_SUBPIXEL) {
+      last_error_ = "set_keypoint_refinement: mode must be 0 (integer) or 1 (sub-pixel)"; return false;
+    }
+    keypoint_refinement_ = mode;
+    return true;
+  }
+  int keypoint_refinement() const { return keypoint_refinement_; }
   // How a keypoint's descriptor is read from the descriptor map (include/sship.h): SSHIP_DESC_NEAREST (default, the reference's
   // nearest-cell gather) or SSHIP_DESC_BILINEAR (upstream SuperPoint's sample_descriptors).  Descriptors only: keypoints, scores and
   // counts do not change.  Before initialize() the mode is validated, kept and applied by initialize(); afterwards it applies to the
@@ -263,6 +279,7 @@ private:
   double keypoint_threshold_;
   int remove_borders_;
   int descriptor_sampling_ = SSHIP_DESC_NEAREST;
+  int keypoint_refinement_ = SSHIP_KP_INTEGER;
   sship_sp* sp_ = nullptr;
   std::unique_ptr<DescriptorPool> pool_;
   std::string last_error_;

@@ -78,6 +78,14 @@ public:
     return ok;
   }
   int descriptor_sampling() const { return impl_.descriptor_sampling(); }
+  // Sub-pixel keypoints (include/sship.h: SSHIP_KP_SUBPIXEL); no counterpart in the reference, whose keypoints are integer score-map
+  // pixels.  Off (SSHIP_KP_INTEGER) unless called; kept before initialize() and applied by it.
+  bool set_keypoint_refinement(int mode) {
+    const bool ok = impl_.set_keypoint_refinement(mode);
+    if (!ok) SLOG_ERROR("SuperPoint(HIP): {}", impl_.last_error());
+    return ok;
+  }
+  int keypoint_refinement() const { return impl_.keypoint_refinement(); }
   bool infer(const cv::Mat& image, std::vector<cv::KeyPoint>& keypoints, cv::Mat& descriptors) {
     cv::Mat keep;
     std::vector<superslam_hip::KeyPoint> kp;

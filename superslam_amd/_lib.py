@@ -65,6 +65,8 @@ _SIGS = {
     "sship_gather_normalize_hwc": (ip, [vp, ip, ip, ip, vp, vp, ip, vp, vp]),
     "sship_sample_descriptors_bilinear": (ip, [vp, ip, ip, ip, vp, ip, vp, vp]),
     "sship_sample_descriptors_bilinear_hwc": (ip, [vp, ip, ip, ip, vp, ip, vp, vp]),
+    "sship_refine_keypoints": (ip, [vp, ip, ip, vp, ip, vp, vp]),
+    "sship_refine_keypoints_hwc": (ip, [vp, ip, ip, ip, vp, ip, vp, vp]),
     "sship_nms": (ip, [vp, ip, ip, ip, ip, vp, vp]),
     "sship_select_topk": (ip, [vp, ip, ip, ip, ip, C.c_double, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_create": (ip, [C.POINTER(SpConfig), C.POINTER(vp)]),
@@ -73,6 +75,8 @@ _SIGS = {
     "sship_sp_max_keypoints": (ip, [vp]),
     "sship_sp_set_descriptor_sampling": (ip, [vp, ip]),
     "sship_sp_descriptor_sampling": (ip, [vp]),
+    "sship_sp_set_keypoint_refinement": (ip, [vp, ip]),
+    "sship_sp_keypoint_refinement": (ip, [vp]),
     "sship_sp_extract": (ip, [vp, vp, ip, ip, ip, ip, C.POINTER(Features)]),
     "sship_sp_extract_stereo": (ip, [vp, vp, vp, ip, ip, ip, ip, C.POINTER(Features), C.POINTER(Features)]),
     "sship_sp_infer_host": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, C.POINTER(ip)]),

@@ -560,6 +560,27 @@ extern "C" int sship_sample_descriptors_bilinear_hwc(const void* grid, int chann
                                                      void* stream) {
   return sample_bilinear(true, grid, channels, gh, gw, kp_xy, n, out, stream);
 }
+static int refine_stage(const float* logits, size_t cell_stride, size_t chan_stride, int Hc, int Wc, const int* pix, int n, float* offsets, void* stream) {
+  bind_thread();
+  if (n <= 0) return SSHIP_OK;
+  if (!logits || !pix || !offsets) return fail(SSHIP_ERR_INVALID, "refine_keypoints: null argument");
+  if (Hc < 1 || Wc < 1 || Hc > 8191 || Wc > 8191) return fail(SSHIP_ERR_INVALID, "refine_keypoints: the cell grid must be 1 .. 8191 cells a side");
+  if (int rc = require_device()) return rc;
+  KpRefineArgs a{};
+  a.logits = logits; a.img_stride = 0; a.cell_stride = cell_stride; a.chan_stride = chan_stride; a.Hc = Hc; a.Wc = Wc;
+  a.pix = pix; a.n_dev = nullptr; a.n_host = n; a.max_kp = n; a.offsets = offsets;
+  launch_kp_refine(a, 1, static_cast<hipStream_t>(stream));
+  SSHIP_HIP_CHECK(hipGetLastError());
+  return SSHIP_OK;
+}
+extern "C" int sship_refine_keypoints(const float* logits_chw, int Hc, int Wc, const int* pix, int n, float* offsets, void* stream) {
+  return refine_stage(logits_chw, 1, (size_t)(Hc > 0 ? Hc : 0) * (size_t)(Wc > 0 ? Wc : 0), Hc, Wc, pix, n, offsets, stream);
+}
+extern "C" int sship_refine_keypoints_hwc(const float* logits, int row_stride, int Hc, int Wc, const int* pix, int n, float* offsets,
+                                          void* stream) {
+  if (n > 0 && row_stride < 65) { bind_thread(); return fail(SSHIP_ERR_INVALID, "refine_keypoints_hwc: row_stride must be at least 65"); }
+  return refine_stage(logits, (size_t)(row_stride > 0 ? row_stride : 0), 1, Hc, Wc, pix, n, offsets, stream);
+}
 extern "C" int sship_nms(const float* scores, int batch, int h, int w, int radius, float* out, void* stream) {
   bind_thread();
   if (!scores || !out || batch <= 0 || h <= 0 || w <= 0) return fail(SSHIP_ERR_INVALID, "nms: bad arguments");
@@ -620,7 +641,8 @@ struct sship_sp {
   hipStream_t cand_zero_stream = nullptr;                      // ... for work ordered after the last k_topk on THIS stream
   DevBuf kp, cell_h, cell_w, n_dev, desc_stage, gray_in;
   int desc_sampling = SSHIP_DESC_NEAREST;  // sship_sp_set_descriptor_sampling
-  DevBuf pix;                              // [B, max_kp] score-map pixels of the keypoints (h << 16 | w): written by k_topk in bilinear mode only
+  int kp_refinement = SSHIP_KP_INTEGER;    // sship_sp_set_keypoint_refinement
+  DevBuf pix;                              // [B, max_kp] score-map pixels of the keypoints (h << 16 | w): written by k_topk in bilinear / sub-pixel mode only
   PinBuf h_kp, h_n, h_img;
   int cap = 0;
   float thr_f = 0.f;
@@ -781,6 +803,17 @@ static int sp_network(sship_sp* sp, const uint8_t* imgs, int B, int H, int W, hi
   return SSHIP_OK;
 }
 
+// k_topk writes the packed score-map pixels only for the modes that read them
+static bool sp_wants_pix(const sship_sp* sp) { return sp->desc_sampling == SSHIP_DESC_BILINEAR || sp->kp_refinement == SSHIP_KP_SUBPIXEL; }
+// sub-pixel mode: overwrite x, y of the keypoints of `B` images (kp [B, max_kp, 3], counts on the device) - k_kp_refine
+static hipError_t sp_refine(sship_sp* sp, int B, int Hc, int Wc, float* kp, const int* n_dev, float scale_x, float scale_y, hipStream_t s) {
+  KpRefineArgs r{};
+  r.logits = sp->logits.as<float>(); r.img_stride = (size_t)Hc * Wc * kLogitStride; r.cell_stride = kLogitStride; r.chan_stride = 1;
+  r.Hc = Hc; r.Wc = Wc; r.pix = sp->pix.as<int>(); r.n_dev = n_dev; r.n_host = 0; r.max_kp = sp->cfg.max_keypoints;
+  r.kp_xys = kp; r.scale_x = scale_x; r.scale_y = scale_y; r.offsets = nullptr;
+  launch_kp_refine(r, B, s);
+  return hipGetLastError();
+}
 // heatmap softmax + NMS + threshold -> candidates -> top-k keypoints/cells (all on device).
 static int sp_select(sship_sp* sp, int B, int H, int W, float* scores_out, float* kp_out, int* n_out, hipStream_t s) {
   int H2, W2, H4, W4, Hc, Wc;
@@ -806,10 +839,18 @@ static int sp_select(sship_sp* sp, int B, int H, int W, float* scores_out, float
   t.scale_y = static_cast<float>(H) / (Hc * 8);
   t.desc_h = Hc; t.desc_w = Wc; t.kp_xys = kp_out; t.cell_h = sp->cell_h.as<int>(); t.cell_w = sp->cell_w.as<int>();
   t.n_out = n_out; t.n_cand_out = nullptr; t.reset_count = a.cand_count;
-  t.pix = sp->desc_sampling == SSHIP_DESC_BILINEAR ? sp->pix.as<int>() : nullptr;
+  t.pix = sp_wants_pix(sp) ? sp->pix.as<int>() : nullptr;
   launch_topk(t, B, s);
   SSHIP_HIP_CHECK(hipGetLastError());
   sp->cand_zero_n = B;
+  if (sp->kp_refinement == SSHIP_KP_SUBPIXEL) {
+    // one more launch, in this mode only: x, y of every keypoint from the logits convPb left in sp->logits (nothing writes them before the
+    // next call's network) at the pixels k_topk left in sp->pix.  Scores, cells and the descriptor head do not see it.
+    g_timer.mark_fine("sp_extract_stereo:select/topk", s);
+    SSHIP_HIP_CHECK(sp_refine(sp, B, Hc, Wc, kp_out, n_out, t.scale_x, t.scale_y, s));
+    g_timer.mark(g_profiling >= 2 ? "sp_extract_stereo:select/kp_refine" : "sp_extract_stereo:select", s);
+    return SSHIP_OK;
+  }
   g_timer.mark(g_profiling >= 2 ? "sp_extract_stereo:select/topk" : "sp_extract_stereo:select", s);
   return SSHIP_OK;
 }
@@ -952,6 +993,18 @@ extern "C" int sship_sp_set_descriptor_sampling(sship_sp* sp, int mode) {
   return SSHIP_OK;
 }
 extern "C" int sship_sp_descriptor_sampling(const sship_sp* sp) { return sp ? sp->desc_sampling : SSHIP_DESC_NEAREST; }
+extern "C" int sship_sp_set_keypoint_refinement(sship_sp* sp, int mode) {
+  if (!sp) return fail(SSHIP_ERR_INVALID, "sp_set_keypoint_refinement: null handle");
+  if (mode != SSHIP_KP_INTEGER && mode != SSHIP_KP_SUBPIXEL)
+    return fail(SSHIP_ERR_INVALID, "sp_set_keypoint_refinement: mode must be 0 (integer) or 1 (sub-pixel)");
+  for (const auto& pd : sp->ring.pending)
+    if (pd.active) return fail(SSHIP_ERR_INVALID, "sp_set_keypoint_refinement: a ring submission is pending (collect it with sship_sp_extract_stereo_ring first)");
+  // developer build: every detector-head switch (SUPERSLAM_HIP_CONVPB=igemm, the SUPERSLAM_HIP_CONV* encoder kernels) still writes the
+  // fp32 logits as 68-float rows into sp->logits, so none of them has to refuse SSHIP_KP_SUBPIXEL; a switch that keeps the logits on chip must.
+  sp->kp_refinement = mode;
+  return SSHIP_OK;
+}
+extern "C" int sship_sp_keypoint_refinement(const sship_sp* sp) { return sp ? sp->kp_refinement : SSHIP_KP_INTEGER; }
 
 extern "C" int sship_sp_extract_batch_device(sship_sp* sp, const uint8_t* imgs, int batch, int h, int w, void* desc_out,
                                              float* kp_out, int* n_out, void* stream) {
@@ -1011,7 +1064,7 @@ extern "C" int sship_mfma_probe(int random_operands, float* tflops) {
 extern "C" int sship_sp_bench_layer(sship_sp* sp, int layer, int batch, int h, int w, int iters, float* avg_ms,
                                     double* macs) {
   bind_thread();
-  if (!sp || !avg_ms || iters <= 0 || layer < 0 || layer > 15) return fail(SSHIP_ERR_INVALID, "sp_bench_layer: bad arguments");
+  if (!sp || !avg_ms || iters <= 0 || layer < 0 || layer > 16) return fail(SSHIP_ERR_INVALID, "sp_bench_layer: bad arguments");
   if (batch > sp->wsB || h != sp->wsH || w != sp->wsW) return fail(SSHIP_ERR_INVALID, "sp_bench_layer: run the network at this shape first");
   if (layer <= 1 && !sp->img_valid)
     return fail(SSHIP_ERR_INVALID, "sp_bench_layer: the handle holds no copy of the last input - make one call with sship_set_profiling(1) first "
@@ -1023,6 +1076,7 @@ extern "C" int sship_sp_bench_layer(sship_sp* sp, int layer, int batch, int h, i
            *a2b = sp->a2b.as<_Float16>(), *a3a = sp->a3a.as<_Float16>(), *a3b = sp->a3b.as<_Float16>(),
            *a4a = sp->a4a.as<_Float16>(), *a4b = sp->a4b.as<_Float16>(), *aPa = sp->aPa.as<_Float16>(),
            *aDa = sp->aDa.as<_Float16>();
+  const bool for_refine = layer == 16;  // its k_topk launch leaves the packed pixels whatever mode the handle is in
   auto run = [&]() -> hipError_t {
     switch (layer) {
       case 0: launch_conv1a(sp->img.as<uint8_t>(), sp->w1a, sp->b1a, a1a, batch, h, w, s); return hipGetLastError();  // stand-alone (not on the path)
@@ -1057,17 +1111,19 @@ extern "C" int sship_sp_bench_layer(sship_sp* sp, int layer, int batch, int h, i
         t.scale_x = static_cast<float>(w) / (Wc * 8); t.scale_y = static_cast<float>(h) / (Hc * 8);
         t.desc_h = Hc; t.desc_w = Wc; t.kp_xys = sp->kp.as<float>(); t.cell_h = sp->cell_h.as<int>(); t.cell_w = sp->cell_w.as<int>();
         t.n_out = sp->n_dev.as<int>(); t.n_cand_out = nullptr;
-        t.pix = sp->desc_sampling == SSHIP_DESC_BILINEAR ? sp->pix.as<int>() : nullptr;
+        t.pix = (sp_wants_pix(sp) || for_refine) ? sp->pix.as<int>() : nullptr;
         launch_topk(t, batch, s);
         return hipGetLastError();
       }
+      case 16:  // sub-pixel refinement of the selected keypoints (k_kp_refine), whatever mode the handle is in
+        return sp_refine(sp, batch, Hc, Wc, sp->kp.as<float>(), sp->n_dev.as<int>(), static_cast<float>(w) / (Wc * 8), static_cast<float>(h) / (Hc * 8), s);
       default:  // 14: descriptor head at the selected keypoints (k_desc_head_sparse) into the staging rows
         if (hipError_t e = sp->desc_stage.ensure((size_t)batch * sp->cfg.max_keypoints * 512)) return e;
         return desc_head(sp, 0, Hc, Wc, sp->cell_h.as<int>(), sp->cell_w.as<int>(), sp->n_dev.as<int>(), batch, sp->desc_stage.as<_Float16>(),
                          (size_t)sp->cfg.max_keypoints * 256, s);
     }
   };
-  if (layer == 13 || layer == 14) {  // these read the selection's outputs: produce them once on this handle's own buffers
+  if (layer == 13 || layer == 14 || layer == 16) {  // these read the selection's outputs: produce them once on this handle's own buffers
     const int keep = layer;
     layer = 12; SSHIP_HIP_CHECK(run());
     layer = 13; SSHIP_HIP_CHECK(run());

@@ -40,9 +40,24 @@ struct TopkArgs {
   int* cell_w;                     // [B, max_kp]
   int* n_out;                      // [B]
   int* n_cand_out;                 // [B] or null
-  int* pix;                        // [B, max_kp] or null: the keypoint's score-map pixel (h << 16 | w), what the bilinear descriptor head samples at
+  int* pix;                        // [B, max_kp] or null: the keypoint's score-map pixel (h << 16 | w), what the bilinear descriptor head samples at and k_kp_refine refines
 };
 void launch_topk(const TopkArgs& a, int B, hipStream_t s);
+// Sub-pixel keypoint refinement (include/sship.h, sship_sp_set_keypoint_refinement): the three-point log-parabola fit per axis on the
+// pre-NMS log-scores of the keypoint's pixel and its four neighbours.  Logit c of cell (cy, cx) of image b is
+// logits[b * img_stride + (cy * Wc + cx) * cell_stride + c * chan_stride]; keypoint i of image b is pix[b * max_kp + i].
+struct KpRefineArgs {
+  const float* logits;
+  size_t img_stride, cell_stride, chan_stride;  // in floats
+  int Hc, Wc;
+  const int* pix;        // [B, max_kp] score-map pixels (h << 16 | w), the packing k_topk writes; clamped into the map
+  const int* n_dev;      // [B] device counts (clamped to [0, max_kp]) or null: n_host keypoints
+  int n_host, max_kp;
+  float* kp_xys;         // [B, max_kp, 3]: x = (w + dx) * scale_x and y = (h + dy) * scale_y overwrite kp[0], kp[1] ...
+  float scale_x, scale_y;
+  float* offsets;        // ... unless this is set: [B, max_kp, 2] = (dx, dy) (the stage form)
+};
+void launch_kp_refine(const KpRefineArgs& a, int B, hipStream_t s);
 void launch_threshold_scan(const float* scores, int H, int W, float thr_f, int border, unsigned long long* cand,
                            int* cand_count, int cap, hipStream_t s);
 void launch_gather_hwc(bool raw, const _Float16* grid, int C, int gh, int gw, size_t img_stride, const int* cell_h,

@@ -534,6 +534,99 @@ void launch_topk(const TopkArgs& a, int B, hipStream_t s) {
   hipLaunchKernelGGL(k_topk, dim3(B), dim3(1024), 0, s, a);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Sub-pixel keypoint refinement (include/sship.h: SSHIP_KP_SUBPIXEL, sship_refine_keypoints*; the reference has no counterpart).
+// Per axis, the three-point log-parabola fit on L = logit - logsumexp(the 65 logits of the pixel's cell), the log of the softmax score
+// k_nms_tile compared.  A 16-lane group owns a keypoint (four per wave): lanes 0-3 hold the centre cell, 4-7 the cell of the x neighbour
+// that leaves it (the centre cell again if none does), 8-15 the same for y; a lane holds 16 of the 64 position logits, as in
+// k_nms_tile, and the quad shares max / sum through two exchanges.  Every lane then forms the log-score of the five taps as if it owned
+// them and the owner's value is fetched with one __shfl per tap.  Addresses are clamped, never branched on; a neighbour outside the map
+// only turns that axis' offset into 0.  No LDS, no atomics; 3 x 272 B per keypoint in the cell-major layout.  The arithmetic of a
+// keypoint does not depend on the batch or on its wave mates: every entry point gives the same bits.
+// VEC: cell-major rows of 16-B aligned floats (chan_stride 1, four float4 per lane); otherwise any two strides (the CHW stage form).
+// ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float kp_refine_fit(float lo, float mid, float hi, bool inside) {
+  const float den = 2.f * mid - lo - hi;
+  const float d = fminf(fmaxf(0.5f * (hi - lo) / den, -0.5f), 0.5f);
+  return (inside && den > 0.f) ? d : 0.f;
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_kp_refine(KpRefineArgs a) {
+  const int b = blockIdx.y, lane = threadIdx.x & 63;
+  const int n = a.n_dev ? min(max(a.n_dev[b], 0), a.max_kp) : a.n_host;
+  const int i0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4;
+  if (i0 >= n) return;  // wave-uniform
+  const int gl = lane & 15, slot = min(gl >> 2, 2), qd = gl & 3;
+  const int i = i0 + (lane >> 4);
+  const int p = a.pix[(size_t)b * a.max_kp + min(i, n - 1)];
+  const int H = a.Hc * 8, W = a.Wc * 8;
+  const int h = min((int)((unsigned)p >> 16), H - 1), w = min(p & 0xffff, W - 1);  // both fields are unsigned 16-bit: never negative
+  const int ch = h >> 3, cw = w >> 3;
+  // the taps: centre, left, right, up, down (clamped into the map; an outside neighbour becomes the centre pixel and is not used)
+  const int th[5] = {h, h, h, max(h - 1, 0), min(h + 1, H - 1)};
+  const int tw[5] = {w, max(w - 1, 0), min(w + 1, W - 1), w, w};
+  // the one other cell an axis can touch: the previous one from the cell's first row / column, else the next one (or none: the centre cell)
+  const int xcw = min(max((((w & 7) == 0) ? w - 1 : w + 1) >> 3, 0), a.Wc - 1);
+  const int ych = min(max((((h & 7) == 0) ? h - 1 : h + 1) >> 3, 0), a.Hc - 1);
+  const int cy = slot == 2 ? ych : ch, cx = slot == 1 ? xcw : cw;
+  const float* lp = a.logits + (size_t)b * a.img_stride + ((size_t)cy * a.Wc + cx) * a.cell_stride;
+  float v[16];
+  if constexpr (VEC) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float4 t = *reinterpret_cast<const float4*>(lp + qd * 16 + j * 4);
+      v[4 * j] = t.x; v[4 * j + 1] = t.y; v[4 * j + 2] = t.z; v[4 * j + 3] = t.w;
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = lp[(size_t)(qd * 16 + j) * a.chan_stride];
+  }
+  const float d = lp[(size_t)64 * a.chan_stride];  // the dustbin: part of the normaliser
+  float m = d;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) m = fmaxf(m, v[j]);
+  m = fmaxf(m, __shfl_xor(m, 1, 64));
+  m = fmaxf(m, __shfl_xor(m, 2, 64));
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) sum += __expf(v[j] - m);
+  sum += __shfl_xor(sum, 1, 64);
+  sum += __shfl_xor(sum, 2, 64);
+  sum += __expf(d - m);
+  const float lg = __logf(sum);
+  float L[5];
+#pragma unroll
+  for (int t = 0; t < 5; ++t) {
+    const int pos = 8 * (th[t] & 7) + (tw[t] & 7);
+    const int owner = (tw[t] >> 3) != cw ? 1 : (th[t] >> 3) != ch ? 2 : 0;
+    float x = v[0];
+#pragma unroll
+    for (int j = 1; j < 16; ++j) x = (pos & 15) == j ? v[j] : x;
+    L[t] = __shfl((x - m) - lg, (lane & 48) + 4 * owner + (pos >> 4), 64);
+  }
+  if (gl != 0 || i >= n) return;
+  const float dx = kp_refine_fit(L[1], L[0], L[2], w > 0 && w < W - 1);
+  const float dy = kp_refine_fit(L[3], L[0], L[4], h > 0 && h < H - 1);
+  if (a.offsets) {
+    float* o = a.offsets + ((size_t)b * a.max_kp + i) * 2;
+    o[0] = dx; o[1] = dy;
+  } else {
+    float* kp = a.kp_xys + ((size_t)b * a.max_kp + i) * 3;
+    kp[0] = ((float)w + dx) * a.scale_x;
+    kp[1] = ((float)h + dy) * a.scale_y;
+  }
+}
+
+void launch_kp_refine(const KpRefineArgs& a, int B, hipStream_t s) {
+  const int nmax = a.n_dev ? a.max_kp : a.n_host;
+  if (nmax <= 0 || B <= 0) return;
+  const dim3 grid((nmax + 15) / 16, B);
+  const bool vec = a.chan_stride == 1 && a.cell_stride % 4 == 0 && a.img_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(a.logits) & 15) == 0;
+  if (vec) hipLaunchKernelGGL(k_kp_refine<true>, grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_kp_refine<false>, grid, dim3(256), 0, s, a);
+}
+
 // Threshold scan of a dense score map (stage API sship_select_topk; SuperPoint.cc:696-702).
 __global__ void k_threshold_scan(const float* __restrict__ scores, int H, int W, float thr_f, int border,
                                  unsigned long long* cand, int* cand_count, int cap) {

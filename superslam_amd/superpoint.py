@@ -58,11 +58,51 @@ def sample_descriptors_bilinear(grid, kp_xy, layout: str = "chw", stream=None):
     return out
 
 
+KEYPOINT_REFINEMENT = {"integer": 0, "subpixel": 1}   # SSHIP_KP_INTEGER / SSHIP_KP_SUBPIXEL (include/sship.h)
+
+
+def _refinement_mode(name) -> int:
+    if name not in KEYPOINT_REFINEMENT:
+        raise ValueError(f"keypoint_refinement must be one of {sorted(KEYPOINT_REFINEMENT)}, not {name!r}")
+    return KEYPOINT_REFINEMENT[name]
+
+
+def refine_keypoints(logits, pix, layout: str = "chw", stream=None):
+    """The sub-pixel offsets of keypoints on given detector logits (include/sship.h: sship_refine_keypoints[_hwc]).
+    logits: torch fp32 CUDA tensor, [65,Hc,Wc] (layout "chw", what dense() returns) or [Hc,Wc,S] with S >= 65 ("hwc"); pix: int32 CUDA
+    tensor [n] of packed score-map pixels (h << 16) | w.  Returns fp32 [n,2] = (dx, dy), each in [-0.5, 0.5]."""
+    import torch
+
+    if layout not in ("chw", "hwc"):
+        raise ValueError("layout must be 'chw' or 'hwc'")
+    if logits.dtype != torch.float32 or logits.dim() != 3 or not logits.is_contiguous():
+        raise ValueError("logits must be a contiguous fp32 tensor of three dimensions")
+    if (logits.shape[0] != 65) if layout == "chw" else (logits.shape[2] < 65):
+        raise ValueError("logits must hold the 65 detector channels of every cell")
+    pix = pix.reshape(-1)
+    if pix.dtype != torch.int32 or not pix.is_contiguous():
+        raise ValueError("pix must be a contiguous int32 tensor [n]")
+    n = pix.shape[0]
+    out = torch.empty((n, 2), dtype=torch.float32, device=logits.device)
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    if layout == "chw":
+        _lib.check(_lib.lib().sship_refine_keypoints(logits.data_ptr(), logits.shape[1], logits.shape[2], pix.data_ptr() if n else None, n,
+                                                     out.data_ptr() if n else None, s))
+    else:
+        _lib.check(_lib.lib().sship_refine_keypoints_hwc(logits.data_ptr(), logits.shape[2], logits.shape[0], logits.shape[1],
+                                                         pix.data_ptr() if n else None, n, out.data_ptr() if n else None, s))
+    return out
+
+
 class SuperPoint:
     descriptor_dim = 256
 
     def __init__(self, engine_file: str, max_keypoints: int, keypoint_threshold: float, remove_borders: int,
-                 nms_radius: int = 4, pool_slots: int = 8, max_batch: int = 2, descriptor_sampling: str = "nearest"):
+                 nms_radius: int = 4, pool_slots: int = 8, max_batch: int = 2, descriptor_sampling: str = "nearest",
+                 keypoint_refinement: str = "integer"):
+        # "integer": the reference's integer score-map pixels (default); "subpixel": the log-parabola peak fit of include/sship.h
+        _refinement_mode(keypoint_refinement)
+        self._keypoint_refinement = keypoint_refinement
         # "nearest": the reference's nearest-cell gather (default); "bilinear": upstream SuperPoint's sample_descriptors
         _sampling_mode(descriptor_sampling)
         self._descriptor_sampling = descriptor_sampling
@@ -87,6 +127,12 @@ class SuperPoint:
             _lib.check(_lib.lib().sship_sp_create(C.byref(cfg), C.byref(h)))
             if self._descriptor_sampling != "nearest":
                 rc = _lib.lib().sship_sp_set_descriptor_sampling(h, _sampling_mode(self._descriptor_sampling))
+                if rc != _lib.OK:
+                    self.last_error = (_lib.lib().sship_last_error() or b"").decode()
+                    _lib.lib().sship_sp_destroy(h)
+                    return False
+            if self._keypoint_refinement != "integer":
+                rc = _lib.lib().sship_sp_set_keypoint_refinement(h, _refinement_mode(self._keypoint_refinement))
                 if rc != _lib.OK:
                     self.last_error = (_lib.lib().sship_last_error() or b"").decode()
                     _lib.lib().sship_sp_destroy(h)
@@ -120,6 +166,19 @@ class SuperPoint:
         if self._h is not None:
             _lib.check(_lib.lib().sship_sp_set_descriptor_sampling(self._h, m))
         self._descriptor_sampling = mode
+
+    @property
+    def keypoint_refinement(self) -> str:
+        return self._keypoint_refinement
+
+    def set_keypoint_refinement(self, mode: str) -> None:
+        """"integer" | "subpixel" for the calls after this one (x and y only: counts, order, scores and descriptors do not change).
+        Before initialize() the mode is kept and applied by it.  Raises ValueError for any other name and SshipError if the library
+        refuses (a ring submission is pending); the mode is then unchanged."""
+        m = _refinement_mode(mode)
+        if self._h is not None:
+            _lib.check(_lib.lib().sship_sp_set_keypoint_refinement(self._h, m))
+        self._keypoint_refinement = mode
 
     @property
     def pool_handle(self):
