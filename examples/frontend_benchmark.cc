@@ -21,10 +21,13 @@
 //             -Lsuperslam_amd/lib -lsuperslam_hip -Wl,-rpath,$PWD/superslam_amd/lib -Wl,-rpath,/opt/rocm/lib -lpthread -lz
 // run:    ./frontend_benchmark --sp sp.safetensors --lg lg.safetensors (--sequence DIR | --synthetic 200) [--keyframe-match]
 //                              [--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--subpixel] [--matcher lightglue|nn]
-//                              [--dump-keypoints FILE]
+//                              [--dump-keypoints FILE] [--stereo-gate MIN,MAX,ROW] [--track-window R]
 //
 // --matcher nn: the mutual nearest-neighbour matcher (superslam_hip::NNMatcher, hloc's NN-mutual) in LightGlue's place - same
 // IFeatureMatcher calls, no --lg needed.  Default: lightglue.
+// --stereo-gate MIN,MAX,ROW (with --matcher nn): the stereo match searches the epipolar band only - MIN <= uL - uR <= MAX and
+// |vL - vR| <= ROW (NNMatcher::set_stereo_gate) - instead of rejecting impossible partners after they have won a row or a column.  The
+// temporal match of --keyframe-match then uses a second NNMatcher without a gate, or with --track-window R one gated (-R, R, -R, R).
 // --bilinear: descriptors by upstream SuperPoint's bilinear sampling (SSHIP_DESC_BILINEAR) instead of the reference's nearest-cell gather.
 // --subpixel: keypoints refined by the log-parabola peak fit (SSHIP_KP_SUBPIXEL) instead of the reference's integer score-map pixels.
 // --dump-keypoints FILE: the first frame's keypoints as int32 n_left, n_right | f32 [n_left][3] (x, y, score) | f32 [n_right][3].
@@ -124,7 +127,8 @@ int main(int argc, char** argv) {
   Source src;
   int max_kp = 600, border = 4;
   double thr = 0.005;
-  bool keyframe = false, use_ring = true, pipeline = true, bilinear = false, subpixel = false;
+  bool keyframe = false, use_ring = true, pipeline = true, bilinear = false, subpixel = false, stereo_gate = false;
+  float gate_min = 0.f, gate_max = 0.f, gate_row = 0.f, track_window = -1.f;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
     auto next = [&]() -> const char* { return i + 1 < argc ? argv[++i] : ""; };
@@ -142,13 +146,19 @@ int main(int argc, char** argv) {
     else if (a == "--subpixel") subpixel = true;
     else if (a == "--dump-keypoints") dump_path = next();
     else if (a == "--matcher") matcher_name = next();
+    else if (a == "--stereo-gate") {
+      stereo_gate = std::sscanf(next(), "%f,%f,%f", &gate_min, &gate_max, &gate_row) == 3;
+      if (!stereo_gate) { std::fprintf(stderr, "--stereo-gate needs MIN,MAX,ROW\n"); return 2; }
+    }
+    else if (a == "--track-window") track_window = (float)std::atof(next());
     else { std::fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
   }
   const bool use_nn = matcher_name == "nn";
-  if (sp_path.empty() || (!use_nn && (lg_path.empty() || matcher_name != "lightglue")) || (src.sequence.empty() && src.synthetic <= 0)) {
+  const bool gated = stereo_gate || track_window >= 0.f;  // the gates belong to the nn matcher
+  if (sp_path.empty() || (!use_nn && (lg_path.empty() || matcher_name != "lightglue" || gated)) || (src.sequence.empty() && src.synthetic <= 0)) {
     std::fprintf(stderr, "usage: %s --sp W.safetensors --lg W.safetensors (--sequence DIR | --synthetic N) [--keyframe-match] "
                          "[--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--subpixel] [--matcher lightglue|nn] "
-                         "[--dump-keypoints FILE]\n", argv[0]);
+                         "[--dump-keypoints FILE] [--stereo-gate MIN,MAX,ROW] [--track-window R] (the gates need --matcher nn)\n", argv[0]);
     return 2;
   }
 
@@ -169,11 +179,17 @@ int main(int argc, char** argv) {
   }
   sh::SuperPoint extractor(sp_path, max_kp, thr, border);
   sh::LightGlue lightglue(lg_path, cols, rows, max_kp);
-  sh::NNMatcher nn(max_kp);
+  sh::NNMatcher nn(max_kp), nn_track(max_kp);  // nn_track: the temporal match of a gated run (its own window, or none)
   sh::IFeatureMatcher& matcher = use_nn ? static_cast<sh::IFeatureMatcher&>(nn) : lightglue;
+  sh::IFeatureMatcher& track_matcher = gated ? static_cast<sh::IFeatureMatcher&>(nn_track) : matcher;
+  if (stereo_gate && !nn.set_stereo_gate(gate_min, gate_max, gate_row)) { std::fprintf(stderr, "--stereo-gate: %s\n", nn.last_error().c_str()); return 2; }
+  if (track_window >= 0.f && !nn_track.set_gate(-track_window, track_window, -track_window, track_window)) {
+    std::fprintf(stderr, "--track-window: %s\n", nn_track.last_error().c_str());
+    return 2;
+  }
   if (bilinear) extractor.set_descriptor_sampling(SSHIP_DESC_BILINEAR);  // kept, applied by initialize()
   if (subpixel) extractor.set_keypoint_refinement(SSHIP_KP_SUBPIXEL);
-  if (!extractor.initialize() || !(use_nn ? nn.initialize() : lightglue.initialize())) {
+  if (!extractor.initialize() || !(use_nn ? nn.initialize() : lightglue.initialize()) || (gated && keyframe && !nn_track.initialize())) {
     std::fprintf(stderr, "initialisation failed: %s\n", sship_last_error());
     return 1;
   }
@@ -248,7 +264,7 @@ int main(int argc, char** argv) {
     }
     stereo_matches += (long)lr.matches.size();
     if (keyframe && !prev_left.descriptors.empty())
-      track_matches += (long)matcher.match(feats.first.keypoints, feats.first.descriptors, prev_left.keypoints, prev_left.descriptors).matches.size();
+      track_matches += (long)track_matcher.match(feats.first.keypoints, feats.first.descriptors, prev_left.keypoints, prev_left.descriptors).matches.size();
     const auto t2 = std::chrono::steady_clock::now();
     ms.push_back((float)std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count() / 1000.0f);
     if (keyframe) prev_left = std::move(feats.first);  // holds its pool slot until the next frame replaces it
@@ -268,6 +284,8 @@ int main(int argc, char** argv) {
               use_ring ? "pinned upload ring" : "copying host API", ts.empty() ? "" : ", times.txt");
   std::printf("frames           : %zu\n", ms.size());
   if (use_nn) std::printf("matcher          : nn (mutual nearest neighbour)\n");
+  if (stereo_gate) std::printf("stereo gate      : %g <= uL - uR <= %g, |vL - vR| <= %g\n", gate_min, gate_max, gate_row);
+  if (track_window >= 0.f) std::printf("track window     : +-%g px\n", track_window);
   if (subpixel) std::printf("keypoints        : sub-pixel (SSHIP_KP_SUBPIXEL)\n");
   if (use_ring) std::printf("pipelined        : %s (%ld of %zu extractions enqueued one frame ahead)\n", pipeline ? "yes" : "no", submitted_ahead, ms.size());
   std::printf("per-frame ms      mean=%.2f p50=%.2f p95=%.2f max=%.2f\n", mean, percentile(ms, 0.50), percentile(ms, 0.95), percentile(ms, 1.0));

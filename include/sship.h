@@ -416,6 +416,45 @@ int sship_nn_match_batch_device(sship_nn* nn, const int* n_dev, const void* desc
 /* Measurement hook: re-run the launches of the last match call on this handle `iters` times (over the same buffers, which the caller of a
  * batch call keeps alive), timed with hipEvents on the handle's stream; *avg_ms = mean duration of one call's launches. */
 int sship_nn_bench(sship_nn* nn, int iters, float* avg_ms);
+/* Keypoint-window gate - per handle, off by default.  The matcher above reads descriptors only: every row of set 0 competes against every
+ * row of set 1.  For rectified stereo (the partner lies in the epipolar band, src/StereoFrontEnd.cc:35-47 rejects the others AFTER matching)
+ * and for frame-to-frame tracking (a square window around the previous position) the search space is restricted BEFORE the best and the
+ * second best are chosen.  Gate g = (dx_lo, dx_hi, dy_lo, dy_hi); keypoints (x, y) in whatever pixel unit the caller uses.  The rule:
+ *   For row i of set 0 and row j of set 1:  dx = x0_i - x1_j and dy = y0_i - y1_j, one fp32 subtraction each;
+ *   in_ij = dx >= dx_lo && dx <= dx_hi && dy >= dy_lo && dy <= dy_hi, exactly this form: a NaN coordinate is in no window.
+ *   An entry with !in_ij is absent, exactly like an index outside n0 x n1.  Everything else is the rule above over the PRESENT entries of
+ *   a row or column: j1 = the smallest present index of the maximum, s2 = the maximum over the other present entries; s2 is absent when
+ *   fewer than two entries are present (the generalisation of n1 == 1: the ratio test passes); a row with no present entry gives fwd_i = -1;
+ *   columns follow the same rule; the mutual check and the scores are unchanged.
+ *   Bounds may be +-INFINITY: the gate (-inf, inf, -inf, inf) with finite coordinates gives the ungated result bit for bit.
+ *   Stereo use: (min_disparity, max_disparity, -row, +row).  A tracking window: (-r, r, -r, r).
+ *   Swapping the sets with the gate (-dx_hi, -dx_lo, -dy_hi, -dy_lo) gives the inverse map under the mutual check.
+ * sship_nn_set_gate: a NaN bound, lo > hi or a NULL handle -> SSHIP_ERR_INVALID (the handle keeps its setting); refused before any device is
+ * touched.  sship_nn_get_gate: any output may be NULL.
+ * The _gated entry points are the three above plus keypoints, and the handle's gate applies: the per-frame calls take HOST keypoints as
+ * (kp, kp_stride) with 2 or 3 floats per keypoint, like sship_lg_match_device; the batch call takes kp_dev [2*pairs, max_kp, 3] f32 (x, y,
+ * score), the layout sship_sp_extract_batch_device writes and sship_lg_match_batch_device reads.  Keypoint rows >= n are never used, whatever
+ * they hold.  With the gate disabled they return the bits of the plain calls, and kp may be NULL.  On a handle whose gate is enabled the
+ * PLAIN entry points return SSHIP_ERR_INVALID (a silent ungated match would be the worst outcome); on a handle without a gate they make
+ * exactly the launches they made before the gate existed.  sship_nn_bench replays the gated launches after a gated call. */
+int sship_nn_set_gate(sship_nn* nn, int enabled, float dx_lo, float dx_hi, float dy_lo, float dy_hi);
+int sship_nn_get_gate(const sship_nn* nn, int* enabled, float* dx_lo, float* dx_hi, float* dy_lo, float* dy_hi);
+int sship_nn_match_gated_device(sship_nn* nn, const float* kp0, int kp0_stride, int n0, const void* desc0_dev, const float* kp1, int kp1_stride,
+                                int n1, const void* desc1_dev, int32_t* matches0, float* mscores0);
+int sship_nn_match_gated_host(sship_nn* nn, const float* kp0, int kp0_stride, int n0, const float* desc0_f32, const float* kp1, int kp1_stride,
+                              int n1, const float* desc1_f32, int32_t* matches0, float* mscores0);
+int sship_nn_match_gated_batch_device(sship_nn* nn, const int* n_dev, const void* desc_dev, const float* kp_dev, int pairs,
+                                      int32_t* matches0_dev, float* mscores0_dev, void* stream);
+/* Stereo association - src/StereoFrontEnd.cc:35-47 as a device stage, on the output of either matcher: turns matches0 into the right
+ * image's u coordinate (the disparity's other half) without going through the host.  kp_dev [2*pairs, max_kp, 3], n_dev [2*pairs]
+ * (clamped to [0, max_keypoints] on the device), matches0_dev [pairs, max_kp].  For pair p and left keypoint i < n0, j = matches0[p, i]:
+ *   has_depth = 0 <= j < n1 && (uL - uR >= min_disparity) && (|vL - vR| <= max_row_diff), in fp32, in this positive form: NaN gives no
+ *   depth - the one stated difference from the reference's `continue` form, which lets NaN through.
+ *   stereo_dev [pairs, max_kp, 3] f32 = (uL, has_depth ? uR : quiet NaN, vL);  has_depth_dev [pairs, max_kp] u8.
+ *   Rows >= n0 are (0, NaN, 0) / 0, and every entry is written.
+ * Asynchronous on `stream`, one launch.  The reference's defaults are min_disparity = 1, max_row_diff = 2. */
+int sship_stereo_associate_batch_device(const float* kp_dev, const int* n_dev, const int32_t* matches0_dev, int pairs, int max_keypoints,
+                                        float min_disparity, float max_row_diff, float* stereo_dev, uint8_t* has_depth_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * EigenPlaces place recogniser - include/EigenPlaces.h:19-40, src/EigenPlaces.cc

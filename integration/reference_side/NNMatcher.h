@@ -1,8 +1,9 @@
 // Reference-side binding (goes into the SuperSLAM tree as include/NNMatcher.h): the mutual nearest-neighbour matcher of
 // libsuperslam_hip as a superslam::IFeatureMatcher ("Pluggable feature matcher", include/InferenceInterfaces.h).  It drops in wherever a
 // LightGlue* is passed today - StereoFrontEnd, LoopCloser - and needs no engine file: hloc's NN-mutual by default, NN-ratio /
-// NN-superpoint through set_params.  Keypoints are accepted and ignored; distance = 1 - cosine, what tests/test_superpoint_cosine_matching.cc
-// of the reference writes.
+// NN-superpoint through set_params.  Without a gate keypoints are accepted and ignored; with set_gate / set_stereo_gate (the epipolar band
+// that src/StereoFrontEnd.cc:35-47 applies after matching, applied before the best and the second best are chosen) they are passed
+// through.  distance = 1 - cosine, what tests/test_superpoint_cosine_matching.cc of the reference writes.
 #ifndef NNMATCHER_HIP_ADAPTER_H_
 #define NNMATCHER_HIP_ADAPTER_H_
 
@@ -30,14 +31,22 @@ public:
     if (!ok) SLOG_ERROR("NNMatcher(HIP): {}", impl_.last_error());
     return ok;
   }
+  // keypoint-window gate: dx_lo <= x0 - x1 <= dx_hi and dy_lo <= y0 - y1 <= dy_hi; false for a NaN bound or lo > hi (setting unchanged)
+  bool set_gate(float dx_lo, float dx_hi, float dy_lo, float dy_hi) { return logged(impl_.set_gate(dx_lo, dx_hi, dy_lo, dy_hi)); }
+  bool set_stereo_gate(float min_disparity, float max_disparity, float max_row_diff = 2.f) {
+    return logged(impl_.set_stereo_gate(min_disparity, max_disparity, max_row_diff));
+  }
+  bool clear_gate() { return logged(impl_.clear_gate()); }
+  bool gate_enabled() const { return impl_.gate_enabled(); }
+  const float* gate() const { return impl_.gate(); }
   float ratio_threshold() const { return impl_.ratio_threshold(); }
   float distance_threshold() const { return impl_.distance_threshold(); }
   bool mutual_check() const { return impl_.mutual_check(); }
 
-  bool match(const std::vector<cv::KeyPoint>&, const cv::Mat& d0, const std::vector<cv::KeyPoint>&, const cv::Mat& d1, MatchResult& result) {
+  bool match(const std::vector<cv::KeyPoint>& kp0, const cv::Mat& d0, const std::vector<cv::KeyPoint>& kp1, const cv::Mat& d1,
+             MatchResult& result) {
     superslam_hip::MatchResult r;
-    const std::vector<superslam_hip::KeyPoint> none;
-    const bool ok = impl_.match(none, from_cv(d0), none, from_cv(d1), r);
+    const bool ok = impl_.match(from_kp(kp0), from_cv(d0), from_kp(kp1), from_cv(d1), r);
     to_cv(r, result);
     return ok;
   }
@@ -47,11 +56,10 @@ public:
     match(kp0, d0, kp1, d1, r);
     return r;
   }
-  MatchResult match(const std::vector<cv::KeyPoint>&, const superslam::DeviceDescriptors& d0, const std::vector<cv::KeyPoint>&,
+  MatchResult match(const std::vector<cv::KeyPoint>& kp0, const superslam::DeviceDescriptors& d0, const std::vector<cv::KeyPoint>& kp1,
                     const superslam::DeviceDescriptors& d1) override {
     MatchResult out;
-    const std::vector<superslam_hip::KeyPoint> none;
-    to_cv(impl_.match(none, from_ref(d0), none, from_ref(d1)), out);
+    to_cv(impl_.match(from_kp(kp0), from_ref(d0), from_kp(kp1), from_ref(d1)), out);
     return out;
   }
   cv::Mat descriptors_to_host(const superslam::DeviceDescriptors& d) override {
@@ -60,6 +68,18 @@ public:
   }
 
 private:
+  bool logged(bool ok) {
+    if (!ok) SLOG_ERROR("NNMatcher(HIP): {}", impl_.last_error());
+    return ok;
+  }
+  // the keypoints are converted only while a gate is set: without one the matcher never reads them
+  std::vector<superslam_hip::KeyPoint> from_kp(const std::vector<cv::KeyPoint>& kp) const {
+    std::vector<superslam_hip::KeyPoint> out;
+    if (!impl_.gate_enabled()) return out;
+    out.resize(kp.size());
+    for (size_t i = 0; i < kp.size(); ++i) { out[i].x = kp[i].pt.x; out[i].y = kp[i].pt.y; }
+    return out;
+  }
   static superslam_hip::HostDescriptors from_cv(const cv::Mat& m) {
     superslam_hip::HostDescriptors h;
     cv::Mat f;

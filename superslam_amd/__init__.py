@@ -5,11 +5,11 @@ imports the CPU oracle; the HIP library is the only compute path.
 """
 from . import _lib  # noqa: F401
 from .eigenplaces import EigenPlaces  # noqa: F401
-from .frontend import FrontEndBatch, process_stereo  # noqa: F401
+from .frontend import FrontEndBatch, process_stereo, stereo_associate_batch  # noqa: F401
 from .lightglue import LightGlue, LightGlueEngine, MatchResult  # noqa: F401
 from .nn_matcher import NNMatcher  # noqa: F401
 from .pool import DescriptorPool, DeviceDescriptors  # noqa: F401
 from .superpoint import Features, SuperPoint  # noqa: F401
 
 __all__ = ["SuperPoint", "LightGlue", "LightGlueEngine", "MatchResult", "Features", "DescriptorPool",
-           "DeviceDescriptors", "FrontEndBatch", "process_stereo", "EigenPlaces", "NNMatcher"]
+           "DeviceDescriptors", "FrontEndBatch", "process_stereo", "stereo_associate_batch", "EigenPlaces", "NNMatcher"]

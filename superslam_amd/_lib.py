@@ -112,6 +112,12 @@ _SIGS = {
     "sship_nn_match_host": (ip, [vp, ip, vp, ip, vp, vp, vp]),
     "sship_nn_match_batch_device": (ip, [vp, vp, vp, ip, vp, vp, vp]),
     "sship_nn_bench": (ip, [vp, ip, C.POINTER(fp)]),
+    "sship_nn_set_gate": (ip, [vp, ip, fp, fp, fp, fp]),
+    "sship_nn_get_gate": (ip, [vp, C.POINTER(ip), C.POINTER(fp), C.POINTER(fp), C.POINTER(fp), C.POINTER(fp)]),
+    "sship_nn_match_gated_device": (ip, [vp, vp, ip, ip, vp, vp, ip, ip, vp, vp, vp]),
+    "sship_nn_match_gated_host": (ip, [vp, vp, ip, ip, vp, vp, ip, ip, vp, vp, vp]),
+    "sship_nn_match_gated_batch_device": (ip, [vp, vp, vp, vp, ip, vp, vp, vp]),
+    "sship_stereo_associate_batch_device": (ip, [vp, vp, vp, ip, ip, fp, fp, vp, vp, vp]),
     "sship_ep_create": (ip, [C.c_char_p, ip, ip, C.POINTER(vp)]),
     "sship_ep_destroy": (None, [vp]),
     "sship_ep_descriptor_dim": (ip, [vp]),

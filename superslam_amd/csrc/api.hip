@@ -2179,12 +2179,16 @@ struct sship_nn {
   int max_kp = 0, max_pairs = 0;
   float ratio = 0.f, dist = 0.f;
   int mutual = 1;
+  // the keypoint-window gate (include/sship.h "Keypoint-window gate"): off by default; (dx_lo, dx_hi, dy_lo, dy_hi)
+  int gate_on = 0;
+  float gate[4] = {-INFINITY, INFINITY, -INFINITY, INFINITY};
   hipStream_t stream = nullptr;
-  DevBuf ws, desc_stage, lens, m0, ms0;
-  PinBuf h_lens, h_m0, h_ms0, h_desc;
+  DevBuf ws, desc_stage, kp_stage, lens, m0, ms0;
+  PinBuf h_lens, h_m0, h_ms0, h_desc, h_kp;
   // the last call's launch arguments (sship_nn_bench re-runs them; the caller keeps a batch call's buffers alive until then)
   const int* last_n = nullptr;
   const _Float16* last_desc = nullptr;
+  const float* last_kp = nullptr;  // non-null: the last call was gated
   int32_t* last_m0 = nullptr;
   float* last_ms0 = nullptr;
   int last_pairs = 0;
@@ -2199,6 +2203,7 @@ extern "C" int sship_nn_create(int max_kp, int max_pairs, sship_nn** out) {
   nn->max_kp = max_kp; nn->max_pairs = max_pairs;
   SSHIP_HIP_CHECK(nn->ws.ensure(nn_workspace_floats(max_kp, max_pairs) * 4));
   SSHIP_HIP_CHECK(nn->desc_stage.ensure(2 * (size_t)max_kp * 256 * 2));
+  SSHIP_HIP_CHECK(nn->kp_stage.ensure(2 * (size_t)max_kp * 3 * 4));
   SSHIP_HIP_CHECK(nn->lens.ensure(2 * 4));
   SSHIP_HIP_CHECK(nn->m0.ensure((size_t)max_kp * 4));
   SSHIP_HIP_CHECK(nn->ms0.ensure((size_t)max_kp * 4));
@@ -2206,7 +2211,9 @@ extern "C" int sship_nn_create(int max_kp, int max_pairs, sship_nn** out) {
   SSHIP_HIP_CHECK(nn->h_m0.ensure((size_t)max_kp * 4));
   SSHIP_HIP_CHECK(nn->h_ms0.ensure((size_t)max_kp * 4));
   SSHIP_HIP_CHECK(nn->h_desc.ensure(2 * (size_t)max_kp * 256 * 2));
+  SSHIP_HIP_CHECK(nn->h_kp.ensure(2 * (size_t)max_kp * 3 * 4));
   SSHIP_HIP_CHECK(hipMemset(nn->desc_stage.p, 0, nn->desc_stage.bytes));
+  SSHIP_HIP_CHECK(hipMemset(nn->kp_stage.p, 0, nn->kp_stage.bytes));
   SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&nn->stream, hipStreamDefault));
   *out = nn.release();
   return SSHIP_OK;
@@ -2232,28 +2239,87 @@ extern "C" int sship_nn_get_params(const sship_nn* nn, float* ratio_threshold, f
   if (mutual_check) *mutual_check = nn->mutual;
   return SSHIP_OK;
 }
-static int nn_launch(sship_nn* nn, const int* n, const _Float16* desc, int pairs, int32_t* m0, float* ms0, hipStream_t s) {
-  launch_nn_match(desc, n, nn->max_kp, pairs, nn->ws.as<float>(), nn->ratio, nn->dist, nn->mutual, m0, ms0, s);
-  SSHIP_HIP_CHECK(hipGetLastError());
-  nn->last_n = n; nn->last_desc = desc; nn->last_m0 = m0; nn->last_ms0 = ms0; nn->last_pairs = pairs;
+extern "C" int sship_nn_set_gate(sship_nn* nn, int enabled, float dx_lo, float dx_hi, float dy_lo, float dy_hi) {
+  if (!nn) return fail(SSHIP_ERR_INVALID, "nn_set_gate: null handle");
+  if (std::isnan(dx_lo) || std::isnan(dx_hi) || std::isnan(dy_lo) || std::isnan(dy_hi)) return fail(SSHIP_ERR_INVALID, "nn_set_gate: a bound is NaN");
+  if (dx_lo > dx_hi || dy_lo > dy_hi) return fail(SSHIP_ERR_INVALID, "nn_set_gate: lo > hi");
+  nn->gate_on = enabled ? 1 : 0;
+  nn->gate[0] = dx_lo; nn->gate[1] = dx_hi; nn->gate[2] = dy_lo; nn->gate[3] = dy_hi;
   return SSHIP_OK;
 }
+extern "C" int sship_nn_get_gate(const sship_nn* nn, int* enabled, float* dx_lo, float* dx_hi, float* dy_lo, float* dy_hi) {
+  if (!nn) return fail(SSHIP_ERR_INVALID, "nn_get_gate: null handle");
+  if (enabled) *enabled = nn->gate_on;
+  if (dx_lo) *dx_lo = nn->gate[0];
+  if (dx_hi) *dx_hi = nn->gate[1];
+  if (dy_lo) *dy_lo = nn->gate[2];
+  if (dy_hi) *dy_hi = nn->gate[3];
+  return SSHIP_OK;
+}
+// kp == nullptr: the plain launches (a handle without a gate); otherwise the gated ones with the handle's window
+static int nn_launch(sship_nn* nn, const int* n, const _Float16* desc, const float* kp, int pairs, int32_t* m0, float* ms0, hipStream_t s) {
+  if (kp) launch_nn_match_gated(desc, kp, n, nn->max_kp, pairs, nn->ws.as<float>(), nn->ratio, nn->dist, nn->mutual, nn->gate, m0, ms0, s);
+  else launch_nn_match(desc, n, nn->max_kp, pairs, nn->ws.as<float>(), nn->ratio, nn->dist, nn->mutual, m0, ms0, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  nn->last_n = n; nn->last_desc = desc; nn->last_kp = kp; nn->last_m0 = m0; nn->last_ms0 = ms0; nn->last_pairs = pairs;
+  return SSHIP_OK;
+}
+static const char kNnGatedMsg[] = ": the handle's gate is enabled - use the _gated entry point (keypoints are needed)";
 extern "C" int sship_nn_match_batch_device(sship_nn* nn, const int* n, const void* desc, int pairs, int32_t* m0, float* ms0, void* stream) {
   if (!nn || !n || !desc || !m0 || !ms0) return fail(SSHIP_ERR_INVALID, "nn_match_batch_device: null argument");
   if (pairs <= 0 || pairs > nn->max_pairs) return fail(SSHIP_ERR_INVALID, "nn_match_batch_device: pairs exceeds max_pairs");
+  if (nn->gate_on) return fail(SSHIP_ERR_INVALID, std::string("nn_match_batch_device") + kNnGatedMsg);
   bind_thread();
   hipStream_t s = static_cast<hipStream_t>(stream);  // NULL = legacy default stream: ordered after an extractor call made with NULL
   g_timer.begin_if_idle(s);
-  if (int rc = nn_launch(nn, n, static_cast<const _Float16*>(desc), pairs, m0, ms0, s)) return rc;
+  if (int rc = nn_launch(nn, n, static_cast<const _Float16*>(desc), nullptr, pairs, m0, ms0, s)) return rc;
   g_timer.mark("nn_match:stream_final", s);
   return SSHIP_OK;
 }
+extern "C" int sship_nn_match_gated_batch_device(sship_nn* nn, const int* n, const void* desc, const float* kp, int pairs, int32_t* m0,
+                                                 float* ms0, void* stream) {
+  if (!nn || !n || !desc || !m0 || !ms0) return fail(SSHIP_ERR_INVALID, "nn_match_gated_batch_device: null argument");
+  if (pairs <= 0 || pairs > nn->max_pairs) return fail(SSHIP_ERR_INVALID, "nn_match_gated_batch_device: pairs exceeds max_pairs");
+  if (nn->gate_on && !kp) return fail(SSHIP_ERR_INVALID, "nn_match_gated_batch_device: the gate is enabled and kp_dev is NULL");
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  if (int rc = nn_launch(nn, n, static_cast<const _Float16*>(desc), nn->gate_on ? kp : nullptr, pairs, m0, ms0, s)) return rc;
+  g_timer.mark(nn->gate_on ? "nn_match_gated:stream_final" : "nn_match:stream_final", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_stereo_associate_batch_device(const float* kp, const int* n, const int32_t* matches0, int pairs, int max_keypoints,
+                                                   float min_disparity, float max_row_diff, float* stereo, uint8_t* has_depth, void* stream) {
+  if (!kp || !n || !matches0 || !stereo || !has_depth) return fail(SSHIP_ERR_INVALID, "stereo_associate_batch_device: null argument");
+  if (pairs <= 0 || max_keypoints <= 0 || max_keypoints > kMaxKp)
+    return fail(SSHIP_ERR_INVALID, "stereo_associate_batch_device: pairs must be positive and max_keypoints in [1, 4096]");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  launch_stereo_associate(kp, n, matches0, max_keypoints, pairs, min_disparity, max_row_diff, stereo, has_depth, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("stereo_associate", s);
+  return SSHIP_OK;
+}
 // one pair out of the handle's own staging buffers (descriptors already enqueued into desc_stage on the handle's stream)
-static int nn_match_common(sship_nn* nn, int n0, int n1, int32_t* matches0, float* mscores0) {
+// gated (kp0 != nullptr): the host keypoints go into kp_stage as [2][max_kp][3] (x, y, 0) first
+static int nn_match_common(sship_nn* nn, int n0, int n1, int32_t* matches0, float* mscores0, const float* kp0 = nullptr, int st0 = 0,
+                           const float* kp1 = nullptr, int st1 = 0) {
   hipStream_t s = nn->stream;
   nn->h_lens.as<int>()[0] = n0; nn->h_lens.as<int>()[1] = n1;
   SSHIP_HIP_CHECK(hipMemcpyAsync(nn->lens.p, nn->h_lens.p, 8, hipMemcpyHostToDevice, s));
-  if (int rc = nn_launch(nn, nn->lens.as<int>(), nn->desc_stage.as<_Float16>(), 1, nn->m0.as<int32_t>(), nn->ms0.as<float>(), s)) return rc;
+  if (kp0) {
+    float* hk = nn->h_kp.as<float>();
+    float* hk1 = hk + (size_t)nn->max_kp * 3;
+    for (int i = 0; i < n0; ++i) { hk[3 * i] = kp0[(size_t)i * st0]; hk[3 * i + 1] = kp0[(size_t)i * st0 + 1]; hk[3 * i + 2] = 0.f; }
+    for (int i = 0; i < n1; ++i) { hk1[3 * i] = kp1[(size_t)i * st1]; hk1[3 * i + 1] = kp1[(size_t)i * st1 + 1]; hk1[3 * i + 2] = 0.f; }
+    SSHIP_HIP_CHECK(hipMemcpyAsync(nn->kp_stage.p, hk, (size_t)n0 * 12, hipMemcpyHostToDevice, s));
+    SSHIP_HIP_CHECK(hipMemcpyAsync(nn->kp_stage.as<float>() + (size_t)nn->max_kp * 3, hk1, (size_t)n1 * 12, hipMemcpyHostToDevice, s));
+  }
+  if (int rc = nn_launch(nn, nn->lens.as<int>(), nn->desc_stage.as<_Float16>(), kp0 ? nn->kp_stage.as<float>() : nullptr, 1,
+                         nn->m0.as<int32_t>(), nn->ms0.as<float>(), s))
+    return rc;
   SSHIP_HIP_CHECK(hipMemcpyAsync(nn->h_m0.p, nn->m0.p, (size_t)n0 * 4, hipMemcpyDeviceToHost, s));
   SSHIP_HIP_CHECK(hipMemcpyAsync(nn->h_ms0.p, nn->ms0.p, (size_t)n0 * 4, hipMemcpyDeviceToHost, s));
   SSHIP_HIP_CHECK(hipStreamSynchronize(s));
@@ -2267,17 +2333,53 @@ static int nn_check_pair(const sship_nn* nn, int n0, const void* d0, int n1, con
   if (n0 > nn->max_kp || n1 > nn->max_kp) return fail(SSHIP_ERR_INVALID, std::string(who) + ": n exceeds max_keypoints");
   return SSHIP_OK;
 }
-extern "C" int sship_nn_match_device(sship_nn* nn, int n0, const void* desc0, int n1, const void* desc1, int32_t* matches0, float* mscores0) {
-  if (int rc = nn_check_pair(nn, n0, desc0, n1, desc1, matches0, mscores0, "nn_match_device")) return rc;
-  bind_thread();
+// the gated calls' keypoint arguments: needed (and checked) only while the gate is enabled
+static int nn_check_kp(const sship_nn* nn, const float* kp0, int st0, const float* kp1, int st1, const char* who) {
+  if (!nn->gate_on) return SSHIP_OK;
+  if (!kp0 || !kp1) return fail(SSHIP_ERR_INVALID, std::string(who) + ": the gate is enabled and a keypoint pointer is NULL");
+  if (st0 < 2 || st1 < 2) return fail(SSHIP_ERR_INVALID, std::string(who) + ": kp_stride must be >= 2");
+  return SSHIP_OK;
+}
+static int nn_stage_device(sship_nn* nn, int n0, const void* desc0, int n1, const void* desc1) {
   hipStream_t s = nn->stream;
   SSHIP_HIP_CHECK(hipMemcpyAsync(nn->desc_stage.p, desc0, (size_t)n0 * 512, hipMemcpyDeviceToDevice, s));
   SSHIP_HIP_CHECK(hipMemcpyAsync(nn->desc_stage.as<_Float16>() + (size_t)nn->max_kp * 256, desc1, (size_t)n1 * 512, hipMemcpyDeviceToDevice, s));
+  return SSHIP_OK;
+}
+static int nn_stage_host(sship_nn* nn, int n0, const float* desc0, int n1, const float* desc1);
+extern "C" int sship_nn_match_device(sship_nn* nn, int n0, const void* desc0, int n1, const void* desc1, int32_t* matches0, float* mscores0) {
+  if (int rc = nn_check_pair(nn, n0, desc0, n1, desc1, matches0, mscores0, "nn_match_device")) return rc;
+  if (nn->gate_on) return fail(SSHIP_ERR_INVALID, std::string("nn_match_device") + kNnGatedMsg);
+  bind_thread();
+  if (int rc = nn_stage_device(nn, n0, desc0, n1, desc1)) return rc;
   return nn_match_common(nn, n0, n1, matches0, mscores0);
+}
+extern "C" int sship_nn_match_gated_device(sship_nn* nn, const float* kp0, int st0, int n0, const void* desc0, const float* kp1, int st1, int n1,
+                                           const void* desc1, int32_t* matches0, float* mscores0) {
+  if (int rc = nn_check_pair(nn, n0, desc0, n1, desc1, matches0, mscores0, "nn_match_gated_device")) return rc;
+  if (int rc = nn_check_kp(nn, kp0, st0, kp1, st1, "nn_match_gated_device")) return rc;
+  bind_thread();
+  if (int rc = nn_stage_device(nn, n0, desc0, n1, desc1)) return rc;
+  if (!nn->gate_on) return nn_match_common(nn, n0, n1, matches0, mscores0);
+  return nn_match_common(nn, n0, n1, matches0, mscores0, kp0, st0, kp1, st1);
+}
+extern "C" int sship_nn_match_gated_host(sship_nn* nn, const float* kp0, int st0, int n0, const float* desc0, const float* kp1, int st1, int n1,
+                                         const float* desc1, int32_t* matches0, float* mscores0) {
+  if (int rc = nn_check_pair(nn, n0, desc0, n1, desc1, matches0, mscores0, "nn_match_gated_host")) return rc;
+  if (int rc = nn_check_kp(nn, kp0, st0, kp1, st1, "nn_match_gated_host")) return rc;
+  bind_thread();
+  if (int rc = nn_stage_host(nn, n0, desc0, n1, desc1)) return rc;
+  if (!nn->gate_on) return nn_match_common(nn, n0, n1, matches0, mscores0);
+  return nn_match_common(nn, n0, n1, matches0, mscores0, kp0, st0, kp1, st1);
 }
 extern "C" int sship_nn_match_host(sship_nn* nn, int n0, const float* desc0, int n1, const float* desc1, int32_t* matches0, float* mscores0) {
   if (int rc = nn_check_pair(nn, n0, desc0, n1, desc1, matches0, mscores0, "nn_match_host")) return rc;
+  if (nn->gate_on) return fail(SSHIP_ERR_INVALID, std::string("nn_match_host") + kNnGatedMsg);
   bind_thread();
+  if (int rc = nn_stage_host(nn, n0, desc0, n1, desc1)) return rc;
+  return nn_match_common(nn, n0, n1, matches0, mscores0);
+}
+static int nn_stage_host(sship_nn* nn, int n0, const float* desc0, int n1, const float* desc1) {
   hipStream_t s = nn->stream;
   _Float16* hd = nn->h_desc.as<_Float16>();  // CV_32F -> fp16 on the host, as sship_lg_match_host
   for (size_t i = 0; i < (size_t)n0 * 256; ++i) hd[i] = (_Float16)desc0[i];
@@ -2285,7 +2387,7 @@ extern "C" int sship_nn_match_host(sship_nn* nn, int n0, const float* desc0, int
   SSHIP_HIP_CHECK(hipMemcpyAsync(nn->desc_stage.p, hd, (size_t)n0 * 512, hipMemcpyHostToDevice, s));
   SSHIP_HIP_CHECK(hipMemcpyAsync(nn->desc_stage.as<_Float16>() + (size_t)nn->max_kp * 256, hd + (size_t)nn->max_kp * 256, (size_t)n1 * 512,
                                  hipMemcpyHostToDevice, s));
-  return nn_match_common(nn, n0, n1, matches0, mscores0);
+  return SSHIP_OK;
 }
 // Measurement hook (include/sship.h): the last call's two launches re-run `iters` times on the handle's stream.
 extern "C" int sship_nn_bench(sship_nn* nn, int iters, float* avg_ms) {
@@ -2294,9 +2396,13 @@ extern "C" int sship_nn_bench(sship_nn* nn, int iters, float* avg_ms) {
   bind_thread();
   hipStream_t s = nn->stream;
   SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
-  auto run = [&]() -> hipError_t {
-    launch_nn_match(nn->last_desc, nn->last_n, nn->max_kp, nn->last_pairs, nn->ws.as<float>(), nn->ratio, nn->dist, nn->mutual, nn->last_m0,
-                    nn->last_ms0, s);
+  auto run = [&]() -> hipError_t {  // the gated launches after a gated call
+    if (nn->last_kp)
+      launch_nn_match_gated(nn->last_desc, nn->last_kp, nn->last_n, nn->max_kp, nn->last_pairs, nn->ws.as<float>(), nn->ratio, nn->dist,
+                            nn->mutual, nn->gate, nn->last_m0, nn->last_ms0, s);
+    else
+      launch_nn_match(nn->last_desc, nn->last_n, nn->max_kp, nn->last_pairs, nn->ws.as<float>(), nn->ratio, nn->dist, nn->mutual, nn->last_m0,
+                      nn->last_ms0, s);
     return hipGetLastError();
   };
   SSHIP_HIP_CHECK(run());  // warm

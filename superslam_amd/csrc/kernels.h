@@ -217,5 +217,11 @@ void launch_lg_assign(const _Float16* md, const float* logsig, const int* lens, 
 size_t nn_workspace_floats(int max_kp, int max_pairs);
 void launch_nn_match(const _Float16* desc, const int* lens, int max_kp, int pairs, float* ws, float ratio, float dist, int mutual,
                      int32_t* matches0, float* mscores0, hipStream_t s);
+// the same with the keypoint-window gate: kp [2 pairs][max_kp][3] fp32 (x, y, score), gate = (dx_lo, dx_hi, dy_lo, dy_hi); same workspace
+void launch_nn_match_gated(const _Float16* desc, const float* kp, const int* lens, int max_kp, int pairs, float* ws, float ratio, float dist,
+                           int mutual, const float gate[4], int32_t* matches0, float* mscores0, hipStream_t s);
+// StereoFrontEnd::process's association on the device: stereo [pairs][max_kp][3] = (uL, uR or NaN, vL), has_depth [pairs][max_kp] u8
+void launch_stereo_associate(const float* kp, const int* lens, const int32_t* matches0, int max_kp, int pairs, float min_disparity,
+                             float max_row_diff, float* stereo, uint8_t* has_depth, hipStream_t s);
 
 }  // namespace sship

@@ -37,6 +37,27 @@ def process_stereo(extractor, matcher, left: np.ndarray, right: np.ndarray, min_
     return StereoObservation(L.keypoints, u_right, has_depth), L, R, m
 
 
+def stereo_associate_batch(kp, n, matches0, min_disparity: float = 1.0, max_row_diff: float = 2.0, stereo=None, has_depth=None, stream=None):
+    """process_stereo's association as a device stage (sship_stereo_associate_batch_device), on the output of either matcher:
+    kp f32 [2P, K, 3], n i32 [2P], matches0 i32 [P, K] (torch CUDA) -> stereo f32 [P, K, 3] = (uL, uR or NaN, vL), has_depth u8 [P, K].
+    has_depth = 0 <= j < n1 and uL - uR >= min_disparity and |vL - vR| <= max_row_diff.  Asynchronous on `stream` (default: torch's current)."""
+    import torch
+
+    pairs, k = matches0.shape
+    if tuple(kp.shape) != (2 * pairs, k, 3) or kp.dtype != torch.float32 or matches0.dtype != torch.int32 or n.dtype != torch.int32:
+        raise ValueError(f"kp must be float32 [{2 * pairs}, {k}, 3], n int32 [{2 * pairs}], matches0 int32 [{pairs}, {k}]")
+    if n.numel() != 2 * pairs or not (kp.is_contiguous() and matches0.is_contiguous() and n.is_contiguous()):
+        raise ValueError("n must have 2 * pairs entries and the tensors must be contiguous")
+    if stereo is None:
+        stereo = torch.empty((pairs, k, 3), dtype=torch.float32, device=kp.device)
+    if has_depth is None:
+        has_depth = torch.empty((pairs, k), dtype=torch.uint8, device=kp.device)
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    _lib.check(_lib.lib().sship_stereo_associate_batch_device(kp.data_ptr(), n.data_ptr(), matches0.data_ptr(), pairs, k, float(min_disparity),
+                                                              float(max_row_diff), stereo.data_ptr(), has_depth.data_ptr(), s))
+    return stereo, has_depth
+
+
 class FrontEndBatch:
     """Device-resident throughput step: SuperPoint on 2P images + LightGlue on P pairs, no host sync."""
 
