@@ -362,12 +362,16 @@ int sship_lg_prune_counts(sship_lg* lg, int pair, int32_t* prune0, int n0, int32
 enum { SSHIP_LG_DEBUG_X = 0, SSHIP_LG_DEBUG_SIM = 1, SSHIP_LG_DEBUG_KPTS = 2, SSHIP_LG_DEBUG_ROPE = 3, SSHIP_LG_DEBUG_IND = 4 };
 int sship_lg_debug_set_layers(sship_lg* lg, int n_layers);
 int sship_lg_debug_read(sship_lg* lg, int what, int index, int rows, int cols, float* out);
-/* Test-only: copy one encoder activation of the extractor's LAST call to the host as raw fp16 (channels-last [batch][h_l][w_l][c_l]),
- * device-synchronising.  layer: 1 conv1b (+pool), 2 conv2a, 3 conv2b (+pool), 4 conv3a, 5 conv3b (+pool), 6 conv4a, 7 conv4b (the ids of
- * sship_sp_bench_layer).  Used by the parity suite to compare single layers (e.g. the Winograd variant of conv2a / conv2b) with a CPU
- * convolution of the previous layer's activation; the product never calls it.  `bytes` must not exceed the activation's size.
- * Layer 2 (conv2a) is NOT materialised by the shipped library: conv2a -> conv2b -> pool run as one kernel whose intermediate map never leaves the CU
- * (csrc/conv_fuse2.hip); its buffer holds the last two-launch run's map (developer build, SUPERSLAM_HIP_CONV2=split / SUPERSLAM_HIP_CONV64=wino) or nothing. */
+/* Test-only: copy one activation of the extractor's LAST call to the host, raw (channels-last [batch][h_l][w_l][c_l]), device-synchronising.
+ * layer: 1 conv1b (+pool), 2 conv2a, 3 conv2b (+pool), 4 conv3a, 5 conv3b (+pool), 6 conv4a, 7 conv4b (the ids of sship_sp_bench_layer), all fp16;
+ * and the heads: 8 convPa, fp16 [B,Hc,Wc,256]; 9 convDa, the same layout, filled only by sship_sp_dense called with a descriptor grid;
+ * 10 convDb's raw output before normalisation, fp16 [B,Hc,Wc,256], sship_sp_dense with a grid only; 11 convPb's logits, fp32 [B,Hc,Wc,68]:
+ * 65 meaningful values at the head of every 68-float row.
+ * Used by the parity suite to compare single layers with an fp64 convolution of the previous layer's activation (tests/test_gpu_sp_layers.py);
+ * the product never calls it.  `bytes` must not exceed the activation's size.
+ * Layer 2 (conv2a) is materialised only where conv2a and conv2b run as two launches: in the shipped library when the fused kernel
+ * (csrc/conv_fuse2.hip, whose intermediate map never leaves the CU) does not fit - maps under 8 pixels, an 8x8 image for one - and in the developer
+ * build under SUPERSLAM_HIP_CONV2=split / SUPERSLAM_HIP_CONV64=wino.  After a fused run its buffer holds an earlier run's map or nothing. */
 int sship_sp_debug_activation(sship_sp* sp, int layer, void* out_host, unsigned long long bytes);
 /* Match post-processing, src/LightGlue.cc:326-363: ascending i, skip -1, distance = 1 - score.
  * Returns the number of matches (>= 0). */

@@ -723,7 +723,8 @@ static hipError_t conv3(const ConvW& w, const _Float16* in, _Float16* out, int B
 // conv2a + conv2b + pool run as ONE launch (conv_fuse2.hip) at every batch size - the strips are cut into as many row segments as it takes to give
 // every CU work, so a one-pair call gains as well (0.736 -> 0.710 ms) - unless the shape does not fit the kernel (maps under 8 pixels, images beyond
 // 32-bit offsets): then, and in the developer build under SUPERSLAM_HIP_CONV2=split (A/B; tests/test_gpu_alt_paths.py), the two conv3x3_pp launches run.
-// Both paths give the same bits.  (sship_sp_debug_activation layer 2 = conv2a's map exists only on the two-launch path.)
+// Both paths give the same bits.  (sship_sp_debug_activation layer 2 = conv2a's map exists only on the two-launch path, which the shipped
+// library does take where the fused kernel does not fit: an 8x8 image, for one.)
 static bool conv2_fused(int B, int H2, int W2) {
 #if SSHIP_DEV_SWITCHES
   static const std::string mode = [] { const char* e = dev_env("SUPERSLAM_HIP_CONV2"); return std::string(e ? e : ""); }();
@@ -970,8 +971,9 @@ extern "C" void sship_sp_destroy(sship_sp* sp) {
 extern "C" int sship_sp_debug_activation(sship_sp* sp, int layer, void* out_host, unsigned long long bytes) {
   bind_thread();
   if (!sp || !out_host) return fail(SSHIP_ERR_INVALID, "sp_debug_activation: null argument");
-  DevBuf* bufs[8] = {nullptr, &sp->a1b, &sp->a2a, &sp->a2b, &sp->a3a, &sp->a3b, &sp->a4a, &sp->a4b};
-  if (layer < 1 || layer > 7 || !bufs[layer]->p || bytes > bufs[layer]->bytes) return fail(SSHIP_ERR_INVALID, "sp_debug_activation: bad layer / size");
+  // 8 convPa, 9 convDa, 10 convDb (raw) and 11 convPb's logits (fp32, kLogitStride floats a cell): the head activations
+  DevBuf* bufs[12] = {nullptr, &sp->a1b, &sp->a2a, &sp->a2b, &sp->a3a, &sp->a3b, &sp->a4a, &sp->a4b, &sp->aPa, &sp->aDa, &sp->draw, &sp->logits};
+  if (layer < 1 || layer > 11 || !bufs[layer]->p || bytes > bufs[layer]->bytes) return fail(SSHIP_ERR_INVALID, "sp_debug_activation: bad layer / size");
   SSHIP_HIP_CHECK(hipDeviceSynchronize());
   SSHIP_HIP_CHECK(hipMemcpy(out_host, bufs[layer]->p, bytes, hipMemcpyDeviceToHost));
   return SSHIP_OK;
