@@ -495,6 +495,63 @@ int sship_ep_bench(sship_ep* ep, const uint8_t* img_dev, int h, int w, int strid
 int sship_ep_preprocess(const uint8_t* img, int h, int w, int stride, int channels, int input_w, int input_h, float* chw_out);
 
 /* ------------------------------------------------------------------------------------------------
+ * Place-recognition index - the reference's CosineDescriptorIndex (include/PlaceRecognizer.h, src/PlaceRecognizer.cc:21-52: add,
+ * exclude-recent window, score gate, top-k) with the database resident on the device, so that the descriptor sship_ep_infer_u8_device
+ * leaves in device memory is stored and searched without a host copy; and, with many queries per call, hloc's "pairs from retrieval"
+ * over a whole sequence.  Any global descriptor: dim is a multiple of 4 in [4, 4096] (EigenPlaces: 512).  The rule:
+ *   Stored row (normalizedRow, PlaceRecognizer.cc:10-18): n = sqrt(sum_k x_k x_k) accumulated in fp64; row_k = (float)((double)x_k / n) if
+ *     n > 1e-12, else the row is stored unchanged - a NaN norm fails that comparison, so such a row stays as given.  Queries are
+ *     normalised by the same rule inside the query call.
+ *   Score: s_i = sum_k row_i[k] q[k], fp32 operands, fp32 accumulation; the database is never narrowed to fp16 / bf16.  A score's bits depend
+ *     only on the row, the query and dim - not on the index size, the number of queries in the call, the query's position in the batch or
+ *     the device's CU count: one query gives the same bits alone (_query_host / _query_device) and inside any batch.
+ *   Candidates of query j: rows i < limit_j with s_i >= min_score, exactly this form: a NaN score is never a candidate, also with
+ *     min_score = -INFINITY.  limit_j = size - exclude_recent (exclude_recent >= size: no candidates), or limits_dev[j] clamped to
+ *     [0, size] when limits_dev is given (exclude_recent is then not used) - what a batch of consecutive keyframes or an all-against-all
+ *     run needs.  Insertion order is recency.
+ *   Order: descending score, ties by ascending row (the stable sort of oracle/eigenplaces_ref.py; the reference's std::sort leaves ties
+ *     unspecified).  Output: the first min(top_k, #candidates) entries and that number as the count.  In the batch outputs entries at and
+ *     beyond the count are -1 / 0.0f, and every entry is written.
+ *   Stated difference from the reference: topK <= 0 means "all" there; here top_k must be in 1..max_top_k.
+ * Handle: sship_index_create(dim, capacity, max_queries 1..1024, max_top_k 1..128); capacity >= 1 and capacity * dim * 4 <= 2 GiB.  All
+ * storage and workspaces are allocated once at create: the fp32 database [capacity, dim], the normalised queries, and
+ * ceil(capacity / 256) * max_queries * max_top_k 8-byte partial keys (one list per 256-row chunk and query).
+ * Bad arguments are refused with SSHIP_ERR_INVALID before any device is touched, the handle unchanged: a bad create argument, a NULL
+ * handle or pointer, count < 1, a stride below dim, an add beyond capacity, num_queries outside 1..max_queries, top_k outside
+ * 1..max_top_k, exclude_recent < 0, a NaN min_score.  Valid create arguments without a GPU give SSHIP_ERR_NO_DEVICE.
+ * State and ordering: keyframe ids (int64) and the size are HOST state, updated when an add is enqueued; device work is stream-ordered.
+ * A handle is not thread-safe, and its calls must be ordered on one stream or by events (as for sship_ep_infer_u8_device): _add_device and
+ * _query_batch_device run on `stream` (NULL = the legacy default stream); _add_host, _query_host and _query_device run on the handle's
+ * own blocking stream and return after synchronising it; _read synchronises the device.  Device outputs of the batch call are ROW indices
+ * (insertion positions); the per-query calls map them to ids.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sship_index sship_index;
+int sship_index_create(int dim, int capacity, int max_queries, int max_top_k, sship_index** out);
+void sship_index_destroy(sship_index* index);
+int sship_index_dim(const sship_index* index);        /* NULL -> 0 */
+int sship_index_capacity(const sship_index* index);   /* NULL -> 0 */
+int sship_index_size(const sship_index* index);       /* NULL -> 0 */
+int sship_index_clear(sship_index* index);            /* size = 0; the storage is kept */
+/* Append `count` rows (row r at desc + r * row_stride floats, row_stride >= dim, no alignment needed) with their ids (host). */
+int sship_index_add_host(sship_index* index, const int64_t* ids, const float* desc_f32, int count, int row_stride);
+int sship_index_add_device(sship_index* index, const int64_t* ids, const float* desc_dev, int count, int row_stride, void* stream);
+/* Stored rows [first_row, first_row + count) as they are on the device, and their ids; either output may be NULL. */
+int sship_index_read(sship_index* index, int first_row, int count, float* rows_out, int64_t* ids_out);
+/* One query, results on the host: ids_out / scores_out [top_k], *count_out entries are valid. */
+int sship_index_query_host(sship_index* index, const float* desc_f32, int exclude_recent, int top_k, float min_score, int64_t* ids_out,
+                           float* scores_out, int* count_out);
+int sship_index_query_device(sship_index* index, const float* desc_dev, int exclude_recent, int top_k, float min_score, int64_t* ids_out,
+                             float* scores_out, int* count_out);
+/* num_queries queries (row j at q_dev + j * q_stride floats), everything device-resident and asynchronous on `stream`:
+ * rows_dev i32 [num_queries, top_k], scores_dev f32 [num_queries, top_k], counts_dev i32 [num_queries].  limits_dev i32 [num_queries] or NULL. */
+int sship_index_query_batch_device(sship_index* index, const float* q_dev, int num_queries, int q_stride, const int32_t* limits_dev,
+                                   int exclude_recent, int top_k, float min_score, int32_t* rows_dev, float* scores_dev, int32_t* counts_dev,
+                                   void* stream);
+/* Measurement hook: re-run the launches of the last query call on this handle `iters` times (over the same buffers and the size of that
+ * call, which the caller of a batch call keeps alive), timed with hipEvents on the handle's stream; *avg_ms = mean duration of one call. */
+int sship_index_bench(sship_index* index, int iters, float* avg_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused front-end step: what StereoFrontEnd::process asks of the two interfaces per frame
  * (src/StereoFrontEnd.cc:14,33): SuperPoint on L and R (one batch) + gather x2 + one LightGlue match,
  * for `pairs` stereo pairs at once, device-resident, no host synchronisation.  imgs_dev is

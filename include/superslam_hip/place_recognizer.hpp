@@ -5,7 +5,8 @@
 // The retrieval side - superslam::CosineDescriptorIndex, TemporalConsistencyVoter, IPlaceRecognizer::add / query (include/PlaceRecognizer.h,
 // src/PlaceRecognizer.cc) - is GPU-free control plane that stays the reference's own code in libsuperslam_core: the reference-side
 // adapter (integration/reference_side/EigenPlaces.h) holds a superslam::CosineDescriptorIndex exactly as include/EigenPlaces.h:30-36,62 does.
-// Nothing of it is restated in this product (a restatement for the tests lives in oracle/eigenplaces_ref.py).
+// The opt-in device-resident form of the index is superslam_hip::DescriptorIndex (place_index.hpp, sship_index_*); the voter is not restated
+// in this product (a restatement for the tests lives in oracle/eigenplaces_ref.py).
 #pragma once
 #include <algorithm>
 #include <cmath>

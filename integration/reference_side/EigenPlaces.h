@@ -3,6 +3,8 @@
 // LoopCloser compile and run unchanged against superslam::IPlaceRecognizer.  The descriptor is computed by libsuperslam_hip.so
 // (include/superslam_hip/place_recognizer.hpp -> include/sship.h, sship_ep_*); retrieval stays the reference's own
 // superslam::CosineDescriptorIndex (src/PlaceRecognizer.cc in libsuperslam_core), held and used exactly as include/EigenPlaces.h:30-36,53,62.
+// Opt-in: set_device_index(true, capacity) moves retrieval to the device-resident index of the library
+// (include/superslam_hip/place_index.hpp -> sship_index_*: the same rule, ties by insertion order, topK <= 0 refused); off by default.
 #ifndef EIGENPLACES_HIP_ADAPTER_H_
 #define EIGENPLACES_HIP_ADAPTER_H_
 
@@ -15,6 +17,7 @@
 #include "Logging.h"
 #include "SshipLogForward.h"   // library log callback -> SLOG_* (include/Logging.h:21-26)
 #include "PlaceRecognizer.h"  // the reference's own header (unchanged): superslam::IPlaceRecognizer, LoopCandidate
+#include "superslam_hip/place_index.hpp"
 #include "superslam_hip/place_recognizer.hpp"
 
 class EigenPlaces : public superslam::IPlaceRecognizer {
@@ -38,14 +41,37 @@ public:
     for (size_t i = 0; i < d.size(); ++i) out.ptr<float>(0)[i] = d[i];
     return out;
   }
-  void add(size_t keyframe_id, const cv::Mat& global_descriptor) override { index_.add(keyframe_id, global_descriptor); }
+  // Retrieval on the device (default off).  Switch before the first add: the two indices do not share their content, and a switch
+  // starts from an empty device index of `capacity` rows.
+  void set_device_index(bool on, int capacity = 16384) {
+    device_index_.reset(on ? new superslam_hip::DescriptorIndex(capacity) : nullptr);
+  }
+  bool device_index() const { return device_index_ != nullptr; }
+  void add(size_t keyframe_id, const cv::Mat& global_descriptor) override {
+    if (!device_index_) { index_.add(keyframe_id, global_descriptor); return; }
+    const cv::Mat row = float_row(global_descriptor);
+    if (!device_index_->add(keyframe_id, row.ptr<float>(0), row.cols)) SLOG_ERROR("EigenPlaces(HIP) index: {}", device_index_->last_error());
+  }
   std::vector<superslam::LoopCandidate> query(const cv::Mat& global_descriptor, size_t excludeRecent, int topK) override {
-    return index_.query(global_descriptor, excludeRecent, topK, min_score_);
+    if (!device_index_) return index_.query(global_descriptor, excludeRecent, topK, min_score_);
+    std::vector<superslam::LoopCandidate> out;
+    if (device_index_->size() == 0) return out;
+    const cv::Mat row = float_row(global_descriptor);
+    const auto found = device_index_->query(row.ptr<float>(0), row.cols, excludeRecent, topK, min_score_);
+    if (found.empty() && !device_index_->last_error().empty()) SLOG_ERROR("EigenPlaces(HIP) index: {}", device_index_->last_error());
+    for (const auto& c : found) { superslam::LoopCandidate lc; lc.keyframe_id = c.keyframe_id; lc.score = c.score; out.push_back(lc); }
+    return out;
   }
 
 private:
+  static cv::Mat float_row(const cv::Mat& desc) {  // normalizedRow's first half (src/PlaceRecognizer.cc:10-13): 1 x D, CV_32F
+    cv::Mat row = desc.reshape(1, 1);
+    if (row.type() != CV_32F) row.convertTo(row, CV_32F);
+    return row;
+  }
   superslam_hip::EigenPlaces impl_;
   float min_score_ = 0.75f;                  // include/EigenPlaces.h:53
   superslam::CosineDescriptorIndex index_;   // include/EigenPlaces.h:62
+  std::unique_ptr<superslam_hip::DescriptorIndex> device_index_;   // set_device_index(true): retrieval on the device instead
 };
 #endif

@@ -126,6 +126,19 @@ _SIGS = {
     "sship_ep_infer_u8": (ip, [vp, vp, ip, ip, ip, ip, vp]),
     "sship_ep_infer_u8_device": (ip, [vp, vp, ip, ip, ip, ip, vp, vp]),
     "sship_ep_bench": (ip, [vp, vp, ip, ip, ip, ip, ip, C.POINTER(C.c_float)]),
+    "sship_index_create": (ip, [ip, ip, ip, ip, C.POINTER(vp)]),
+    "sship_index_destroy": (None, [vp]),
+    "sship_index_dim": (ip, [vp]),
+    "sship_index_capacity": (ip, [vp]),
+    "sship_index_size": (ip, [vp]),
+    "sship_index_clear": (ip, [vp]),
+    "sship_index_add_host": (ip, [vp, vp, vp, ip, ip]),
+    "sship_index_add_device": (ip, [vp, vp, vp, ip, ip, vp]),
+    "sship_index_read": (ip, [vp, ip, ip, vp, vp]),
+    "sship_index_query_host": (ip, [vp, vp, ip, ip, fp, vp, vp, C.POINTER(ip)]),
+    "sship_index_query_device": (ip, [vp, vp, ip, ip, fp, vp, vp, C.POINTER(ip)]),
+    "sship_index_query_batch_device": (ip, [vp, vp, ip, ip, vp, ip, ip, fp, vp, vp, vp, vp]),
+    "sship_index_bench": (ip, [vp, ip, C.POINTER(fp)]),
     "sship_desc_to_host": (ip, [vp, ip, ip, vp]),
     "sship_frontend_batch_device": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_bench_layer": (ip, [vp, ip, ip, ip, ip, ip, C.POINTER(fp), C.POINTER(C.c_double)]),

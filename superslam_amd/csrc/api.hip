@@ -2674,6 +2674,212 @@ extern "C" int sship_ep_bench(sship_ep* ep, const uint8_t* img_dev, int h, int w
 }
 
 // ====================================================================================================
+// Place-recognition index (include/sship.h "Place-recognition index"; csrc/index_kernels.hip)
+// ====================================================================================================
+constexpr long long kIndexMaxBytes = 1ll << 31;  // capacity * dim * 4 (the header states it)
+struct sship_index {
+  int dim = 0, capacity = 0, max_queries = 0, max_top_k = 0;
+  int size = 0;                 // host state, updated when an add is enqueued
+  std::vector<int64_t> ids;     // [size] keyframe ids
+  hipStream_t stream = nullptr;
+  DevBuf db, qn, partial;       // [capacity][dim] stored rows; [ceil16(max_queries)][dim] normalised queries; chunk partials
+  DevBuf q1, rows1, scores1, count1;   // the per-query calls: one staged query and its results
+  PinBuf h_q, h_rows, h_scores, h_count;
+  // the last query call's arguments (sship_index_bench re-runs its launches; the caller keeps a batch call's buffers alive until then)
+  struct Last { const float* q = nullptr; long long q_stride = 0; int nq = 0; const int* limits = nullptr; int limit_all = 0, top_k = 0, size = 0;
+                float min_score = 0.f; int* rows = nullptr; float* scores = nullptr; int* counts = nullptr; } last;
+};
+extern "C" int sship_index_create(int dim, int capacity, int max_queries, int max_top_k, sship_index** out) {
+  if (!out) return fail(SSHIP_ERR_INVALID, "index_create: null argument");
+  *out = nullptr;
+  if (dim < 4 || dim > 4096 || dim % 4) return fail(SSHIP_ERR_INVALID, "index_create: dim must be a multiple of 4 in [4, 4096]");
+  if (capacity < 1 || (long long)capacity * dim * 4 > kIndexMaxBytes) return fail(SSHIP_ERR_INVALID, "index_create: capacity must be >= 1 and capacity * dim * 4 <= 2 GiB");
+  if (max_queries < 1 || max_queries > 1024) return fail(SSHIP_ERR_INVALID, "index_create: max_queries must be in [1, 1024]");
+  if (max_top_k < 1 || max_top_k > kIndexMaxTopK) return fail(SSHIP_ERR_INVALID, "index_create: max_top_k must be in [1, 128]");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  std::unique_ptr<sship_index, void (*)(sship_index*)> ix(new sship_index(), sship_index_destroy);
+  ix->dim = dim; ix->capacity = capacity; ix->max_queries = max_queries; ix->max_top_k = max_top_k;
+  ix->ids.reserve(capacity);
+  const size_t chunks = ((size_t)capacity + kIndexRows - 1) / kIndexRows;
+  const size_t qpad = ((size_t)max_queries + kIndexTile - 1) / kIndexTile * kIndexTile;
+  SSHIP_HIP_CHECK(ix->db.ensure((size_t)capacity * dim * 4));
+  SSHIP_HIP_CHECK(ix->qn.ensure(qpad * dim * 4));
+  SSHIP_HIP_CHECK(ix->partial.ensure(chunks * max_queries * max_top_k * 8));
+  SSHIP_HIP_CHECK(ix->q1.ensure((size_t)dim * 4));
+  SSHIP_HIP_CHECK(ix->rows1.ensure((size_t)max_top_k * 4));
+  SSHIP_HIP_CHECK(ix->scores1.ensure((size_t)max_top_k * 4));
+  SSHIP_HIP_CHECK(ix->count1.ensure(4));
+  SSHIP_HIP_CHECK(ix->h_q.ensure((size_t)dim * 4));
+  SSHIP_HIP_CHECK(ix->h_rows.ensure((size_t)max_top_k * 4));
+  SSHIP_HIP_CHECK(ix->h_scores.ensure((size_t)max_top_k * 4));
+  SSHIP_HIP_CHECK(ix->h_count.ensure(4));
+  SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&ix->stream, hipStreamDefault));
+  *out = ix.release();
+  return SSHIP_OK;
+}
+extern "C" void sship_index_destroy(sship_index* ix) {
+  if (!ix) return;
+  bind_thread();
+  (void)hipDeviceSynchronize();
+  if (ix->stream) (void)hipStreamDestroy(ix->stream);
+  delete ix;
+}
+extern "C" int sship_index_dim(const sship_index* ix) { return ix ? ix->dim : 0; }
+extern "C" int sship_index_capacity(const sship_index* ix) { return ix ? ix->capacity : 0; }
+extern "C" int sship_index_size(const sship_index* ix) { return ix ? ix->size : 0; }
+extern "C" int sship_index_clear(sship_index* ix) {
+  if (!ix) return fail(SSHIP_ERR_INVALID, "index_clear: null handle");
+  ix->size = 0; ix->ids.clear(); ix->last = sship_index::Last();
+  return SSHIP_OK;
+}
+static int index_check_add(const sship_index* ix, const int64_t* ids, const float* desc, int count, int row_stride, const char* who) {
+  if (!ix || !ids || !desc) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  if (count < 1) return fail(SSHIP_ERR_INVALID, std::string(who) + ": count must be >= 1");
+  if (row_stride < ix->dim) return fail(SSHIP_ERR_INVALID, std::string(who) + ": row_stride must be >= dim");
+  if (count > ix->capacity - ix->size) return fail(SSHIP_ERR_INVALID, std::string(who) + ": the index is full (size + count exceeds capacity)");
+  return SSHIP_OK;
+}
+static void index_commit_add(sship_index* ix, const int64_t* ids, int count) {
+  ix->ids.insert(ix->ids.end(), ids, ids + count);
+  ix->size += count;
+}
+extern "C" int sship_index_add_device(sship_index* ix, const int64_t* ids, const float* desc_dev, int count, int row_stride, void* stream) {
+  if (int rc = index_check_add(ix, ids, desc_dev, count, row_stride, "index_add_device")) return rc;
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_index_normalize(desc_dev, row_stride, count, count, ix->dim, ix->db.as<float>() + (size_t)ix->size * ix->dim, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  index_commit_add(ix, ids, count);
+  return SSHIP_OK;
+}
+// the raw rows go straight to their place in the database and are normalised there
+extern "C" int sship_index_add_host(sship_index* ix, const int64_t* ids, const float* desc, int count, int row_stride) {
+  if (int rc = index_check_add(ix, ids, desc, count, row_stride, "index_add_host")) return rc;
+  bind_thread();
+  hipStream_t s = ix->stream;
+  float* dst = ix->db.as<float>() + (size_t)ix->size * ix->dim;
+  SSHIP_HIP_CHECK(hipMemcpy2DAsync(dst, (size_t)ix->dim * 4, desc, (size_t)row_stride * 4, (size_t)ix->dim * 4, count, hipMemcpyHostToDevice, s));
+  launch_index_normalize(dst, ix->dim, count, count, ix->dim, dst, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  SSHIP_HIP_CHECK(hipStreamSynchronize(s));
+  index_commit_add(ix, ids, count);
+  return SSHIP_OK;
+}
+extern "C" int sship_index_read(sship_index* ix, int first_row, int count, float* rows_out, int64_t* ids_out) {
+  if (!ix) return fail(SSHIP_ERR_INVALID, "index_read: null handle");
+  if (first_row < 0 || count < 0 || first_row > ix->size || count > ix->size - first_row)
+    return fail(SSHIP_ERR_INVALID, "index_read: [first_row, first_row + count) must lie inside [0, size)");
+  if (count == 0) return SSHIP_OK;
+  if (ids_out) memcpy(ids_out, ix->ids.data() + first_row, (size_t)count * sizeof(int64_t));
+  if (rows_out) {
+    bind_thread();
+    SSHIP_HIP_CHECK(hipDeviceSynchronize());  // an add may have been enqueued on the caller's stream
+    SSHIP_HIP_CHECK(hipMemcpy(rows_out, ix->db.as<float>() + (size_t)first_row * ix->dim, (size_t)count * ix->dim * 4, hipMemcpyDeviceToHost));
+  }
+  return SSHIP_OK;
+}
+static int index_check_query(const sship_index* ix, int exclude_recent, int top_k, float min_score, const char* who) {
+  if (exclude_recent < 0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": exclude_recent must be >= 0");
+  if (top_k < 1 || top_k > ix->max_top_k) return fail(SSHIP_ERR_INVALID, std::string(who) + ": top_k must be in [1, max_top_k] (there is no 'all')");
+  if (std::isnan(min_score)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": min_score is NaN");
+  return SSHIP_OK;
+}
+static int index_launch(sship_index* ix, const float* q, long long q_stride, int nq, const int* limits, int exclude_recent, int top_k, float min_score,
+                        int* rows, float* scores, int* counts, hipStream_t s) {
+  sship_index::Last& l = ix->last;
+  l.q = q; l.q_stride = q_stride; l.nq = nq; l.limits = limits; l.top_k = top_k; l.min_score = min_score; l.size = ix->size;
+  l.limit_all = exclude_recent >= ix->size ? 0 : ix->size - exclude_recent;
+  l.rows = rows; l.scores = scores; l.counts = counts;
+  launch_index_query(ix->db.as<float>(), ix->dim, l.size, q, q_stride, nq, limits, l.limit_all, top_k, min_score, ix->qn.as<float>(),
+                     ix->partial.as<unsigned long long>(), rows, scores, counts, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  return SSHIP_OK;
+}
+extern "C" int sship_index_query_batch_device(sship_index* ix, const float* q_dev, int num_queries, int q_stride, const int32_t* limits_dev,
+                                              int exclude_recent, int top_k, float min_score, int32_t* rows_dev, float* scores_dev,
+                                              int32_t* counts_dev, void* stream) {
+  if (!ix || !q_dev || !rows_dev || !scores_dev || !counts_dev) return fail(SSHIP_ERR_INVALID, "index_query_batch_device: null argument");
+  if (num_queries < 1 || num_queries > ix->max_queries) return fail(SSHIP_ERR_INVALID, "index_query_batch_device: num_queries must be in [1, max_queries]");
+  if (q_stride < ix->dim) return fail(SSHIP_ERR_INVALID, "index_query_batch_device: q_stride must be >= dim");
+  if (int rc = index_check_query(ix, exclude_recent, top_k, min_score, "index_query_batch_device")) return rc;
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  if (int rc = index_launch(ix, q_dev, q_stride, num_queries, limits_dev, exclude_recent, top_k, min_score, rows_dev, scores_dev, counts_dev, s)) return rc;
+  g_timer.mark("index_query:stream_final", s);
+  return SSHIP_OK;
+}
+// one query, already enqueued into q1 on the handle's stream: the batch launches with Q = 1, results mapped to ids on the host
+static int index_query_one(sship_index* ix, int exclude_recent, int top_k, float min_score, int64_t* ids_out, float* scores_out, int* count_out) {
+  hipStream_t s = ix->stream;
+  if (int rc = index_launch(ix, ix->q1.as<float>(), ix->dim, 1, nullptr, exclude_recent, top_k, min_score, ix->rows1.as<int>(), ix->scores1.as<float>(),
+                            ix->count1.as<int>(), s))
+    return rc;
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ix->h_rows.p, ix->rows1.p, (size_t)top_k * 4, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ix->h_scores.p, ix->scores1.p, (size_t)top_k * 4, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ix->h_count.p, ix->count1.p, 4, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipStreamSynchronize(s));
+  const int n = ix->h_count.as<int>()[0];
+  if (n < 0 || n > top_k) return fail(SSHIP_ERR_HIP, "index_query: the device returned an impossible count");
+  for (int i = 0; i < n; ++i) {
+    const int row = ix->h_rows.as<int>()[i];
+    if (row < 0 || row >= ix->size) return fail(SSHIP_ERR_HIP, "index_query: the device returned a row outside the index");
+    ids_out[i] = ix->ids[row];
+    scores_out[i] = ix->h_scores.as<float>()[i];
+  }
+  *count_out = n;
+  return SSHIP_OK;
+}
+static int index_check_one(const sship_index* ix, const float* desc, int exclude_recent, int top_k, float min_score, const int64_t* ids_out,
+                           const float* scores_out, const int* count_out, const char* who) {
+  if (!ix || !desc || !ids_out || !scores_out || !count_out) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  return index_check_query(ix, exclude_recent, top_k, min_score, who);
+}
+extern "C" int sship_index_query_host(sship_index* ix, const float* desc, int exclude_recent, int top_k, float min_score, int64_t* ids_out,
+                                      float* scores_out, int* count_out) {
+  if (int rc = index_check_one(ix, desc, exclude_recent, top_k, min_score, ids_out, scores_out, count_out, "index_query_host")) return rc;
+  bind_thread();
+  memcpy(ix->h_q.p, desc, (size_t)ix->dim * 4);
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ix->q1.p, ix->h_q.p, (size_t)ix->dim * 4, hipMemcpyHostToDevice, ix->stream));
+  return index_query_one(ix, exclude_recent, top_k, min_score, ids_out, scores_out, count_out);
+}
+extern "C" int sship_index_query_device(sship_index* ix, const float* desc_dev, int exclude_recent, int top_k, float min_score, int64_t* ids_out,
+                                        float* scores_out, int* count_out) {
+  if (int rc = index_check_one(ix, desc_dev, exclude_recent, top_k, min_score, ids_out, scores_out, count_out, "index_query_device")) return rc;
+  bind_thread();
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ix->q1.p, desc_dev, (size_t)ix->dim * 4, hipMemcpyDeviceToDevice, ix->stream));
+  return index_query_one(ix, exclude_recent, top_k, min_score, ids_out, scores_out, count_out);
+}
+// Measurement hook (include/sship.h): the last query call's launches (normalise, scan, merge) re-run `iters` times on the handle's stream.
+extern "C" int sship_index_bench(sship_index* ix, int iters, float* avg_ms) {
+  if (!ix || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "index_bench: bad arguments");
+  if (ix->last.nq <= 0) return fail(SSHIP_ERR_INVALID, "index_bench: run a query on this handle first");
+  bind_thread();
+  hipStream_t s = ix->stream;
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
+  const sship_index::Last& l = ix->last;
+  auto run = [&]() -> hipError_t {
+    launch_index_query(ix->db.as<float>(), ix->dim, l.size, l.q, l.q_stride, l.nq, l.limits, l.limit_all, l.top_k, l.min_score, ix->qn.as<float>(),
+                       ix->partial.as<unsigned long long>(), l.rows, l.scores, l.counts, s);
+    return hipGetLastError();
+  };
+  SSHIP_HIP_CHECK(run());  // warm
+  hipEvent_t e0, e1;
+  SSHIP_HIP_CHECK(hipEventCreate(&e0));
+  SSHIP_HIP_CHECK(hipEventCreate(&e1));
+  SSHIP_HIP_CHECK(hipEventRecord(e0, s));
+  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
+  SSHIP_HIP_CHECK(hipEventRecord(e1, s));
+  SSHIP_HIP_CHECK(hipEventSynchronize(e1));
+  float ms = 0.f;
+  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  *avg_ms = ms / iters;
+  return SSHIP_OK;
+}
+
+// ====================================================================================================
 // fused front-end step: SuperPoint(batch 2P) + select + gather + LightGlue(P)
 // ====================================================================================================
 extern "C" int sship_frontend_batch_device(sship_sp* sp, sship_lg* lg, const uint8_t* imgs, int pairs, int h, int w,

@@ -224,4 +224,17 @@ void launch_nn_match_gated(const _Float16* desc, const float* kp, const int* len
 void launch_stereo_associate(const float* kp, const int* lens, const int32_t* matches0, int max_kp, int pairs, float min_disparity,
                              float max_row_diff, float* stereo, uint8_t* has_depth, hipStream_t s);
 
+// ---- index_kernels.hip : place-recognition index (sship_index_*) ----
+constexpr int kIndexRows = 256;     // database rows per scan workgroup (one chunk of partials)
+constexpr int kIndexTile = 16;      // queries per scan workgroup (the MFMA's N)
+constexpr int kIndexMaxTopK = 128;
+// the stored-row rule: dst [rows_total][dim] (16-byte aligned) = normalised src rows (`stride` floats apart, any alignment); rows >= count
+// are zeroed.  src == dst with stride == dim normalises in place.
+void launch_index_normalize(const float* src, long long stride, int count, int rows_total, int dim, float* dst, hipStream_t s);
+// one query call = normalise + scan + merge.  db [size][dim] stored rows; q: num_queries rows q_stride floats apart; limits: device [Q] or
+// null (then limit_all for every query); qn: [ceil16(Q)][dim] floats; partial: ceil(size / kIndexRows) * Q * top_k keys;
+// rows / scores [Q][top_k] and counts [Q] are written completely.
+void launch_index_query(const float* db, int dim, int size, const float* q, long long q_stride, int num_queries, const int* limits, int limit_all,
+                        int top_k, float min_score, float* qn, unsigned long long* partial, int* rows, float* scores, int* counts, hipStream_t s);
+
 }  // namespace sship

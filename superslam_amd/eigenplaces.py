@@ -3,7 +3,8 @@
   EigenPlaces(engine_file, input_width, input_height); initialize() -> bool;
   compute_global_descriptor(image) -> float32 [512] (empty array when not initialised).
 Retrieval (superslam::CosineDescriptorIndex / TemporalConsistencyVoter, src/PlaceRecognizer.cc) is the reference's own GPU-free control
-plane and is not restated in this package (the tests' restatement: oracle/eigenplaces_ref.py).  NOTE for users of rounds <= 4: `add` / `query`
+plane; its opt-in device-resident form is superslam_amd.PlaceIndex (place_index.py), which takes infer_u8_device's tensor as it is (the tests'
+restatement of the host form: oracle/eigenplaces_ref.py).  NOTE for users of rounds <= 4: `add` / `query`
 of IPlaceRecognizer (include/EigenPlaces.h:30-36) were removed from this class on purpose in round 5 - in a SuperSLAM build the adapter
 integration/reference_side/EigenPlaces.h implements them with the reference's own index.
 `engine_file` is the safetensors state dict utils/convert_eigenplaces_to_onnx.py:99 saves (the .engine's replacement).
@@ -85,3 +86,23 @@ class EigenPlaces:
             return np.zeros(0, np.float32)
         n = float(np.linalg.norm(d))
         return d / np.float32(n) if n > 0 else d     # cv::normalize(desc, desc, 1.0, 0.0, NORM_L2)
+
+    def infer_u8_device(self, image_dev, out=None, stream=None):
+        """sship_ep_infer_u8_device: a uint8 torch CUDA image ([H, W] gray or [H, W, 3] BGR, contiguous) -> the 512-d descriptor as a float32
+        CUDA tensor, asynchronous on `stream` (default: torch's current stream); nothing crosses to the host.  This is the network's output as
+        sship_ep_infer_u8 returns it; what consumes it (PlaceIndex.add / query) normalises by its own rule.  Raises on failure."""
+        import torch
+
+        if self._h is None:
+            raise _lib.SshipError(_lib.ERR_INVALID, "EigenPlaces.infer_u8_device: not initialised")
+        if image_dev.dtype != torch.uint8 or not image_dev.is_cuda or not image_dev.is_contiguous():
+            raise TypeError("EigenPlaces.infer_u8_device: expected a contiguous uint8 CUDA tensor")
+        if not (image_dev.dim() == 2 or (image_dev.dim() == 3 and image_dev.shape[2] in (1, 3))):
+            raise ValueError(f"EigenPlaces: expected [H, W] gray or [H, W, 3] BGR, got shape {tuple(image_dev.shape)}")
+        h, w = int(image_dev.shape[0]), int(image_dev.shape[1])
+        ch = 1 if image_dev.dim() == 2 else int(image_dev.shape[2])
+        if out is None:
+            out = torch.empty(512, dtype=torch.float32, device=image_dev.device)
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        _lib.check(_lib.lib().sship_ep_infer_u8_device(self._h, image_dev.data_ptr(), h, w, w * ch, ch, out.data_ptr(), s))
+        return out
