@@ -552,6 +552,88 @@ int sship_index_query_batch_device(sship_index* index, const float* q_dev, int n
 int sship_index_bench(sship_index* index, int iters, float* avg_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * Pose-only stereo solver - what both consumers of the front-end's output do with it: src/VoEstimator.cc:249-270 (FrameTracker::track on
+ * PointObs {Xw, meas}) and src/LoopCloser.cc:55-89 (the same solve from identity, then an inlier count).  One 6x6 system per pair, `pairs`
+ * pairs per call, device-resident, no GTSAM.  The objective is FrameTracker's (PoseOnlyStereoFactor under a Huber-robust diagonal noise,
+ * include/PoseOptimizationFactors.h); the Levenberg-Marquardt schedule is this library's own and is stated here - the rule is NOT
+ * "whatever GTSAM does".  Inputs are fp32 and are widened on load; all arithmetic is fp64.  The rule:
+ *   Camera (fx, fy, cx, cy, baseline), no skew.  Pose Twc = [R | t], row-major 3x4, 12 doubles (superslam_hip::Pose3x4).
+ *   Observation k = (X, (uL, uR, v), valid).  It is PRESENT iff its valid byte is non-zero and all six floats are finite; an absent
+ *     observation contributes nothing, whatever it holds.
+ *   q = R^T (X - t).  projection = (fx q.x / q.z + cx, fx (q.x - baseline) / q.z + cx, fy q.y / q.z + cy);  r = projection - (uL, uR, v).
+ *   Whitened r~ = (r0 / sigma_px, r1 / sigma_uR, r2 / sigma_px) with sigma_uR = sigma_d0 sqrt(1 + (d_cond / d)^2), d = max(uL - uR, 1e-3)
+ *     of the measurement, d_cond = fx baseline / cond_depth (stereo_diag_noise).
+ *   Behind the camera, !(q.z > 0) in exactly this form: r = (2 fx, 2 fx, 2 fx) and the Jacobian is zero (the reference's cheirality branch).
+ *   Huber on e = |r~| with k^2 = huber_k2: rho = e^2 / 2 for e <= k, k e - k^2 / 2 above;  IRLS weight w = min(1, k / e).
+ *   Jacobian J~ = d r~ / d xi for the right perturbation T Exp(xi), xi = (omega, v), rotation first: dq/d omega = [q]x, dq/dv = -I.
+ *   H = sum w J~^T J~,  g = sum w J~^T r~,  c = sum rho  over the present observations.
+ *   Schedule:  (c, H, g) at T0, lambda = lambda0.  Repeat: if trials == max_iterations stop with ITER_CAP.  Solve (H + lambda I) delta = -g
+ *     by Cholesky; a pivot that is not > 0 is a rejected trial (counted, nothing evaluated).  T' = T Exp(delta), the full SE(3) exponential
+ *     (R' = R Exp(omega), t' = t + R V(omega) v; no re-orthonormalisation); (c', H', g') at T' in one pass; one trial.  Then, in this order:
+ *     c' finite and |c - c'| <= max(abs_tol, rel_tol c): take T', CONVERGED, stop;  else c' < c: accept, lambda /= 10;  else reject,
+ *     lambda *= 10, and lambda > lambda_max stops with STALLED at T.
+ *   Fewer than 3 present observations: TOO_FEW.  A non-finite initial pose: BAD_INPUT.  In both the pose out is the pose in, and
+ *     n_inliers, trials and both costs are 0.
+ *   n_inliers (LoopCloser.cc:74-86): the present observations with q.z > 0 and hypot(r0, r2) < inlier_px at the final pose.
+ *   Defaults (the reference's): sigma_px 10, sigma_d0 8, cond_depth 40, huber_k2 7.815, inlier_px 3 (LoopParams); the schedule's own:
+ *     lambda0 1e-5, lambda_max 1e5, abs_tol = rel_tol = 1e-5, max_iterations 100.
+ *   Sums run in one fixed order (per thread over its observations k = tid, tid + 256, ..., then lanes, then waves): a pair gives the same
+ *     bits alone, inside any batch and at any batch position.
+ * Handle: sship_pose_create(max_obs 1..2048, max_pairs 1..65535).  The camera must be set before a solve or a gather.
+ * Bad arguments are refused with SSHIP_ERR_INVALID and a message before any device is touched, the handle unchanged: a NULL handle or
+ * pointer, max_obs / max_pairs / pairs / n_obs out of range, fx, fy or baseline not > 0 (or any camera value not finite), a NaN in the
+ * params, a sigma, cond_depth, huber_k2 or lambda0 not > 0, lambda_max < lambda0, a negative tolerance or inlier_px, max_iterations < 1.
+ * Valid create arguments without a GPU give SSHIP_ERR_NO_DEVICE.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sship_pose sship_pose;
+typedef struct sship_pose_params {
+  double sigma_px, sigma_d0, cond_depth, huber_k2;
+  double lambda0, lambda_max, abs_tol, rel_tol;
+  double inlier_px;
+  int max_iterations;
+} sship_pose_params;
+#define SSHIP_POSE_CONVERGED 0
+#define SSHIP_POSE_ITER_CAP 1
+#define SSHIP_POSE_STALLED 2
+#define SSHIP_POSE_TOO_FEW 3
+#define SSHIP_POSE_BAD_INPUT 4
+int sship_pose_create(int max_obs, int max_pairs, sship_pose** out);
+void sship_pose_destroy(sship_pose* ps);
+int sship_pose_set_camera(sship_pose* ps, double fx, double fy, double cx, double cy, double baseline);
+int sship_pose_get_camera(const sship_pose* ps, double* fx, double* fy, double* cx, double* cy, double* baseline); /* any output may be NULL */
+int sship_pose_set_params(sship_pose* ps, const sship_pose_params* params);
+int sship_pose_get_params(const sship_pose* ps, sship_pose_params* params);
+/* Throughput path, one launch, asynchronous on `stream` (NULL = the legacy default stream), no host synchronisation inside:
+ * points_dev [pairs, max_obs, 3] f32 (X in the frame the pose maps into), meas_dev [pairs, max_obs, 3] f32 (uL, uR, v),
+ * valid_dev [pairs, max_obs] u8, pose0_dev [pairs, 12] f64 or NULL = identity;  pose_dev [pairs, 12] f64, stats_dev [pairs, 4] i32 =
+ * (n_obs, n_inliers, trials, status), cost_dev [pairs, 2] f64 = (initial, final), inlier_dev [pairs, max_obs] u8 or NULL.  Every entry
+ * of the outputs is written. */
+int sship_pose_solve_batch_device(sship_pose* ps, const float* points_dev, const float* meas_dev, const uint8_t* valid_dev,
+                                  const double* pose0_dev, int pairs, double* pose_dev, int32_t* stats_dev, double* cost_dev,
+                                  uint8_t* inlier_dev, void* stream);
+/* One pair from host arrays - the drop-in for one FrameTracker::track call: points / meas [n_obs, 3], valid [n_obs] or NULL = all,
+ * pose0 [12] or NULL = identity; pose_out [12], stats_out [4], cost_out [2], inlier_out [n_obs] or NULL.  n_obs in 0..max_obs.
+ * Synchronous on the handle's own stream; the same launch as the batch call with pairs = 1, hence the same bits. */
+int sship_pose_solve_host(sship_pose* ps, const float* points, const float* meas, const uint8_t* valid, int n_obs, const double* pose0,
+                          double* pose_out, int32_t* stats_out, double* cost_out, uint8_t* inlier_out);
+/* The observation list from what the front-end leaves on the device (LoopCloser.cc:55-70), one launch, asynchronous on `stream`:
+ * stereo0_dev / has_depth0_dev [pairs, max_obs, 3] / [pairs, max_obs] of the keyframe and stereo1_dev / has_depth1_dev of the frame (the
+ * outputs of sship_stereo_associate_batch_device), matches0_dev [pairs, max_obs] from keyframe-left to frame-left keypoints, and the two
+ * left-image counts of pair p at n0_dev[p * n_stride] and n1_dev[p * n_stride] (n_stride = 2 reads them out of an extractor's [2 * pairs]
+ * array), clamped to [0, max_obs] on the device.  For keyframe keypoint i < n0 with j = matches0[p, i]:
+ *   valid = 0 <= j < n1 && has_depth0[p, i] && has_depth1[p, j];
+ *   X = backproject_cam(stereo0[p, i]) (LoopCloser.cc:19-24) in the keyframe's camera frame, in fp64 from the fp32 values and rounded
+ *   once to fp32: Z = fx baseline / (uL - uR), X = (uL - cx) Z / fx, Y = (v - cy) Z / fy;   meas = stereo1[p, j].
+ *   An invalid row, and every row >= n0, is (0, 0, 0) / (0, 0, 0) / 0.  Every entry is written. */
+int sship_pose_obs_from_matches_batch_device(const sship_pose* ps, const float* stereo0_dev, const uint8_t* has_depth0_dev,
+                                             const float* stereo1_dev, const uint8_t* has_depth1_dev, const int32_t* matches0_dev,
+                                             const int* n0_dev, const int* n1_dev, int n_stride, int pairs, float* points_dev,
+                                             float* meas_dev, uint8_t* valid_dev, void* stream);
+/* Measurement hook: re-run the last solve call's launch on this handle `iters` times (over the same buffers, which the caller of a batch
+ * call keeps alive), timed with hipEvents on the handle's stream; *avg_ms = mean duration of one launch. */
+int sship_pose_bench(sship_pose* ps, int iters, float* avg_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused front-end step: what StereoFrontEnd::process asks of the two interfaces per frame
  * (src/StereoFrontEnd.cc:14,33): SuperPoint on L and R (one batch) + gather x2 + one LightGlue match,
  * for `pairs` stereo pairs at once, device-resident, no host synchronisation.  imgs_dev is

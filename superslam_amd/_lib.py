@@ -46,8 +46,14 @@ class Features(C.Structure):
     _fields_ = [("kp_xys", C.POINTER(C.c_float)), ("n", C.c_int), ("desc_dev", C.c_void_p), ("slot", C.c_int)]
 
 
+class PoseParams(C.Structure):
+    _fields_ = [("sigma_px", C.c_double), ("sigma_d0", C.c_double), ("cond_depth", C.c_double), ("huber_k2", C.c_double),
+                ("lambda0", C.c_double), ("lambda_max", C.c_double), ("abs_tol", C.c_double), ("rel_tol", C.c_double),
+                ("inlier_px", C.c_double), ("max_iterations", C.c_int)]
+
+
 _lib = None
-vp, ip, fp = C.c_void_p, C.c_int, C.c_float
+vp, ip, fp, dp = C.c_void_p, C.c_int, C.c_float, C.c_double
 _SIGS = {
     "sship_init": (ip, [ip]),
     "sship_version": (ip, []),
@@ -139,6 +145,16 @@ _SIGS = {
     "sship_index_query_device": (ip, [vp, vp, ip, ip, fp, vp, vp, C.POINTER(ip)]),
     "sship_index_query_batch_device": (ip, [vp, vp, ip, ip, vp, ip, ip, fp, vp, vp, vp, vp]),
     "sship_index_bench": (ip, [vp, ip, C.POINTER(fp)]),
+    "sship_pose_create": (ip, [ip, ip, C.POINTER(vp)]),
+    "sship_pose_destroy": (None, [vp]),
+    "sship_pose_set_camera": (ip, [vp, dp, dp, dp, dp, dp]),
+    "sship_pose_get_camera": (ip, [vp, C.POINTER(dp), C.POINTER(dp), C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]),
+    "sship_pose_set_params": (ip, [vp, C.POINTER(PoseParams)]),
+    "sship_pose_get_params": (ip, [vp, C.POINTER(PoseParams)]),
+    "sship_pose_solve_batch_device": (ip, [vp, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp]),
+    "sship_pose_solve_host": (ip, [vp, vp, vp, vp, ip, vp, vp, vp, vp, vp]),
+    "sship_pose_obs_from_matches_batch_device": (ip, [vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, vp, vp, vp, vp]),
+    "sship_pose_bench": (ip, [vp, ip, C.POINTER(fp)]),
     "sship_desc_to_host": (ip, [vp, ip, ip, vp]),
     "sship_frontend_batch_device": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_bench_layer": (ip, [vp, ip, ip, ip, ip, ip, C.POINTER(fp), C.POINTER(C.c_double)]),

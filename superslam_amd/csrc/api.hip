@@ -2880,6 +2880,202 @@ extern "C" int sship_index_bench(sship_index* ix, int iters, float* avg_ms) {
 }
 
 // ====================================================================================================
+// Pose-only stereo solver (include/sship.h "Pose-only stereo solver"; csrc/pose_kernels.hip)
+// ====================================================================================================
+constexpr int kPoseMaxPairs = 65535;
+struct sship_pose {
+  int max_obs = 0, max_pairs = 0;
+  bool has_camera = false;
+  double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;
+  sship_pose_params prm{10.0, 8.0, 40.0, 7.815, 1e-5, 1e5, 1e-5, 1e-5, 3.0, 100};
+  hipStream_t stream = nullptr;
+  DevBuf points1, meas1, valid1, pose01, pose1, stats1, cost1, inlier1;   // sship_pose_solve_host: one staged pair and its results
+  PinBuf h_in, h_out;
+  // the last solve call's arguments (sship_pose_bench re-runs its launch; the caller keeps a batch call's buffers alive until then)
+  struct Last { const float* points = nullptr; const float* meas = nullptr; const uint8_t* valid = nullptr; const double* pose0 = nullptr; int pairs = 0;
+                double* pose = nullptr; int32_t* stats = nullptr; double* cost = nullptr; uint8_t* inlier = nullptr; } last;
+};
+static PoseK pose_constants(const sship_pose* ps) {
+  PoseK k;
+  k.fx = ps->fx; k.fy = ps->fy; k.cx = ps->cx; k.cy = ps->cy; k.baseline = ps->baseline;
+  k.inv_sigma_px = 1.0 / ps->prm.sigma_px; k.sigma_d0 = ps->prm.sigma_d0; k.d_cond = ps->fx * ps->baseline / ps->prm.cond_depth;
+  k.k = std::sqrt(ps->prm.huber_k2); k.k2 = ps->prm.huber_k2;
+  k.lambda0 = ps->prm.lambda0; k.lambda_max = ps->prm.lambda_max; k.abs_tol = ps->prm.abs_tol; k.rel_tol = ps->prm.rel_tol;
+  k.inlier_px = ps->prm.inlier_px; k.max_iterations = ps->prm.max_iterations;
+  return k;
+}
+extern "C" int sship_pose_create(int max_obs, int max_pairs, sship_pose** out) {
+  if (!out) return fail(SSHIP_ERR_INVALID, "pose_create: null argument");
+  *out = nullptr;
+  if (max_obs < 1 || max_obs > kPoseMaxObs) return fail(SSHIP_ERR_INVALID, "pose_create: max_obs must be in [1, 2048]");
+  if (max_pairs < 1 || max_pairs > kPoseMaxPairs) return fail(SSHIP_ERR_INVALID, "pose_create: max_pairs must be in [1, 65535]");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  std::unique_ptr<sship_pose, void (*)(sship_pose*)> ps(new sship_pose(), sship_pose_destroy);
+  ps->max_obs = max_obs; ps->max_pairs = max_pairs;
+  const size_t n = (size_t)max_obs;
+  SSHIP_HIP_CHECK(ps->points1.ensure(n * 12));
+  SSHIP_HIP_CHECK(ps->meas1.ensure(n * 12));
+  SSHIP_HIP_CHECK(ps->valid1.ensure(n));
+  SSHIP_HIP_CHECK(ps->inlier1.ensure(n));
+  SSHIP_HIP_CHECK(ps->pose01.ensure(96));
+  SSHIP_HIP_CHECK(ps->pose1.ensure(96));
+  SSHIP_HIP_CHECK(ps->stats1.ensure(16));
+  SSHIP_HIP_CHECK(ps->cost1.ensure(16));
+  SSHIP_HIP_CHECK(ps->h_in.ensure(n * 25 + 96));
+  SSHIP_HIP_CHECK(ps->h_out.ensure(128 + n));
+  SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&ps->stream, hipStreamDefault));
+  *out = ps.release();
+  return SSHIP_OK;
+}
+extern "C" void sship_pose_destroy(sship_pose* ps) {
+  if (!ps) return;
+  bind_thread();
+  (void)hipDeviceSynchronize();
+  if (ps->stream) (void)hipStreamDestroy(ps->stream);
+  delete ps;
+}
+extern "C" int sship_pose_set_camera(sship_pose* ps, double fx, double fy, double cx, double cy, double baseline) {
+  if (!ps) return fail(SSHIP_ERR_INVALID, "pose_set_camera: null handle");
+  if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(baseline))
+    return fail(SSHIP_ERR_INVALID, "pose_set_camera: every camera value must be finite");
+  if (!(fx > 0.0) || !(fy > 0.0) || !(baseline > 0.0)) return fail(SSHIP_ERR_INVALID, "pose_set_camera: fx, fy and baseline must be > 0");
+  ps->fx = fx; ps->fy = fy; ps->cx = cx; ps->cy = cy; ps->baseline = baseline; ps->has_camera = true;
+  return SSHIP_OK;
+}
+extern "C" int sship_pose_get_camera(const sship_pose* ps, double* fx, double* fy, double* cx, double* cy, double* baseline) {
+  if (!ps) return fail(SSHIP_ERR_INVALID, "pose_get_camera: null handle");
+  if (!ps->has_camera) return fail(SSHIP_ERR_INVALID, "pose_get_camera: no camera has been set");
+  if (fx) *fx = ps->fx;
+  if (fy) *fy = ps->fy;
+  if (cx) *cx = ps->cx;
+  if (cy) *cy = ps->cy;
+  if (baseline) *baseline = ps->baseline;
+  return SSHIP_OK;
+}
+extern "C" int sship_pose_set_params(sship_pose* ps, const sship_pose_params* p) {
+  if (!ps || !p) return fail(SSHIP_ERR_INVALID, "pose_set_params: null argument");
+  const double all[9] = {p->sigma_px, p->sigma_d0, p->cond_depth, p->huber_k2, p->lambda0, p->lambda_max, p->abs_tol, p->rel_tol, p->inlier_px};
+  for (double v : all)
+    if (std::isnan(v)) return fail(SSHIP_ERR_INVALID, "pose_set_params: a parameter is NaN");
+  if (!(p->sigma_px > 0.0) || !(p->sigma_d0 > 0.0) || !(p->cond_depth > 0.0) || !(p->huber_k2 > 0.0) || std::isinf(p->sigma_px) ||
+      std::isinf(p->sigma_d0) || std::isinf(p->cond_depth) || std::isinf(p->huber_k2))
+    return fail(SSHIP_ERR_INVALID, "pose_set_params: sigma_px, sigma_d0, cond_depth and huber_k2 must be finite and > 0");
+  if (!(p->lambda0 > 0.0) || p->lambda_max < p->lambda0 || std::isinf(p->lambda_max))
+    return fail(SSHIP_ERR_INVALID, "pose_set_params: lambda0 must be > 0 and lambda_max finite and >= lambda0");
+  if (p->abs_tol < 0.0 || p->rel_tol < 0.0 || p->inlier_px < 0.0) return fail(SSHIP_ERR_INVALID, "pose_set_params: a tolerance or inlier_px is negative");
+  if (p->max_iterations < 1) return fail(SSHIP_ERR_INVALID, "pose_set_params: max_iterations must be >= 1");
+  ps->prm = *p;
+  return SSHIP_OK;
+}
+extern "C" int sship_pose_get_params(const sship_pose* ps, sship_pose_params* p) {
+  if (!ps || !p) return fail(SSHIP_ERR_INVALID, "pose_get_params: null argument");
+  *p = ps->prm;
+  return SSHIP_OK;
+}
+static int pose_launch(sship_pose* ps, const float* points, const float* meas, const uint8_t* valid, const double* pose0, int pairs, double* pose,
+                       int32_t* stats, double* cost, uint8_t* inlier, hipStream_t s) {
+  sship_pose::Last& l = ps->last;
+  l.points = points; l.meas = meas; l.valid = valid; l.pose0 = pose0; l.pairs = pairs; l.pose = pose; l.stats = stats; l.cost = cost; l.inlier = inlier;
+  launch_pose_solve(points, meas, valid, pose0, ps->max_obs, pairs, pose_constants(ps), pose, stats, cost, inlier, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  return SSHIP_OK;
+}
+extern "C" int sship_pose_solve_batch_device(sship_pose* ps, const float* points, const float* meas, const uint8_t* valid, const double* pose0,
+                                             int pairs, double* pose, int32_t* stats, double* cost, uint8_t* inlier, void* stream) {
+  if (!ps || !points || !meas || !valid || !pose || !stats || !cost) return fail(SSHIP_ERR_INVALID, "pose_solve_batch_device: null argument");
+  if (pairs < 1 || pairs > ps->max_pairs) return fail(SSHIP_ERR_INVALID, "pose_solve_batch_device: pairs must be in [1, max_pairs]");
+  if (!ps->has_camera) return fail(SSHIP_ERR_INVALID, "pose_solve_batch_device: set the camera first (sship_pose_set_camera)");
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  if (int rc = pose_launch(ps, points, meas, valid, pose0, pairs, pose, stats, cost, inlier, s)) return rc;
+  g_timer.mark("pose_solve", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_pose_solve_host(sship_pose* ps, const float* points, const float* meas, const uint8_t* valid, int n_obs, const double* pose0,
+                                     double* pose_out, int32_t* stats_out, double* cost_out, uint8_t* inlier_out) {
+  if (!ps || !pose_out || !stats_out || !cost_out) return fail(SSHIP_ERR_INVALID, "pose_solve_host: null argument");
+  if (n_obs < 0 || n_obs > ps->max_obs) return fail(SSHIP_ERR_INVALID, "pose_solve_host: n_obs must be in [0, max_obs]");
+  if (n_obs > 0 && (!points || !meas)) return fail(SSHIP_ERR_INVALID, "pose_solve_host: null argument");
+  if (!ps->has_camera) return fail(SSHIP_ERR_INVALID, "pose_solve_host: set the camera first (sship_pose_set_camera)");
+  bind_thread();
+  hipStream_t s = ps->stream;
+  const size_t n = (size_t)ps->max_obs, m = (size_t)n_obs;
+  // pinned staging: points | meas | pose0 | valid, rows >= n_obs absent
+  char* hin = static_cast<char*>(ps->h_in.p);
+  float* hp = reinterpret_cast<float*>(hin);
+  float* hm = reinterpret_cast<float*>(hin + n * 12);
+  double* h0 = reinterpret_cast<double*>(hin + n * 24);
+  uint8_t* hv = reinterpret_cast<uint8_t*>(hin + n * 24 + 96);
+  memset(hin, 0, n * 25 + 96);
+  if (m) { memcpy(hp, points, m * 12); memcpy(hm, meas, m * 12); }
+  for (size_t i = 0; i < m; ++i) hv[i] = valid ? (valid[i] != 0) : 1;
+  if (pose0) memcpy(h0, pose0, 96);
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ps->points1.p, hp, n * 12, hipMemcpyHostToDevice, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ps->meas1.p, hm, n * 12, hipMemcpyHostToDevice, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ps->valid1.p, hv, n, hipMemcpyHostToDevice, s));
+  if (pose0) SSHIP_HIP_CHECK(hipMemcpyAsync(ps->pose01.p, h0, 96, hipMemcpyHostToDevice, s));
+  if (int rc = pose_launch(ps, ps->points1.as<float>(), ps->meas1.as<float>(), ps->valid1.as<uint8_t>(), pose0 ? ps->pose01.as<double>() : nullptr, 1,
+                           ps->pose1.as<double>(), ps->stats1.as<int32_t>(), ps->cost1.as<double>(), ps->inlier1.as<uint8_t>(), s))
+    return rc;
+  char* hout = static_cast<char*>(ps->h_out.p);   // pose (96) | cost (16) | stats (16) | inlier
+  SSHIP_HIP_CHECK(hipMemcpyAsync(hout, ps->pose1.p, 96, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(hout + 96, ps->cost1.p, 16, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(hout + 112, ps->stats1.p, 16, hipMemcpyDeviceToHost, s));
+  if (inlier_out && m) SSHIP_HIP_CHECK(hipMemcpyAsync(hout + 128, ps->inlier1.p, m, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipStreamSynchronize(s));
+  memcpy(pose_out, hout, 96);
+  memcpy(cost_out, hout + 96, 16);
+  memcpy(stats_out, hout + 112, 16);
+  if (inlier_out && m) memcpy(inlier_out, hout + 128, m);
+  return SSHIP_OK;
+}
+extern "C" int sship_pose_obs_from_matches_batch_device(const sship_pose* ps, const float* stereo0, const uint8_t* hd0, const float* stereo1,
+                                                        const uint8_t* hd1, const int32_t* matches0, const int* n0, const int* n1, int n_stride,
+                                                        int pairs, float* points, float* meas, uint8_t* valid, void* stream) {
+  if (!ps || !stereo0 || !hd0 || !stereo1 || !hd1 || !matches0 || !n0 || !n1 || !points || !meas || !valid)
+    return fail(SSHIP_ERR_INVALID, "pose_obs_from_matches_batch_device: null argument");
+  if (pairs < 1 || pairs > ps->max_pairs) return fail(SSHIP_ERR_INVALID, "pose_obs_from_matches_batch_device: pairs must be in [1, max_pairs]");
+  if (n_stride < 1) return fail(SSHIP_ERR_INVALID, "pose_obs_from_matches_batch_device: n_stride must be >= 1");
+  if (!ps->has_camera) return fail(SSHIP_ERR_INVALID, "pose_obs_from_matches_batch_device: set the camera first (sship_pose_set_camera)");
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  launch_pose_gather(stereo0, hd0, stereo1, hd1, matches0, n0, n1, n_stride, ps->max_obs, pairs, pose_constants(ps), points, meas, valid, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("pose_gather", s);
+  return SSHIP_OK;
+}
+// Measurement hook (include/sship.h): the last solve call's launch re-run `iters` times on the handle's stream.
+extern "C" int sship_pose_bench(sship_pose* ps, int iters, float* avg_ms) {
+  if (!ps || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "pose_bench: bad arguments");
+  if (ps->last.pairs <= 0) return fail(SSHIP_ERR_INVALID, "pose_bench: run a solve on this handle first");
+  bind_thread();
+  hipStream_t s = ps->stream;
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
+  const sship_pose::Last& l = ps->last;
+  const PoseK k = pose_constants(ps);
+  auto run = [&]() -> hipError_t {
+    launch_pose_solve(l.points, l.meas, l.valid, l.pose0, ps->max_obs, l.pairs, k, l.pose, l.stats, l.cost, l.inlier, s);
+    return hipGetLastError();
+  };
+  SSHIP_HIP_CHECK(run());  // warm
+  hipEvent_t e0, e1;
+  SSHIP_HIP_CHECK(hipEventCreate(&e0));
+  SSHIP_HIP_CHECK(hipEventCreate(&e1));
+  SSHIP_HIP_CHECK(hipEventRecord(e0, s));
+  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
+  SSHIP_HIP_CHECK(hipEventRecord(e1, s));
+  SSHIP_HIP_CHECK(hipEventSynchronize(e1));
+  float ms = 0.f;
+  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
+  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  *avg_ms = ms / iters;
+  return SSHIP_OK;
+}
+
+// ====================================================================================================
 // fused front-end step: SuperPoint(batch 2P) + select + gather + LightGlue(P)
 // ====================================================================================================
 extern "C" int sship_frontend_batch_device(sship_sp* sp, sship_lg* lg, const uint8_t* imgs, int pairs, int h, int w,

@@ -237,4 +237,20 @@ void launch_index_normalize(const float* src, long long stride, int count, int r
 void launch_index_query(const float* db, int dim, int size, const float* q, long long q_stride, int num_queries, const int* limits, int limit_all,
                         int top_k, float min_score, float* qn, unsigned long long* partial, int* rows, float* scores, int* counts, hipStream_t s);
 
+// ---- pose_kernels.hip : pose-only stereo solver (sship_pose_*) ----
+constexpr int kPoseMaxObs = 2048;   // 8 observations per thread of a 256-thread workgroup, held in registers
+struct PoseK {                      // the camera and the rule's constants, by value
+  double fx, fy, cx, cy, baseline;
+  double inv_sigma_px, sigma_d0, d_cond, k, k2;
+  double lambda0, lambda_max, abs_tol, rel_tol, inlier_px;
+  int max_iterations;
+};
+// one workgroup per pair, the whole LM loop in the launch.  pose0 / inlier may be null; every output entry is written.
+void launch_pose_solve(const float* points, const float* meas, const uint8_t* valid, const double* pose0, int max_obs, int pairs,
+                       const PoseK& k, double* pose, int32_t* stats, double* cost, uint8_t* inlier, hipStream_t s);
+// the observation list from two frames' stereo points and matches0 (include/sship.h); every output entry is written.
+void launch_pose_gather(const float* stereo0, const uint8_t* hd0, const float* stereo1, const uint8_t* hd1, const int32_t* matches0,
+                        const int* n0, const int* n1, int n_stride, int max_obs, int pairs, const PoseK& k, float* points, float* meas,
+                        uint8_t* valid, hipStream_t s);
+
 }  // namespace sship
