@@ -634,6 +634,105 @@ int sship_pose_obs_from_matches_batch_device(const sship_pose* ps, const float* 
 int sship_pose_bench(sship_pose* ps, int iters, float* avg_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * Window smoother - sliding-window stereo bundle adjustment: what VoEstimator::track does at every keyframe with smoother_.optimize()
+ * (src/VoEstimator.cc:316-323, src/WindowSmoother.cc): a fixed-lag window of the last keyframe poses re-optimised against all stereo
+ * observations of the landmarks they share, the landmarks eliminated.  `windows` windows per call, device-resident, no GTSAM.  The
+ * objective follows the reference; the schedule is the pose-only solver's and is stated here - the rule is NOT "whatever GTSAM's smart
+ * factors do".  Measurements are fp32 and are widened on load; all arithmetic is fp64.  The rule:
+ *   Camera as in sship_pose_set_camera.  Poses are Twc = [R | t], row-major 3x4, 12 doubles.
+ *   Window w has K = max_keyframes slots, the oldest first; n_kf = n_kf_dev[w] clamped to [0, K] (NULL: K).  Slot 0 is the gauge and is
+ *     HELD FIXED (the reference pins it with a prior of sigma 1e-4, WindowSmoother.cc:58-60).
+ *   Observation (k, i), k < n_kf, i < max_obs: meas[w, k, i] = (uL, uR, v) f32 and track[w, k, i] i32.  It is PRESENT iff
+ *     0 <= track < max_landmarks, the three floats are finite (the (uL, NaN, vL) rows of stereo association are absent without a flag), and
+ *     no lower row i' < i of the same keyframe is present with the same landmark (the lowest row wins).
+ *   Landmark l is ACTIVE iff it has present observations in at least 2 keyframes (WindowSmoother.cc:85-87) and at least one of them has
+ *     uL - uR > 0.  Only observations of active landmarks count: n_obs is their number, n_landmarks the number of active landmarks.
+ *   Initial point: from the present observation with uL - uR > 0 in the lowest slot k: Xc = backproject_cam (LoopCloser.cc:19-24:
+ *     Z = fx baseline / (uL - uR), X = (uL - cx) Z / fx, Y = (v - cy) Z / fy) in fp64, X_l = R_k Xc + t_k with pose0 of that slot; kept in fp64.
+ *   Residual: q = R_k^T (X_l - t_k); r = projection(q) - meas with the pose-only rule's projection; whitened r~ = r / sigma_px on all three
+ *     components (the smart factors need isotropic noise, WindowSmoother.cc:62-68).  Behind the camera, !(q.z > 0): the constant residual
+ *     r = (2 fx, 2 fx, 2 fx) and zero Jacobians.
+ *   Huber on e = |r~| with k^2 = huber_k2: rho = e^2 / 2 for e <= k, k e - k^2 / 2 above; IRLS weight w = min(1, k / e).  It stands where
+ *     the reference's setDynamicOutlierRejectionThreshold(3.0) stands; the reference drops such observations, here they are down-weighted.
+ *   Jacobians, whitened: Jp (3x6) for the right perturbation T Exp(xi), xi = (omega, v): dq/d omega = [q]x, dq/dv = -I;  Jl (3x3): dq/dX = R_k^T.
+ *   Normal equations at a state: c = sum rho;  per slot k >= 1: A_k = sum w Jp^T Jp, a_k = sum w Jp^T r~;  per active landmark:
+ *     C_l = sum w Jl^T Jl, c_l = sum w Jl^T r~;  per observation W_kl = w Jp^T Jl (6x3).  Slot 0's observations enter c, C_l and c_l only.
+ *   One trial at damping lambda: C~_l = C_l + lambda I = L L^T by 3x3 Cholesky;  S = blockdiag(A_k + lambda I) - sum_l W_kl C~_l^-1 W_k'l^T
+ *     over k, k' >= 1;  b = -a + sum_l W_kl C~_l^-1 c_l;  Cholesky of S, of order 6 (n_kf - 1) <= 90, gives delta_k (delta_0 = 0);
+ *     delta_l = -C~_l^-1 (c_l + sum_k W_kl^T delta_k);  T_k' = T_k Exp(delta_k), the full SE(3) exponential without re-orthonormalisation;
+ *     X_l' = X_l + delta_l.  A pivot that is not > 0, in any 3x3 or in S, makes the trial a rejected one: counted, nothing evaluated.
+ *   Schedule: the pose-only rule's.  (c, normal equations) at the start, lambda = lambda0.  Repeat: trials == max_iterations stops with
+ *     ITER_CAP; one trial; c' at the candidate; then, in this order: c' finite and |c - c'| <= max(abs_tol, rel_tol c): take it, CONVERGED,
+ *     stop;  else c' < c: accept, lambda /= 10, new normal equations;  else reject, lambda *= 10, and lambda > lambda_max stops with STALLED.
+ *   n_kf < 2 (the reference's "need parallax" return) or no active landmark: TOO_FEW.  A non-finite pose0 in a slot < n_kf: BAD_INPUT.  In
+ *     both every pose out is the pose in, trials and both costs are 0, and every landmark out is NaN; n_obs and n_landmarks are still counted.
+ *   A finite pose0 whose arithmetic overflows cannot be evaluated: the initial cost is NaN or Inf, every pivot fails, the trials are counted
+ *     without an evaluation until lambda passes lambda_max, and the window ends STALLED with the pose in and both costs out non-finite.
+ *   Defaults: sigma_px 1, huber_k2 9 (3 sigma), lambda0 1e-5, lambda_max 1e5, abs_tol = rel_tol = 1e-3 (the reference's,
+ *     WindowSmoother.cc:96-97), max_iterations 20 (it counts trials; the reference caps GTSAM's outer iterations at 4).
+ *   Two further differences from the smart factors: landmarks are variables eliminated by the Schur complement at their current estimate,
+ *     not re-triangulated at every linearisation; a degenerate landmark is simply an ill-conditioned 3x3 that lambda regularises (no
+ *     ZERO_ON_DEGENERACY mode).
+ *   A consequence of down-weighting instead of dropping: a landmark seen in TWO keyframes of which one measurement is a gross mismatch has no
+ *     point that fits both rays.  Its observations keep a Huber pull of k on the poses and its point drifts far away (finite, up to 1e7 m on
+ *     the tests' scenes) while the window still ends CONVERGED or at ITER_CAP; with a fifth of the two-view tracks corrupted the poses were
+ *     recovered to 0.01 - 0.12 m instead of 0.01 - 0.02 m (tests/test_ba_cpu.py pins this).  A caller whose matches carry such mismatches
+ *     should gate them before the solve (the keypoint-window gate, the pose-only solver's inlier mask) or leave two-view tracks out.
+ *   Determinism: every sum runs in one fixed order - the blocks of a landmark over its slots in ascending k, the sums of a slot and of
+ *     the cost per thread over its rows in index order, then lanes, then waves; every entry of S and b over the active landmarks in ascending
+ *     l by one thread.  A window gives the same bits alone, inside any batch, at any batch position, and on a second call.
+ * Handle: sship_ba_create(max_keyframes 2..16, max_obs 1..2048, max_landmarks 1..32768, max_windows 1..65535).  Workspace, allocated once
+ * at create:  min(max_windows, 512) x ceil16(max_landmarks (4 max_keyframes + 204) + 288 max_keyframes max_obs) bytes (a launch runs at most
+ * 512 workgroups, which walk the windows), plus the staging of sship_ba_solve_host, one window's inputs and outputs.
+ * Bad arguments are refused with SSHIP_ERR_INVALID and a message before any device is touched, the handle unchanged: a NULL handle or
+ * pointer, a create argument or `windows` out of range, a camera not set, fx, fy or baseline not > 0 (or any camera value not finite), a NaN
+ * in the params, sigma_px, huber_k2 or lambda0 not > 0 (or not finite), lambda_max < lambda0 or infinite, a negative tolerance,
+ * max_iterations < 1.  Valid create arguments without a GPU give SSHIP_ERR_NO_DEVICE.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sship_ba sship_ba;
+typedef struct sship_ba_params {
+  double sigma_px, huber_k2;
+  double lambda0, lambda_max, abs_tol, rel_tol;
+  int max_iterations;
+} sship_ba_params;
+#define SSHIP_BA_CONVERGED 0
+#define SSHIP_BA_ITER_CAP 1
+#define SSHIP_BA_STALLED 2
+#define SSHIP_BA_TOO_FEW 3
+#define SSHIP_BA_BAD_INPUT 4
+int sship_ba_create(int max_keyframes, int max_obs, int max_landmarks, int max_windows, sship_ba** out);
+void sship_ba_destroy(sship_ba* ba);
+int sship_ba_set_camera(sship_ba* ba, double fx, double fy, double cx, double cy, double baseline);
+int sship_ba_get_camera(const sship_ba* ba, double* fx, double* fy, double* cx, double* cy, double* baseline); /* any output may be NULL */
+int sship_ba_set_params(sship_ba* ba, const sship_ba_params* params);
+int sship_ba_get_params(const sship_ba* ba, sship_ba_params* params);
+/* Throughput path, one launch, asynchronous on `stream` (NULL = the legacy default stream), no host synchronisation inside; calls on one
+ * handle share its workspace and must be ordered by the caller.  meas_dev [windows, K, max_obs, 3] f32, track_dev [windows, K, max_obs] i32,
+ * n_kf_dev [windows] i32 or NULL, pose0_dev [windows, K, 12] f64;  pose_dev [windows, K, 12] f64 (slot 0 and slots >= n_kf keep the bits of
+ * pose0), stats_dev [windows, 4] i32 = (n_obs, n_landmarks, trials, status), cost_dev [windows, 2] f64 = (initial, final), landmarks_dev
+ * [windows, max_landmarks, 3] f32 or NULL: the final X_l rounded once for active landmarks, quiet NaN elsewhere.  Every entry is written. */
+int sship_ba_solve_batch_device(sship_ba* ba, const float* meas_dev, const int32_t* track_dev, const int32_t* n_kf_dev, const double* pose0_dev,
+                                int windows, double* pose_dev, int32_t* stats_dev, double* cost_dev, float* landmarks_dev, void* stream);
+/* One window from host arrays - the drop-in for one WindowSmoother::optimize: meas [K, max_obs, 3], track [K, max_obs], n_kf in 0..K,
+ * pose0 [K, 12]; pose_out [K, 12], stats_out [4], cost_out [2], landmarks_out [max_landmarks, 3] or NULL.  Synchronous on the handle's own
+ * stream; the same launch as the batch call with windows = 1, hence the same bits. */
+int sship_ba_solve_host(sship_ba* ba, const float* meas, const int32_t* track, int n_kf, const double* pose0, double* pose_out,
+                        int32_t* stats_out, double* cost_out, float* landmarks_out);
+/* The landmark bookkeeping of VoEstimator.cc:208-214,252-266,306-315 as a device stage, one launch, asynchronous on `stream`:
+ * has_depth_dev [windows, K, max_obs] u8 (of sship_stereo_associate_batch_device), matches_dev [windows, K - 1, max_obs] i32 where
+ * matches_dev[w, k] is matches0 from keyframe k's to keyframe k + 1's left keypoints, n_dev [windows, K] i32 left-image counts (clamped to
+ * [0, max_obs]), n_kf_dev [windows] or NULL;  track_dev [windows, K, max_obs] i32.
+ *   track[0][i] = i for a row i < n_0 with has_depth.  For k >= 1 and a row j < n_k with has_depth: if some i < n_{k-1} has
+ *   matches[k-1][i] == j and track[k-1][i] >= 0 then track[k][j] = track[k-1][i], the HIGHEST such i winning (the reference's map
+ *   assignment in ascending match order); otherwise track[k][j] = k max_obs + j, a new landmark named by its first observation.
+ *   Every other entry, slots >= n_kf included, is -1; every entry is written.  Needs max_landmarks >= max_keyframes max_obs. */
+int sship_ba_tracks_from_matches_batch_device(const sship_ba* ba, const uint8_t* has_depth_dev, const int32_t* matches_dev, const int32_t* n_dev,
+                                              const int32_t* n_kf_dev, int windows, int32_t* track_dev, void* stream);
+/* Measurement hook: re-run the last solve call's launch on this handle `iters` times (over the same buffers, which the caller of a batch
+ * call keeps alive), timed with hipEvents on the handle's stream; *avg_ms = mean duration of one launch. */
+int sship_ba_bench(sship_ba* ba, int iters, float* avg_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused front-end step: what StereoFrontEnd::process asks of the two interfaces per frame
  * (src/StereoFrontEnd.cc:14,33): SuperPoint on L and R (one batch) + gather x2 + one LightGlue match,
  * for `pairs` stereo pairs at once, device-resident, no host synchronisation.  imgs_dev is

@@ -52,6 +52,11 @@ class PoseParams(C.Structure):
                 ("inlier_px", C.c_double), ("max_iterations", C.c_int)]
 
 
+class BaParams(C.Structure):
+    _fields_ = [("sigma_px", C.c_double), ("huber_k2", C.c_double), ("lambda0", C.c_double), ("lambda_max", C.c_double),
+                ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("max_iterations", C.c_int)]
+
+
 _lib = None
 vp, ip, fp, dp = C.c_void_p, C.c_int, C.c_float, C.c_double
 _SIGS = {
@@ -155,6 +160,16 @@ _SIGS = {
     "sship_pose_solve_host": (ip, [vp, vp, vp, vp, ip, vp, vp, vp, vp, vp]),
     "sship_pose_obs_from_matches_batch_device": (ip, [vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, vp, vp, vp, vp]),
     "sship_pose_bench": (ip, [vp, ip, C.POINTER(fp)]),
+    "sship_ba_create": (ip, [ip, ip, ip, ip, C.POINTER(vp)]),
+    "sship_ba_destroy": (None, [vp]),
+    "sship_ba_set_camera": (ip, [vp, dp, dp, dp, dp, dp]),
+    "sship_ba_get_camera": (ip, [vp, C.POINTER(dp), C.POINTER(dp), C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]),
+    "sship_ba_set_params": (ip, [vp, C.POINTER(BaParams)]),
+    "sship_ba_get_params": (ip, [vp, C.POINTER(BaParams)]),
+    "sship_ba_solve_batch_device": (ip, [vp, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp]),
+    "sship_ba_solve_host": (ip, [vp, vp, vp, ip, vp, vp, vp, vp, vp]),
+    "sship_ba_tracks_from_matches_batch_device": (ip, [vp, vp, vp, vp, vp, ip, vp, vp]),
+    "sship_ba_bench": (ip, [vp, ip, C.POINTER(fp)]),
     "sship_desc_to_host": (ip, [vp, ip, ip, vp]),
     "sship_frontend_batch_device": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_bench_layer": (ip, [vp, ip, ip, ip, ip, ip, C.POINTER(fp), C.POINTER(C.c_double)]),

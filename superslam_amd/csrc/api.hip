@@ -2879,6 +2879,12 @@ extern "C" int sship_index_bench(sship_index* ix, int iters, float* avg_ms) {
   return SSHIP_OK;
 }
 
+// the two events of a measurement hook: destroyed whichever way the hook returns
+struct EventPair {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+
 // ====================================================================================================
 // Pose-only stereo solver (include/sship.h "Pose-only stereo solver"; csrc/pose_kernels.hip)
 // ====================================================================================================
@@ -3061,16 +3067,205 @@ extern "C" int sship_pose_bench(sship_pose* ps, int iters, float* avg_ms) {
     return hipGetLastError();
   };
   SSHIP_HIP_CHECK(run());  // warm
-  hipEvent_t e0, e1;
-  SSHIP_HIP_CHECK(hipEventCreate(&e0));
-  SSHIP_HIP_CHECK(hipEventCreate(&e1));
-  SSHIP_HIP_CHECK(hipEventRecord(e0, s));
+  EventPair ev;            // destroyed on every return
+  SSHIP_HIP_CHECK(hipEventCreate(&ev.e0));
+  SSHIP_HIP_CHECK(hipEventCreate(&ev.e1));
+  SSHIP_HIP_CHECK(hipEventRecord(ev.e0, s));
   for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
-  SSHIP_HIP_CHECK(hipEventRecord(e1, s));
-  SSHIP_HIP_CHECK(hipEventSynchronize(e1));
+  SSHIP_HIP_CHECK(hipEventRecord(ev.e1, s));
+  SSHIP_HIP_CHECK(hipEventSynchronize(ev.e1));
   float ms = 0.f;
-  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  *avg_ms = ms / iters;
+  return SSHIP_OK;
+}
+
+// ====================================================================================================
+// Window smoother: sliding-window stereo bundle adjustment (include/sship.h "Window smoother"; csrc/ba_kernels.hip)
+// ====================================================================================================
+constexpr int kBaMaxWindows = 65535;
+struct sship_ba {
+  int K = 0, N = 0, L = 0, max_windows = 0;
+  bool has_camera = false;
+  double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;
+  sship_ba_params prm{1.0, 9.0, 1e-5, 1e5, 1e-3, 1e-3, 20};
+  hipStream_t stream = nullptr;
+  DevBuf workspace;
+  DevBuf meas1, track1, nkf1, pose01, pose1, stats1, cost1, lm1;   // sship_ba_solve_host: one staged window and its results
+  PinBuf h_in, h_out;
+  struct Last { const float* meas = nullptr; const int32_t* track = nullptr; const int32_t* n_kf = nullptr; const double* pose0 = nullptr; int windows = 0;
+                double* pose = nullptr; int32_t* stats = nullptr; double* cost = nullptr; float* landmarks = nullptr; } last;
+};
+static BaK ba_constants(const sship_ba* ba) {
+  BaK k;
+  k.fx = ba->fx; k.fy = ba->fy; k.cx = ba->cx; k.cy = ba->cy; k.baseline = ba->baseline;
+  k.inv_sigma = 1.0 / ba->prm.sigma_px; k.k = std::sqrt(ba->prm.huber_k2); k.k2 = ba->prm.huber_k2;
+  k.lambda0 = ba->prm.lambda0; k.lambda_max = ba->prm.lambda_max; k.abs_tol = ba->prm.abs_tol; k.rel_tol = ba->prm.rel_tol;
+  k.max_iterations = ba->prm.max_iterations;
+  return k;
+}
+extern "C" int sship_ba_create(int max_keyframes, int max_obs, int max_landmarks, int max_windows, sship_ba** out) {
+  if (!out) return fail(SSHIP_ERR_INVALID, "ba_create: null argument");
+  *out = nullptr;
+  if (max_keyframes < 2 || max_keyframes > kBaMaxKf) return fail(SSHIP_ERR_INVALID, "ba_create: max_keyframes must be in [2, 16]");
+  if (max_obs < 1 || max_obs > kBaMaxObs) return fail(SSHIP_ERR_INVALID, "ba_create: max_obs must be in [1, 2048]");
+  if (max_landmarks < 1 || max_landmarks > kBaMaxLandmarks) return fail(SSHIP_ERR_INVALID, "ba_create: max_landmarks must be in [1, 32768]");
+  if (max_windows < 1 || max_windows > kBaMaxWindows) return fail(SSHIP_ERR_INVALID, "ba_create: max_windows must be in [1, 65535]");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  std::unique_ptr<sship_ba, void (*)(sship_ba*)> ba(new sship_ba(), sship_ba_destroy);
+  ba->K = max_keyframes; ba->N = max_obs; ba->L = max_landmarks; ba->max_windows = max_windows;
+  const size_t kn = (size_t)max_keyframes * max_obs, l3 = (size_t)max_landmarks * 12, k12 = (size_t)max_keyframes * 96;
+  SSHIP_HIP_CHECK(ba->workspace.ensure(ba_workspace_bytes(max_keyframes, max_obs, max_landmarks) * (size_t)std::min(max_windows, kBaResident)));
+  SSHIP_HIP_CHECK(ba->meas1.ensure(kn * 12));
+  SSHIP_HIP_CHECK(ba->track1.ensure(kn * 4));
+  SSHIP_HIP_CHECK(ba->nkf1.ensure(16));
+  SSHIP_HIP_CHECK(ba->pose01.ensure(k12));
+  SSHIP_HIP_CHECK(ba->pose1.ensure(k12));
+  SSHIP_HIP_CHECK(ba->stats1.ensure(16));
+  SSHIP_HIP_CHECK(ba->cost1.ensure(16));
+  SSHIP_HIP_CHECK(ba->lm1.ensure(l3));
+  SSHIP_HIP_CHECK(ba->h_in.ensure(k12 + kn * 16 + 16));
+  SSHIP_HIP_CHECK(ba->h_out.ensure(k12 + 32 + l3));
+  SSHIP_HIP_CHECK(ba_solve_prepare());
+  SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&ba->stream, hipStreamDefault));
+  *out = ba.release();
+  return SSHIP_OK;
+}
+extern "C" void sship_ba_destroy(sship_ba* ba) {
+  if (!ba) return;
+  bind_thread();
+  (void)hipDeviceSynchronize();
+  if (ba->stream) (void)hipStreamDestroy(ba->stream);
+  delete ba;
+}
+extern "C" int sship_ba_set_camera(sship_ba* ba, double fx, double fy, double cx, double cy, double baseline) {
+  if (!ba) return fail(SSHIP_ERR_INVALID, "ba_set_camera: null handle");
+  if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(baseline))
+    return fail(SSHIP_ERR_INVALID, "ba_set_camera: every camera value must be finite");
+  if (!(fx > 0.0) || !(fy > 0.0) || !(baseline > 0.0)) return fail(SSHIP_ERR_INVALID, "ba_set_camera: fx, fy and baseline must be > 0");
+  ba->fx = fx; ba->fy = fy; ba->cx = cx; ba->cy = cy; ba->baseline = baseline; ba->has_camera = true;
+  return SSHIP_OK;
+}
+extern "C" int sship_ba_get_camera(const sship_ba* ba, double* fx, double* fy, double* cx, double* cy, double* baseline) {
+  if (!ba) return fail(SSHIP_ERR_INVALID, "ba_get_camera: null handle");
+  if (!ba->has_camera) return fail(SSHIP_ERR_INVALID, "ba_get_camera: no camera has been set");
+  if (fx) *fx = ba->fx;
+  if (fy) *fy = ba->fy;
+  if (cx) *cx = ba->cx;
+  if (cy) *cy = ba->cy;
+  if (baseline) *baseline = ba->baseline;
+  return SSHIP_OK;
+}
+extern "C" int sship_ba_set_params(sship_ba* ba, const sship_ba_params* p) {
+  if (!ba || !p) return fail(SSHIP_ERR_INVALID, "ba_set_params: null argument");
+  const double all[6] = {p->sigma_px, p->huber_k2, p->lambda0, p->lambda_max, p->abs_tol, p->rel_tol};
+  for (double v : all)
+    if (std::isnan(v)) return fail(SSHIP_ERR_INVALID, "ba_set_params: a parameter is NaN");
+  if (!(p->sigma_px > 0.0) || !(p->huber_k2 > 0.0) || std::isinf(p->sigma_px) || std::isinf(p->huber_k2))
+    return fail(SSHIP_ERR_INVALID, "ba_set_params: sigma_px and huber_k2 must be finite and > 0");
+  if (!(p->lambda0 > 0.0) || p->lambda_max < p->lambda0 || std::isinf(p->lambda_max))
+    return fail(SSHIP_ERR_INVALID, "ba_set_params: lambda0 must be > 0 and lambda_max finite and >= lambda0");
+  if (p->abs_tol < 0.0 || p->rel_tol < 0.0) return fail(SSHIP_ERR_INVALID, "ba_set_params: a tolerance is negative");
+  if (p->max_iterations < 1) return fail(SSHIP_ERR_INVALID, "ba_set_params: max_iterations must be >= 1");
+  ba->prm = *p;
+  return SSHIP_OK;
+}
+extern "C" int sship_ba_get_params(const sship_ba* ba, sship_ba_params* p) {
+  if (!ba || !p) return fail(SSHIP_ERR_INVALID, "ba_get_params: null argument");
+  *p = ba->prm;
+  return SSHIP_OK;
+}
+static int ba_launch(sship_ba* ba, const float* meas, const int32_t* track, const int32_t* n_kf, const double* pose0, int windows, double* pose,
+                     int32_t* stats, double* cost, float* landmarks, hipStream_t s) {
+  sship_ba::Last& l = ba->last;
+  l.meas = meas; l.track = track; l.n_kf = n_kf; l.pose0 = pose0; l.windows = windows; l.pose = pose; l.stats = stats; l.cost = cost; l.landmarks = landmarks;
+  launch_ba_solve(meas, track, n_kf, pose0, ba->K, ba->N, ba->L, windows, ba_constants(ba), ba->workspace.p, pose, stats, cost, landmarks, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  return SSHIP_OK;
+}
+extern "C" int sship_ba_solve_batch_device(sship_ba* ba, const float* meas, const int32_t* track, const int32_t* n_kf, const double* pose0,
+                                           int windows, double* pose, int32_t* stats, double* cost, float* landmarks, void* stream) {
+  if (!ba || !meas || !track || !pose0 || !pose || !stats || !cost) return fail(SSHIP_ERR_INVALID, "ba_solve_batch_device: null argument");
+  if (windows < 1 || windows > ba->max_windows) return fail(SSHIP_ERR_INVALID, "ba_solve_batch_device: windows must be in [1, max_windows]");
+  if (!ba->has_camera) return fail(SSHIP_ERR_INVALID, "ba_solve_batch_device: set the camera first (sship_ba_set_camera)");
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  if (int rc = ba_launch(ba, meas, track, n_kf, pose0, windows, pose, stats, cost, landmarks, s)) return rc;
+  g_timer.mark("ba_solve", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_ba_solve_host(sship_ba* ba, const float* meas, const int32_t* track, int n_kf, const double* pose0, double* pose_out,
+                                   int32_t* stats_out, double* cost_out, float* landmarks_out) {
+  if (!ba || !meas || !track || !pose0 || !pose_out || !stats_out || !cost_out) return fail(SSHIP_ERR_INVALID, "ba_solve_host: null argument");
+  if (n_kf < 0 || n_kf > ba->K) return fail(SSHIP_ERR_INVALID, "ba_solve_host: n_kf must be in [0, max_keyframes]");
+  if (!ba->has_camera) return fail(SSHIP_ERR_INVALID, "ba_solve_host: set the camera first (sship_ba_set_camera)");
+  bind_thread();
+  hipStream_t s = ba->stream;
+  const size_t kn = (size_t)ba->K * ba->N, k12 = (size_t)ba->K * 96, l3 = (size_t)ba->L * 12;
+  char* hin = static_cast<char*>(ba->h_in.p);   // pose0 | meas | track | n_kf
+  memcpy(hin, pose0, k12);
+  memcpy(hin + k12, meas, kn * 12);
+  memcpy(hin + k12 + kn * 12, track, kn * 4);
+  const int32_t nk = n_kf;
+  memcpy(hin + k12 + kn * 16, &nk, 4);
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ba->pose01.p, hin, k12, hipMemcpyHostToDevice, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ba->meas1.p, hin + k12, kn * 12, hipMemcpyHostToDevice, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ba->track1.p, hin + k12 + kn * 12, kn * 4, hipMemcpyHostToDevice, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ba->nkf1.p, hin + k12 + kn * 16, 4, hipMemcpyHostToDevice, s));
+  if (int rc = ba_launch(ba, ba->meas1.as<float>(), ba->track1.as<int32_t>(), ba->nkf1.as<int32_t>(), ba->pose01.as<double>(), 1,
+                         ba->pose1.as<double>(), ba->stats1.as<int32_t>(), ba->cost1.as<double>(), ba->lm1.as<float>(), s))
+    return rc;
+  char* hout = static_cast<char*>(ba->h_out.p);   // pose | cost (16) | stats (16) | landmarks
+  SSHIP_HIP_CHECK(hipMemcpyAsync(hout, ba->pose1.p, k12, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(hout + k12, ba->cost1.p, 16, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(hout + k12 + 16, ba->stats1.p, 16, hipMemcpyDeviceToHost, s));
+  if (landmarks_out) SSHIP_HIP_CHECK(hipMemcpyAsync(hout + k12 + 32, ba->lm1.p, l3, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipStreamSynchronize(s));
+  memcpy(pose_out, hout, k12);
+  memcpy(cost_out, hout + k12, 16);
+  memcpy(stats_out, hout + k12 + 16, 16);
+  if (landmarks_out) memcpy(landmarks_out, hout + k12 + 32, l3);
+  return SSHIP_OK;
+}
+extern "C" int sship_ba_tracks_from_matches_batch_device(const sship_ba* ba, const uint8_t* has_depth, const int32_t* matches, const int32_t* n,
+                                                         const int32_t* n_kf, int windows, int32_t* track, void* stream) {
+  if (!ba || !has_depth || !matches || !n || !track) return fail(SSHIP_ERR_INVALID, "ba_tracks_from_matches_batch_device: null argument");
+  if (windows < 1 || windows > ba->max_windows) return fail(SSHIP_ERR_INVALID, "ba_tracks_from_matches_batch_device: windows must be in [1, max_windows]");
+  if ((long long)ba->L < (long long)ba->K * ba->N)
+    return fail(SSHIP_ERR_INVALID, "ba_tracks_from_matches_batch_device: needs max_landmarks >= max_keyframes * max_obs");
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  launch_ba_tracks(has_depth, matches, n, n_kf, ba->K, ba->N, windows, track, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("ba_tracks", s);
+  return SSHIP_OK;
+}
+// Measurement hook (include/sship.h): the last solve call's launch re-run `iters` times on the handle's stream.
+extern "C" int sship_ba_bench(sship_ba* ba, int iters, float* avg_ms) {
+  if (!ba || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "ba_bench: bad arguments");
+  if (ba->last.windows <= 0) return fail(SSHIP_ERR_INVALID, "ba_bench: run a solve on this handle first");
+  bind_thread();
+  hipStream_t s = ba->stream;
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
+  const sship_ba::Last& l = ba->last;
+  const BaK k = ba_constants(ba);
+  auto run = [&]() -> hipError_t {
+    launch_ba_solve(l.meas, l.track, l.n_kf, l.pose0, ba->K, ba->N, ba->L, l.windows, k, ba->workspace.p, l.pose, l.stats, l.cost, l.landmarks, s);
+    return hipGetLastError();
+  };
+  SSHIP_HIP_CHECK(run());  // warm
+  EventPair ev;            // destroyed on every return
+  SSHIP_HIP_CHECK(hipEventCreate(&ev.e0));
+  SSHIP_HIP_CHECK(hipEventCreate(&ev.e1));
+  SSHIP_HIP_CHECK(hipEventRecord(ev.e0, s));
+  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
+  SSHIP_HIP_CHECK(hipEventRecord(ev.e1, s));
+  SSHIP_HIP_CHECK(hipEventSynchronize(ev.e1));
+  float ms = 0.f;
+  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
   *avg_ms = ms / iters;
   return SSHIP_OK;
 }

@@ -253,4 +253,26 @@ void launch_pose_gather(const float* stereo0, const uint8_t* hd0, const float* s
                         const int* n0, const int* n1, int n_stride, int max_obs, int pairs, const PoseK& k, float* points, float* meas,
                         uint8_t* valid, hipStream_t s);
 
+// ---- ba_kernels.hip : sliding-window stereo bundle adjustment (sship_ba_*) ----
+constexpr int kBaMaxKf = 16;
+constexpr int kBaMaxObs = 2048;
+constexpr int kBaMaxLandmarks = 32768;
+constexpr int kBaResident = 512;    // workgroups of a solve launch (they walk the windows), each with a workspace slice
+struct BaK {                        // the camera and the rule's constants, by value
+  double fx, fy, cx, cy, baseline;
+  double inv_sigma, k, k2;
+  double lambda0, lambda_max, abs_tol, rel_tol;
+  int max_iterations;
+};
+// bytes of one workspace slice (include/sship.h states the formula); the handle holds min(max_windows, kBaResident) of them
+size_t ba_workspace_bytes(int max_keyframes, int max_obs, int max_landmarks);
+hipError_t ba_solve_prepare();
+// one workgroup per window, the whole LM loop in the launch.  n_kf / landmarks may be null; every output entry is written.
+void launch_ba_solve(const float* meas, const int32_t* track, const int32_t* n_kf, const double* pose0, int max_keyframes, int max_obs,
+                     int max_landmarks, int windows, const BaK& k, void* workspace, double* pose, int32_t* stats, double* cost,
+                     float* landmarks, hipStream_t s);
+// the landmark bookkeeping from has_depth and matches0 chains (include/sship.h); every entry of track is written.
+void launch_ba_tracks(const uint8_t* has_depth, const int32_t* matches, const int32_t* n, const int32_t* n_kf, int max_keyframes, int max_obs,
+                      int windows, int32_t* track, hipStream_t s);
+
 }  // namespace sship
