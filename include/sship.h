@@ -39,6 +39,7 @@
 #ifndef SSHIP_H_
 #define SSHIP_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -731,6 +732,137 @@ int sship_ba_tracks_from_matches_batch_device(const sship_ba* ba, const uint8_t*
 /* Measurement hook: re-run the last solve call's launch on this handle `iters` times (over the same buffers, which the caller of a batch
  * call keeps alive), timed with hipEvents on the handle's stream; *avg_ms = mean duration of one launch. */
 int sship_ba_bench(sship_ba* ba, int iters, float* avg_ms);
+
+/* ------------------------------------------------------------------------------------------------
+ * Pose graph - what GlobalPoseGraph::optimize_and_get_all does (src/GlobalPoseGraph.cc:56-98): the keyframe poses re-optimised against the
+ * odometry chain and the accepted loop closures, with the reference's drop-the-last-loop retry inside the launch.  `graphs` independent
+ * graphs per call, device-resident, fp64, no GTSAM.  The objective is the reference's (BetweenFactor<Pose3> under diagonal noise, Huber on
+ * the loops); the schedule is the pose-only solver's and is stated here - the rule is NOT "whatever GTSAM does".  The rule:
+ *   Graph g has n = n_nodes_dev[g] nodes clamped to [0, max_nodes] (NULL: max_nodes), in insertion order.  Poses are Twc = [R | t],
+ *     row-major 3x4, 12 doubles.  Node 0 is the gauge and is HELD FIXED (the reference pins it with a prior of sigma 1e-4,
+ *     GlobalPoseGraph.cc:29-30).
+ *   Odometry slot k < n - 1 (backbone_): odom_z[g, k] is the measured T_k^-1 T_{k+1}, odom_sigma[g, k, 0..5] its sigmas (rotation x3,
+ *     translation x3; a NULL array: (odom_sigma_rot x3, odom_sigma_trans x3) of the params, defaults 0.02 / 0.05, VoEstimator.cc:33-37).
+ *     No robust kernel.  The slot is PRESENT iff its 12 + 6 values are finite and every sigma is > 0.
+ *   Loop record l < max_loops (loops_): (i, j, Z, sigma[6], huber_k2).  PRESENT iff 0 <= i, j < n, i != j, all 12 + 6 + 1 values finite,
+ *     every sigma > 0, its enable byte non-zero (NULL: all) and the rejection loop below has not dropped it.  huber_k2 <= 0: no robust
+ *     kernel.  |i - j| == 1 is allowed and is still a loop record.  Anything absent contributes nothing, whatever it holds.
+ *   Residual of an edge (i, j, Z): r = Log(Z^-1 T_i^-1 T_j) = (omega, v), rotation first.  Log of E = [R_E | t_E]:
+ *     a = ((R21 - R12) / 2, (R02 - R20) / 2, (R10 - R01) / 2), s = |a|, c = (trace R_E - 1) / 2, theta = atan2(s, c);
+ *     omega = a / A(theta) for theta^2 < 1e-2, a theta / s otherwise;  v = t_E - (omega x t_E) / 2 + D(theta) omega x (omega x t_E).
+ *     (Within 1e-3 of theta = pi, s loses its digits and so does omega; no special branch.)
+ *   Coefficients, x = theta^2.  For x >= 1e-2 the closed forms A = sin(theta) / theta, B = 2 sin^2(theta / 2) / x, C = (theta - sin) / theta^3,
+ *     D = (1 - A / (2 B)) / x, C2 = (x + 2 cos - 2) / (2 x^2), C3 = (2 theta - 3 sin + theta cos) / (2 x^2 theta);  for x < 1e-2 the series
+ *     A = 1 - x/6 (1 - x/20 (1 - x/42 (1 - x/72))),  B = (1 - x/12 (1 - x/30 (1 - x/56 (1 - x/90)))) / 2,
+ *     C = (1 - x/20 (1 - x/42 (1 - x/72 (1 - x/110)))) / 6,  D = 1/12 + x/720 + x^2/30240 + x^3/1209600,
+ *     C2 = (1 - x/30 (1 - x/56 (1 - x/90))) / 24,  C3 = 1/120 - x/2520 + x^2/120960 - x^3/9979200.
+ *   Whitened r~ = r / sigma.  e = |r~|, k^2 = huber_k2: rho = e^2 / 2 for e <= k, k e - k^2 / 2 above; IRLS weight w = min(1, k / e).
+ *   Jacobians for the right perturbation T Exp(xi), xi = (omega, v):  dr/dxi_j = Jr^-1(r),  dr/dxi_i = -Jr^-1(r) Ad(T_j^-1 T_i),
+ *     Ad(T) = [[R, 0], [[t]x R, R]],  Jr^-1(r) = Jl(-r)^-1,  Jl(omega, v)^-1 = [[Ai, 0], [-Ai Q Ai, Ai]] with P = [omega]x, R = [v]x,
+ *     Ai = I - P / 2 + D P^2 and Q = R / 2 + C (PR + RP + PRP) + C2 (PPR + RPP - 3 PRP) + C3 (PRPP + PPRP)  (Barfoot, eq. 7.86b).
+ *     Whitened J~ = diag(1 / sigma) J.
+ *   Normal equations over the free nodes 1 .. n-1:  H = sum w J~^T J~,  g = sum w J~^T r~,  c = sum rho.  The sums of a node run over its
+ *     edges in the order odometry k-1, odometry k, loops in ascending record index; c per thread over the edges e = tid, tid + 256, ...
+ *     (odometry slots, then loop records), then lanes, then waves.
+ *   One trial at damping lambda solves (H + lambda I) delta = -g by Cholesky in this elimination order (nested dissection of the chain at
+ *     the loop endpoints):  a free node that is the endpoint of no present loop is INTERIOR;  each maximal run of interior nodes (a
+ *     SEGMENT) is eliminated from its lowest index upward - a block-tridiagonal Cholesky whose only fill is the block between the segment's
+ *     two bounding nodes;  the loop endpoints (SEPARATORS) are then eliminated in ascending node index by a dense Cholesky of order
+ *     6 x (number of separators) <= 12 max_loops.  A scalar pivot that is not > 0, anywhere, makes the trial a rejected one: counted,
+ *     nothing evaluated.  Otherwise T_k' = T_k Exp(delta_k), the full SE(3) exponential of the pose-only rule, without
+ *     re-orthonormalisation; delta_0 = 0.
+ *   Schedule: the pose-only rule's.  (c, normal equations) at the start, lambda = lambda0.  Repeat: this attempt's trials == max_iterations
+ *     stops with ITER_CAP; one trial; c' at the candidate; then, in this order: c' finite and |c - c'| <= max(abs_tol, rel_tol c): take it,
+ *     CONVERGED, stop;  else c' < c: accept, lambda /= 10, new normal equations;  else reject, lambda *= 10 (the same normal equations are
+ *     factorised again), and lambda > lambda_max stops with STALLED.
+ *   The rejection loop (GlobalPoseGraph.cc:56-93): after the schedule ends the result is SANE iff every pose entry of a node < n is finite
+ *     and every |t| <= max_translation.  Not sane and a present loop exists: the present loop with the highest record index is dropped,
+ *     loops_dropped grows by one and the solve restarts from pose0 with lambda0 (a new attempt).  Not sane and no loop left: every pose out
+ *     is the pose in, status DIVERGED.  `trials` counts over all attempts; the costs out are the first attempt's initial cost and the last
+ *     attempt's final cost.  GTSAM's IndeterminantLinearSystemException has no counterpart: a failed pivot is a rejected trial.
+ *     What the rejection loop catches is a loop that the solve FOLLOWS out of every sane range, such as a loop 1e9 m long from node 0 with
+ *     tight sigmas.  The same loop between two free nodes defeats every step instead (the damping is lambda I with lambda <= lambda_max,
+ *     nothing next to a Hessian of 1e24): the attempt ends STALLED at pose0, which is sane, nothing is dropped, and loop_chi2 names the loop
+ *     (tests/test_pg_cpu.py pins both).
+ *   n < 2 or no present edge: TOO_FEW.  A non-finite pose0 in a node < n: BAD_INPUT.  In both every pose out is the pose in, trials,
+ *     loops_dropped and both costs are 0, and every loop_chi2 is NaN; n_edges is still counted.
+ *   A node that no present edge connects to node 0 is held by lambda alone and stays where it is; it is not detected.
+ *   Defaults: odom sigmas 0.02 / 0.05, max_translation 1e6, and GTSAM's, which the reference uses unchanged (GlobalPoseGraph.cc:77):
+ *     lambda0 1e-5, lambda_max 1e5, abs_tol = rel_tol = 1e-5, max_iterations 100 (it counts trials).
+ *   Determinism: every sum runs in one fixed order and there are no floating-point atomics: a graph gives the same bits alone, inside any
+ *     batch, at any batch position and on a second call.
+ * Handle: sship_pg_create(max_nodes 2..4096, max_loops 0..128, max_graphs 1..65535).  Workspace, allocated once at create:
+ * min(max_graphs, 256) slices (a launch runs at most 256 workgroups, which walk the graphs) of
+ *   ceil16(8 (80 (N - 1 + L) + 222 N + 120 (S + 1) + (6 S)^2) + 4 (3 N + 5 S + 2))  bytes,  N = max_nodes, L = max_loops,
+ *   S = min(2 L, N - 1) the most separators a graph can have,
+ * plus the staging of sship_pg_solve_host, one graph's inputs and outputs.
+ * Bad arguments are refused with SSHIP_ERR_INVALID and a message before any device is touched, the handle unchanged: a NULL handle or
+ * pointer (the loop arrays may all be NULL when max_loops == 0; they must be all NULL or all given), a create argument, `graphs`, `n_nodes`
+ * or `n_loops` out of range, a NaN in the params, a sigma, lambda0 or max_translation not > 0 (or not finite), lambda_max < lambda0 or
+ * infinite, a negative tolerance, max_iterations < 1, min_inliers < 1, noise_base not finite and > 0.  Valid create arguments without a GPU
+ * give SSHIP_ERR_NO_DEVICE.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sship_pg sship_pg;
+typedef struct sship_pg_params {
+  double odom_sigma_rot, odom_sigma_trans;
+  double lambda0, lambda_max, abs_tol, rel_tol;
+  double max_translation;
+  int max_iterations;
+} sship_pg_params;
+#define SSHIP_PG_CONVERGED 0
+#define SSHIP_PG_ITER_CAP 1
+#define SSHIP_PG_STALLED 2
+#define SSHIP_PG_TOO_FEW 3
+#define SSHIP_PG_BAD_INPUT 4
+#define SSHIP_PG_DIVERGED 5
+int sship_pg_create(int max_nodes, int max_loops, int max_graphs, sship_pg** out);
+/* The bytes of one workspace slice as the library lays it out (the formula above); 0 for sizes that sship_pg_create refuses.  No device. */
+size_t sship_pg_workspace_slice_bytes(int max_nodes, int max_loops);
+void sship_pg_destroy(sship_pg* pg);
+int sship_pg_set_params(sship_pg* pg, const sship_pg_params* params);
+int sship_pg_get_params(const sship_pg* pg, sship_pg_params* params);
+/* Throughput path, one launch, asynchronous on `stream` (NULL = the legacy default stream), no host synchronisation inside; calls on one
+ * handle share its workspace and must be ordered by the caller.  With N = max_nodes and L = max_loops:  n_nodes_dev [graphs] i32 or NULL,
+ * pose0_dev [graphs, N, 12] f64, odom_z_dev [graphs, N - 1, 12] f64, odom_sigma_dev [graphs, N - 1, 6] f64 or NULL, loop_ij_dev
+ * [graphs, L, 2] i32, loop_z_dev [graphs, L, 12] f64, loop_sigma_dev [graphs, L, 6] f64, loop_k2_dev [graphs, L] f64, loop_enable_dev
+ * [graphs, L] u8 or NULL;  pose_dev [graphs, N, 12] f64 (node 0 and nodes >= n keep the bits of pose0), stats_dev [graphs, 4] i32 =
+ * (n_edges, loops_dropped, trials, status) with n_edges the present odometry slots plus the loops present in the last attempt, cost_dev
+ * [graphs, 2] f64 = (initial, final), loop_chi2_dev [graphs, L] f64 or NULL: e^2 of each loop present in the last attempt at the final
+ * poses, quiet NaN elsewhere.  Every entry of the outputs is written.  No output array may overlap an input array (pose_dev != pose0_dev:
+ * the solve restarts from pose0 after a dropped loop, and the kernel reads it to the end).
+ * Length of a launch: a graph is solved by ONE workgroup, a segment by one wave node after node, and the separator system is factorised
+ * column by column in the workspace.  Measured on an MI355X: about 3 ms per trial for 256 graphs of 512 nodes and 16 loops,
+ * 12 ms per trial for one graph of 4 096 nodes and 16 loops, and 0.55 s per trial with 128 loops (separator order 1 536) - so a launch
+ * that runs into max_iterations = 100 there occupies its compute unit for about a minute.  A caller on a shared device bounds it with
+ * max_iterations. */
+int sship_pg_solve_batch_device(sship_pg* pg, const int32_t* n_nodes_dev, const double* pose0_dev, const double* odom_z_dev,
+                                const double* odom_sigma_dev, const int32_t* loop_ij_dev, const double* loop_z_dev,
+                                const double* loop_sigma_dev, const double* loop_k2_dev, const uint8_t* loop_enable_dev, int graphs,
+                                double* pose_dev, int32_t* stats_dev, double* cost_dev, double* loop_chi2_dev, void* stream);
+/* One graph from host arrays - the drop-in for one optimize_and_get_all: pose0 [n_nodes, 12], odom_z [n_nodes - 1, 12], odom_sigma
+ * [n_nodes - 1, 6] or NULL, n_loops in 0..max_loops records loop_ij [n_loops, 2], loop_z [n_loops, 12], loop_sigma [n_loops, 6], loop_k2
+ * [n_loops] (all enabled);  pose_out [n_nodes, 12], stats_out [4], cost_out [2], loop_chi2_out [n_loops] or NULL.  n_nodes in 0..max_nodes.
+ * Synchronous on the handle's own stream; the same launch as the batch call with graphs = 1, hence the same bits. */
+int sship_pg_solve_host(sship_pg* pg, int n_nodes, const double* pose0, const double* odom_z, const double* odom_sigma, int n_loops,
+                        const int32_t* loop_ij, const double* loop_z, const double* loop_sigma, const double* loop_k2, double* pose_out,
+                        int32_t* stats_out, double* cost_out, double* loop_chi2_out);
+/* VoEstimator.cc:337-339 on the output of sship_ba_solve_batch_device, one launch, asynchronous on `stream`: from pose_dev [graphs, N, 12]
+ * odom_z_dev[g, k] = T_k^-1 T_{k+1} = [R_k^T R_{k+1} | R_k^T (t_{k+1} - t_k)] for k < N - 1, every three-term sum as (a0 b0 + a1 b1) + a2 b2
+ * with each product and sum rounded once (no fused multiply-add).  A non-finite pose gives a non-finite, hence absent, slot. */
+int sship_pg_odometry_from_poses_batch_device(const sship_pg* pg, const double* pose_dev, int graphs, double* odom_z_dev, void* stream);
+/* LoopCloser.cc:66-101 on the outputs of sship_pose_solve_batch_device, one launch, asynchronous on `stream`.  Pair p = g max_loops + l
+ * fills loop record l of graph g: i = from_dev[p] (the candidate), j = to_dev[p] (the query), Z = pose_dev[p] (T_candidate_query), with
+ * stats_dev [pairs, 4] the pose solver's (n_obs, n_inliers, trials, status).  Accepted iff n_obs >= min_inliers && n_inliers >= min_inliers,
+ * the status is neither TOO_FEW nor BAD_INPUT, and Z is finite.  s = noise_base / sqrt(n_inliers);  sigma = (max(s, 0.02) x3,
+ * max(s, 0.20) x3);  huber_k2 = 7.815;  the enable byte is the accepted flag.  A record that is not accepted carries Z and (i, j) as
+ * given and sigma = (0.02 x3, 0.20 x3).  Every entry of the five outputs is written.  The reference's min_inliers is 30, noise_base 0.1. */
+int sship_pg_loops_from_pose_batch_device(const sship_pg* pg, const int32_t* from_dev, const int32_t* to_dev, const double* pose_dev,
+                                          const int32_t* stats_dev, int graphs, int min_inliers, double noise_base, int32_t* loop_ij_dev,
+                                          double* loop_z_dev, double* loop_sigma_dev, double* loop_k2_dev, uint8_t* loop_enable_dev,
+                                          void* stream);
+/* Measurement hook: re-run the last solve call's launch on this handle `iters` times (over the same buffers, which the caller of a batch
+ * call keeps alive), timed with hipEvents on the handle's stream; *avg_ms = mean duration of one launch. */
+int sship_pg_bench(sship_pg* pg, int iters, float* avg_ms);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused front-end step: what StereoFrontEnd::process asks of the two interfaces per frame

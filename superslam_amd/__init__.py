@@ -9,6 +9,7 @@ from .frontend import FrontEndBatch, process_stereo, stereo_associate_batch  # n
 from .lightglue import LightGlue, LightGlueEngine, MatchResult  # noqa: F401
 from .nn_matcher import NNMatcher  # noqa: F401
 from .place_index import PlaceIndex  # noqa: F401
+from .pose_graph import PoseGraph, close_loops_batch  # noqa: F401
 from .pose_solver import PoseSolver, track_batch  # noqa: F401
 from .pool import DescriptorPool, DeviceDescriptors  # noqa: F401
 from .superpoint import Features, SuperPoint  # noqa: F401
@@ -16,4 +17,4 @@ from .window_smoother import WindowSmoother, smooth_batch  # noqa: F401
 
 __all__ = ["SuperPoint", "LightGlue", "LightGlueEngine", "MatchResult", "Features", "DescriptorPool",
            "DeviceDescriptors", "FrontEndBatch", "process_stereo", "stereo_associate_batch", "EigenPlaces", "NNMatcher", "PlaceIndex", "PoseSolver",
-           "track_batch", "WindowSmoother", "smooth_batch"]
+           "track_batch", "WindowSmoother", "smooth_batch", "PoseGraph", "close_loops_batch"]

@@ -57,6 +57,11 @@ class BaParams(C.Structure):
                 ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("max_iterations", C.c_int)]
 
 
+class PgParams(C.Structure):
+    _fields_ = [("odom_sigma_rot", C.c_double), ("odom_sigma_trans", C.c_double), ("lambda0", C.c_double), ("lambda_max", C.c_double),
+                ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("max_translation", C.c_double), ("max_iterations", C.c_int)]
+
+
 _lib = None
 vp, ip, fp, dp = C.c_void_p, C.c_int, C.c_float, C.c_double
 _SIGS = {
@@ -170,6 +175,16 @@ _SIGS = {
     "sship_ba_solve_host": (ip, [vp, vp, vp, ip, vp, vp, vp, vp, vp]),
     "sship_ba_tracks_from_matches_batch_device": (ip, [vp, vp, vp, vp, vp, ip, vp, vp]),
     "sship_ba_bench": (ip, [vp, ip, C.POINTER(fp)]),
+    "sship_pg_create": (ip, [ip, ip, ip, C.POINTER(vp)]),
+    "sship_pg_workspace_slice_bytes": (C.c_size_t, [ip, ip]),
+    "sship_pg_destroy": (None, [vp]),
+    "sship_pg_set_params": (ip, [vp, C.POINTER(PgParams)]),
+    "sship_pg_get_params": (ip, [vp, C.POINTER(PgParams)]),
+    "sship_pg_solve_batch_device": (ip, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, ip, vp, vp, vp, vp, vp]),
+    "sship_pg_solve_host": (ip, [vp, ip, vp, vp, vp, ip, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "sship_pg_odometry_from_poses_batch_device": (ip, [vp, vp, ip, vp, vp]),
+    "sship_pg_loops_from_pose_batch_device": (ip, [vp, vp, vp, vp, vp, ip, ip, dp, vp, vp, vp, vp, vp, vp]),
+    "sship_pg_bench": (ip, [vp, ip, C.POINTER(fp)]),
     "sship_desc_to_host": (ip, [vp, ip, ip, vp]),
     "sship_frontend_batch_device": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_bench_layer": (ip, [vp, ip, ip, ip, ip, ip, C.POINTER(fp), C.POINTER(C.c_double)]),

@@ -3271,6 +3271,238 @@ extern "C" int sship_ba_bench(sship_ba* ba, int iters, float* avg_ms) {
 }
 
 // ====================================================================================================
+// Pose graph: batched pose-graph optimiser (include/sship.h "Pose graph"; csrc/pg_kernels.hip)
+// ====================================================================================================
+constexpr int kPgMaxGraphs = 65535;
+struct sship_pg {
+  int N = 0, L = 0, max_graphs = 0;
+  sship_pg_params prm{0.02, 0.05, 1e-5, 1e5, 1e-5, 1e-5, 1e6, 100};
+  hipStream_t stream = nullptr;
+  DevBuf workspace;
+  DevBuf in1, out1;   // sship_pg_solve_host: one staged graph and its results
+  PinBuf h_in, h_out;
+  struct Last { const int32_t* n_nodes = nullptr; const double* pose0 = nullptr; const double* odom_z = nullptr; const double* odom_sigma = nullptr;
+                const int32_t* loop_ij = nullptr; const double* loop_z = nullptr; const double* loop_sigma = nullptr; const double* loop_k2 = nullptr;
+                const uint8_t* loop_enable = nullptr; int graphs = 0;
+                double* pose = nullptr; int32_t* stats = nullptr; double* cost = nullptr; double* chi2 = nullptr; } last;
+};
+static PgK pg_constants(const sship_pg* pg) {
+  PgK k;
+  k.odom_sigma_rot = pg->prm.odom_sigma_rot; k.odom_sigma_trans = pg->prm.odom_sigma_trans;
+  k.lambda0 = pg->prm.lambda0; k.lambda_max = pg->prm.lambda_max; k.abs_tol = pg->prm.abs_tol; k.rel_tol = pg->prm.rel_tol;
+  k.max_translation = pg->prm.max_translation; k.max_iterations = pg->prm.max_iterations;
+  return k;
+}
+// the staging of one graph, byte offsets: inputs pose0 | odom_z | odom_sigma | loop_z | loop_sigma | loop_k2 | loop_ij | n_nodes | enable
+struct PgStage { size_t pose0, oz, osg, lz, lsg, lk2, lij, nn, len, in_bytes, pose, cost, chi2, stats, out_bytes; };
+static PgStage pg_stage(int N, int L) {
+  PgStage s;
+  size_t o = 0;
+  s.pose0 = o; o += (size_t)N * 96;
+  s.oz = o; o += (size_t)(N - 1) * 96;
+  s.osg = o; o += (size_t)(N - 1) * 48;
+  s.lz = o; o += (size_t)L * 96;
+  s.lsg = o; o += (size_t)L * 48;
+  s.lk2 = o; o += (size_t)L * 8;
+  s.lij = o; o += (size_t)L * 8;
+  s.nn = o; o += 16;
+  s.len = o; o += ((size_t)L + 15) / 16 * 16;
+  s.in_bytes = o;
+  o = 0;
+  s.pose = o; o += (size_t)N * 96;
+  s.cost = o; o += 16;
+  s.chi2 = o; o += (size_t)L * 8;
+  s.stats = o; o += 16;
+  s.out_bytes = o;
+  return s;
+}
+extern "C" int sship_pg_create(int max_nodes, int max_loops, int max_graphs, sship_pg** out) {
+  if (!out) return fail(SSHIP_ERR_INVALID, "pg_create: null argument");
+  *out = nullptr;
+  if (max_nodes < 2 || max_nodes > kPgMaxNodes) return fail(SSHIP_ERR_INVALID, "pg_create: max_nodes must be in [2, 4096]");
+  if (max_loops < 0 || max_loops > kPgMaxLoops) return fail(SSHIP_ERR_INVALID, "pg_create: max_loops must be in [0, 128]");
+  if (max_graphs < 1 || max_graphs > kPgMaxGraphs) return fail(SSHIP_ERR_INVALID, "pg_create: max_graphs must be in [1, 65535]");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  std::unique_ptr<sship_pg, void (*)(sship_pg*)> pg(new sship_pg(), sship_pg_destroy);
+  pg->N = max_nodes; pg->L = max_loops; pg->max_graphs = max_graphs;
+  const PgStage st = pg_stage(max_nodes, max_loops);
+  SSHIP_HIP_CHECK(pg->workspace.ensure(pg_workspace_bytes(max_nodes, max_loops) * (size_t)std::min(max_graphs, kPgResident)));
+  SSHIP_HIP_CHECK(pg->in1.ensure(st.in_bytes));
+  SSHIP_HIP_CHECK(pg->out1.ensure(st.out_bytes));
+  SSHIP_HIP_CHECK(pg->h_in.ensure(st.in_bytes));
+  SSHIP_HIP_CHECK(pg->h_out.ensure(st.out_bytes));
+  SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&pg->stream, hipStreamDefault));
+  *out = pg.release();
+  return SSHIP_OK;
+}
+extern "C" size_t sship_pg_workspace_slice_bytes(int max_nodes, int max_loops) {
+  if (max_nodes < 2 || max_nodes > kPgMaxNodes || max_loops < 0 || max_loops > kPgMaxLoops) return 0;
+  return pg_workspace_bytes(max_nodes, max_loops);
+}
+extern "C" void sship_pg_destroy(sship_pg* pg) {
+  if (!pg) return;
+  bind_thread();
+  (void)hipDeviceSynchronize();
+  if (pg->stream) (void)hipStreamDestroy(pg->stream);
+  delete pg;
+}
+extern "C" int sship_pg_set_params(sship_pg* pg, const sship_pg_params* p) {
+  if (!pg || !p) return fail(SSHIP_ERR_INVALID, "pg_set_params: null argument");
+  const double all[7] = {p->odom_sigma_rot, p->odom_sigma_trans, p->lambda0, p->lambda_max, p->abs_tol, p->rel_tol, p->max_translation};
+  for (double v : all)
+    if (std::isnan(v)) return fail(SSHIP_ERR_INVALID, "pg_set_params: a parameter is NaN");
+  if (!(p->odom_sigma_rot > 0.0) || !(p->odom_sigma_trans > 0.0) || std::isinf(p->odom_sigma_rot) || std::isinf(p->odom_sigma_trans))
+    return fail(SSHIP_ERR_INVALID, "pg_set_params: odom_sigma_rot and odom_sigma_trans must be finite and > 0");
+  if (!(p->lambda0 > 0.0) || p->lambda_max < p->lambda0 || std::isinf(p->lambda_max))
+    return fail(SSHIP_ERR_INVALID, "pg_set_params: lambda0 must be > 0 and lambda_max finite and >= lambda0");
+  if (p->abs_tol < 0.0 || p->rel_tol < 0.0) return fail(SSHIP_ERR_INVALID, "pg_set_params: a tolerance is negative");
+  if (!(p->max_translation > 0.0) || std::isinf(p->max_translation))
+    return fail(SSHIP_ERR_INVALID, "pg_set_params: max_translation must be finite and > 0");
+  if (p->max_iterations < 1) return fail(SSHIP_ERR_INVALID, "pg_set_params: max_iterations must be >= 1");
+  pg->prm = *p;
+  return SSHIP_OK;
+}
+extern "C" int sship_pg_get_params(const sship_pg* pg, sship_pg_params* p) {
+  if (!pg || !p) return fail(SSHIP_ERR_INVALID, "pg_get_params: null argument");
+  *p = pg->prm;
+  return SSHIP_OK;
+}
+static int pg_launch(sship_pg* pg, const int32_t* n_nodes, const double* pose0, const double* odom_z, const double* odom_sigma,
+                     const int32_t* loop_ij, const double* loop_z, const double* loop_sigma, const double* loop_k2, const uint8_t* loop_enable,
+                     int graphs, double* pose, int32_t* stats, double* cost, double* chi2, hipStream_t s) {
+  sship_pg::Last& l = pg->last;
+  l.n_nodes = n_nodes; l.pose0 = pose0; l.odom_z = odom_z; l.odom_sigma = odom_sigma; l.loop_ij = loop_ij; l.loop_z = loop_z;
+  l.loop_sigma = loop_sigma; l.loop_k2 = loop_k2; l.loop_enable = loop_enable; l.graphs = graphs; l.pose = pose; l.stats = stats; l.cost = cost;
+  l.chi2 = chi2;
+  launch_pg_solve(n_nodes, pose0, odom_z, odom_sigma, loop_ij, loop_z, loop_sigma, loop_k2, loop_enable, pg->N, pg->L, graphs, pg_constants(pg),
+                  pg->workspace.p, pose, stats, cost, chi2, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  return SSHIP_OK;
+}
+extern "C" int sship_pg_solve_batch_device(sship_pg* pg, const int32_t* n_nodes, const double* pose0, const double* odom_z,
+                                           const double* odom_sigma, const int32_t* loop_ij, const double* loop_z, const double* loop_sigma,
+                                           const double* loop_k2, const uint8_t* loop_enable, int graphs, double* pose, int32_t* stats,
+                                           double* cost, double* loop_chi2, void* stream) {
+  if (!pg || !pose0 || !odom_z || !pose || !stats || !cost) return fail(SSHIP_ERR_INVALID, "pg_solve_batch_device: null argument");
+  const bool all_loops = loop_ij && loop_z && loop_sigma && loop_k2, no_loops = !loop_ij && !loop_z && !loop_sigma && !loop_k2 && !loop_enable;
+  if (!(all_loops || (no_loops && pg->L == 0)))
+    return fail(SSHIP_ERR_INVALID, "pg_solve_batch_device: the loop arrays may be NULL only when max_loops == 0, and then all of them");
+  if (graphs < 1 || graphs > pg->max_graphs) return fail(SSHIP_ERR_INVALID, "pg_solve_batch_device: graphs must be in [1, max_graphs]");
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  if (int rc = pg_launch(pg, n_nodes, pose0, odom_z, odom_sigma, loop_ij, loop_z, loop_sigma, loop_k2, loop_enable, graphs, pose, stats, cost,
+                         loop_chi2, s))
+    return rc;
+  g_timer.mark("pg_solve", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_pg_solve_host(sship_pg* pg, int n_nodes, const double* pose0, const double* odom_z, const double* odom_sigma, int n_loops,
+                                   const int32_t* loop_ij, const double* loop_z, const double* loop_sigma, const double* loop_k2,
+                                   double* pose_out, int32_t* stats_out, double* cost_out, double* loop_chi2_out) {
+  if (!pg || !stats_out || !cost_out) return fail(SSHIP_ERR_INVALID, "pg_solve_host: null argument");
+  if (n_nodes < 0 || n_nodes > pg->N) return fail(SSHIP_ERR_INVALID, "pg_solve_host: n_nodes must be in [0, max_nodes]");
+  if (n_loops < 0 || n_loops > pg->L) return fail(SSHIP_ERR_INVALID, "pg_solve_host: n_loops must be in [0, max_loops]");
+  if (n_nodes > 0 && (!pose0 || !pose_out)) return fail(SSHIP_ERR_INVALID, "pg_solve_host: null argument");
+  if (n_nodes > 1 && !odom_z) return fail(SSHIP_ERR_INVALID, "pg_solve_host: null argument");
+  if (n_loops > 0 && (!loop_ij || !loop_z || !loop_sigma || !loop_k2)) return fail(SSHIP_ERR_INVALID, "pg_solve_host: null argument");
+  bind_thread();
+  hipStream_t s = pg->stream;
+  const int N = pg->N, L = pg->L;
+  const PgStage st = pg_stage(N, L);
+  char* hin = static_cast<char*>(pg->h_in.p);
+  memset(hin, 0, st.in_bytes);   // rows past n_nodes / n_loops: zeros, and enable = 0
+  if (n_nodes > 0) memcpy(hin + st.pose0, pose0, (size_t)n_nodes * 96);
+  if (n_nodes > 1) {
+    memcpy(hin + st.oz, odom_z, (size_t)(n_nodes - 1) * 96);
+    if (odom_sigma) memcpy(hin + st.osg, odom_sigma, (size_t)(n_nodes - 1) * 48);
+  }
+  if (n_loops > 0) {
+    memcpy(hin + st.lz, loop_z, (size_t)n_loops * 96);
+    memcpy(hin + st.lsg, loop_sigma, (size_t)n_loops * 48);
+    memcpy(hin + st.lk2, loop_k2, (size_t)n_loops * 8);
+    memcpy(hin + st.lij, loop_ij, (size_t)n_loops * 8);
+    memset(hin + st.len, 1, (size_t)n_loops);
+  }
+  const int32_t nn = n_nodes;
+  memcpy(hin + st.nn, &nn, 4);
+  SSHIP_HIP_CHECK(hipMemcpyAsync(pg->in1.p, hin, st.in_bytes, hipMemcpyHostToDevice, s));
+  char* din = static_cast<char*>(pg->in1.p);
+  char* dout = static_cast<char*>(pg->out1.p);
+  auto dd = [&](size_t o) { return reinterpret_cast<const double*>(din + o); };
+  if (int rc = pg_launch(pg, reinterpret_cast<const int32_t*>(din + st.nn), dd(st.pose0), dd(st.oz), odom_sigma ? dd(st.osg) : nullptr,
+                         L ? reinterpret_cast<const int32_t*>(din + st.lij) : nullptr, L ? dd(st.lz) : nullptr, L ? dd(st.lsg) : nullptr,
+                         L ? dd(st.lk2) : nullptr, L ? reinterpret_cast<const uint8_t*>(din + st.len) : nullptr, 1,
+                         reinterpret_cast<double*>(dout + st.pose), reinterpret_cast<int32_t*>(dout + st.stats),
+                         reinterpret_cast<double*>(dout + st.cost), reinterpret_cast<double*>(dout + st.chi2), s))
+    return rc;
+  char* hout = static_cast<char*>(pg->h_out.p);
+  SSHIP_HIP_CHECK(hipMemcpyAsync(hout, dout, st.out_bytes, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipStreamSynchronize(s));
+  if (n_nodes > 0) memcpy(pose_out, hout + st.pose, (size_t)n_nodes * 96);
+  memcpy(cost_out, hout + st.cost, 16);
+  memcpy(stats_out, hout + st.stats, 16);
+  if (loop_chi2_out && n_loops > 0) memcpy(loop_chi2_out, hout + st.chi2, (size_t)n_loops * 8);
+  return SSHIP_OK;
+}
+extern "C" int sship_pg_odometry_from_poses_batch_device(const sship_pg* pg, const double* pose, int graphs, double* odom_z, void* stream) {
+  if (!pg || !pose || !odom_z) return fail(SSHIP_ERR_INVALID, "pg_odometry_from_poses_batch_device: null argument");
+  if (graphs < 1 || graphs > pg->max_graphs) return fail(SSHIP_ERR_INVALID, "pg_odometry_from_poses_batch_device: graphs must be in [1, max_graphs]");
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  launch_pg_odometry(pose, pg->N, graphs, odom_z, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("pg_odometry", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_pg_loops_from_pose_batch_device(const sship_pg* pg, const int32_t* from, const int32_t* to, const double* pose,
+                                                     const int32_t* stats, int graphs, int min_inliers, double noise_base, int32_t* loop_ij,
+                                                     double* loop_z, double* loop_sigma, double* loop_k2, uint8_t* loop_enable, void* stream) {
+  if (!pg || !from || !to || !pose || !stats || !loop_ij || !loop_z || !loop_sigma || !loop_k2 || !loop_enable)
+    return fail(SSHIP_ERR_INVALID, "pg_loops_from_pose_batch_device: null argument");
+  if (pg->L < 1) return fail(SSHIP_ERR_INVALID, "pg_loops_from_pose_batch_device: the handle has max_loops == 0");
+  if (graphs < 1 || graphs > pg->max_graphs) return fail(SSHIP_ERR_INVALID, "pg_loops_from_pose_batch_device: graphs must be in [1, max_graphs]");
+  if (min_inliers < 1) return fail(SSHIP_ERR_INVALID, "pg_loops_from_pose_batch_device: min_inliers must be >= 1");
+  if (!std::isfinite(noise_base) || !(noise_base > 0.0)) return fail(SSHIP_ERR_INVALID, "pg_loops_from_pose_batch_device: noise_base must be finite and > 0");
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  launch_pg_loops(from, to, pose, stats, graphs * pg->L, min_inliers, noise_base, loop_ij, loop_z, loop_sigma, loop_k2, loop_enable, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("pg_loops", s);
+  return SSHIP_OK;
+}
+// Measurement hook (include/sship.h): the last solve call's launch re-run `iters` times on the handle's stream.
+extern "C" int sship_pg_bench(sship_pg* pg, int iters, float* avg_ms) {
+  if (!pg || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "pg_bench: bad arguments");
+  if (pg->last.graphs <= 0) return fail(SSHIP_ERR_INVALID, "pg_bench: run a solve on this handle first");
+  bind_thread();
+  hipStream_t s = pg->stream;
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
+  const sship_pg::Last& l = pg->last;
+  const PgK k = pg_constants(pg);
+  auto run = [&]() -> hipError_t {
+    launch_pg_solve(l.n_nodes, l.pose0, l.odom_z, l.odom_sigma, l.loop_ij, l.loop_z, l.loop_sigma, l.loop_k2, l.loop_enable, pg->N, pg->L, l.graphs,
+                    k, pg->workspace.p, l.pose, l.stats, l.cost, l.chi2, s);
+    return hipGetLastError();
+  };
+  SSHIP_HIP_CHECK(run());  // warm
+  EventPair ev;            // destroyed on every return
+  SSHIP_HIP_CHECK(hipEventCreate(&ev.e0));
+  SSHIP_HIP_CHECK(hipEventCreate(&ev.e1));
+  SSHIP_HIP_CHECK(hipEventRecord(ev.e0, s));
+  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
+  SSHIP_HIP_CHECK(hipEventRecord(ev.e1, s));
+  SSHIP_HIP_CHECK(hipEventSynchronize(ev.e1));
+  float ms = 0.f;
+  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  *avg_ms = ms / iters;
+  return SSHIP_OK;
+}
+
+// ====================================================================================================
 // fused front-end step: SuperPoint(batch 2P) + select + gather + LightGlue(P)
 // ====================================================================================================
 extern "C" int sship_frontend_batch_device(sship_sp* sp, sship_lg* lg, const uint8_t* imgs, int pairs, int h, int w,

@@ -275,4 +275,26 @@ void launch_ba_solve(const float* meas, const int32_t* track, const int32_t* n_k
 void launch_ba_tracks(const uint8_t* has_depth, const int32_t* matches, const int32_t* n, const int32_t* n_kf, int max_keyframes, int max_obs,
                       int windows, int32_t* track, hipStream_t s);
 
+// ---- pg_kernels.hip : batched pose-graph optimiser (sship_pg_*) ----
+constexpr int kPgMaxNodes = 4096;
+constexpr int kPgMaxLoops = 128;
+constexpr int kPgResident = 256;    // workgroups of a solve launch (they walk the graphs), each with a workspace slice
+struct PgK {                        // the rule's constants, by value
+  double odom_sigma_rot, odom_sigma_trans;
+  double lambda0, lambda_max, abs_tol, rel_tol, max_translation;
+  int max_iterations;
+};
+// bytes of one workspace slice (include/sship.h states the formula); the handle holds min(max_graphs, kPgResident) of them
+size_t pg_workspace_bytes(int max_nodes, int max_loops);
+// one workgroup per graph, the LM loop and the rejection loop in the launch.  n_nodes / odom_sigma / loop_enable / loop_chi2 may be null,
+// and so may all loop arrays when max_loops == 0; every output entry is written.
+void launch_pg_solve(const int32_t* n_nodes, const double* pose0, const double* odom_z, const double* odom_sigma, const int32_t* loop_ij,
+                     const double* loop_z, const double* loop_sigma, const double* loop_k2, const uint8_t* loop_enable, int max_nodes,
+                     int max_loops, int graphs, const PgK& k, void* workspace, double* pose, int32_t* stats, double* cost, double* loop_chi2,
+                     hipStream_t s);
+void launch_pg_odometry(const double* pose, int max_nodes, int graphs, double* odom_z, hipStream_t s);
+void launch_pg_loops(const int32_t* from, const int32_t* to, const double* pose, const int32_t* stats, int pairs, int min_inliers,
+                     double noise_base, int32_t* loop_ij, double* loop_z, double* loop_sigma, double* loop_k2, uint8_t* loop_enable,
+                     hipStream_t s);
+
 }  // namespace sship
