@@ -865,6 +865,101 @@ int sship_pg_loops_from_pose_batch_device(const sship_pg* pg, const int32_t* fro
 int sship_pg_bench(sship_pg* pg, int iters, float* avg_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * Rectification - the two cv::remap calls of the EuRoC runner (examples/stereo/euroc.cc:88-133,176-177) as a device stage, and the maps
+ * cv::initUndistortRectifyMap builds for them.  The rule is OpenCV's, restated here; OpenCV is not a dependency and equality with cv::remap
+ * is the intent of the rule, NOT something the tests check (they check the library against tests/_rect_ref.py, which restates this text).
+ *
+ * Map construction (cv::initUndistortRectifyMap, m1type = CV_32F): pure host, fp64, this operation order.
+ *   K 3x3 row-major (fx = K[0], cx = K[2], fy = K[4], cy = K[5]);  D = n_dist coefficients of k1 k2 p1 p2 k3 k4 k5 k6, missing ones 0,
+ *   n_dist in {0, 4, 5, 8};  R 3x3 (NULL = identity);  Pnew 3x3 (the left block of P).
+ *   A = Pnew R with A[i][j] = (Pnew[i][0] R[0][j] + Pnew[i][1] R[1][j]) + Pnew[i][2] R[2][j];  iR = adj(A) / det(A) by cofactors,
+ *   det = (A00 c00 + A01 c01) + A02 c02.  det == 0 or a non-finite iR -> SSHIP_ERR_INVALID.
+ *   For the destination pixel (u, v):  X = (iR00 u + iR01 v) + iR02, Y and W alike from rows 1 and 2;  x = X / W, y = Y / W;
+ *   x2 = x x, y2 = y y, r2 = x2 + y2, xy2 = (2 x) y;
+ *   kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2);
+ *   xd = (x kr + p1 xy2) + p2 (r2 + 2 x2);    yd = (y kr + p1 (r2 + 2 y2)) + p2 xy2;
+ *   map_x = fx xd + cx, map_y = fy yd + cy, each rounded once to fp32.  Tables are [dst_h, dst_w] row-major.
+ *
+ * Remap (cv::remap, u8, INTER_LINEAR, BORDER_CONSTANT 0, OpenCV's fixed-point form), per destination pixel:
+ *   sx = rint(map_x * 32), sy = rint(map_y * 32)        the product is exact in fp32; ties to even
+ *   ix = sx >> 5, iy = sy >> 5, ax = sx & 31, ay = sy & 31
+ *   acc = (32-ax)(32-ay) S(iy,ix) + ax (32-ay) S(iy,ix+1) + (32-ax) ay S(iy+1,ix) + ax ay S(iy+1,ix+1)     a tap outside the source is 0
+ *   dst = (acc + 512) >> 10
+ * All of it integer arithmetic: the result does not depend on summation order, batch position or path.
+ * Our additions: a map entry that is not finite, or has |map * 32| > 2^20, makes its pixel 0.  That is decided when the table is built,
+ * on the host; the kernel never sees such an entry.
+ *
+ * sship_rect_fixed_table is the table of the rule, pure host: ix / iy i32, frac u16 = ax | ay << 5; a degenerate entry is (0, 0, 0xFFFF).
+ * The handle's device table (sship_rect_read_table) is that table after set_maps has resolved the border: a pixel none of whose taps is
+ * both inside the source and of non-zero weight - degenerate ones included - reads (-2, -2, 0); every other pixel reads as the rule states.
+ *
+ * The handle: `cameras` (1 or 2) tables for one source and one destination size (each axis in [1, 4096]).  sship_rect_set_maps takes
+ * host fp32 tables (what a holder of cv::Mat maps has), builds the fixed-point table and one source box per 64 x 16 destination tile
+ * on the host, and uploads them (it synchronises the device first: do not call it with a remap of this handle in flight).  A tile whose
+ * box fits 16 KiB of LDS is remapped from a staged copy of the box; any other tile (a transpose, a strong minification) reads its taps
+ * from global memory.  Same arithmetic, same bits.  sship_rect_tile_paths reports how many tiles of a camera took each path.
+ * sship_rect_set_camera = sship_rect_build_maps + sship_rect_set_maps.
+ *
+ * sship_rect_remap_batch_device: src_dev [images, src_h, src_stride] u8 (src_stride in bytes, >= src_w; no alignment is required of the
+ * pointer or the stride), dst_dev [images, dst_h, dst_w] contiguous u8.  Image i uses camera i % cameras: with cameras = 2 the output is
+ * the L0, R0, L1, R1, ... layout sship_frontend_batch_device takes.  One launch, asynchronous on `stream`, no host synchronisation.
+ * A camera the batch uses that has no maps -> SSHIP_ERR_INVALID.  sship_rect_remap_host: one image from host arrays through the handle's
+ * own stream (dst is [dst_h, dst_w] contiguous), the drop-in for one cv::remap call.
+ * sship_rect_bench: `images` synthetic images through the handle's tables, `iters` launches timed with hipEvents; path = SSHIP_RECT_PATH_TILE
+ * (each tile on the path set_maps chose) or SSHIP_RECT_PATH_DIRECT (every tile from global memory).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sship_rect sship_rect;
+#define SSHIP_RECT_PATH_TILE 0
+#define SSHIP_RECT_PATH_DIRECT 1
+int sship_rect_build_maps(const double* K, const double* D, int n_dist, const double* R, const double* Pnew, int dst_w, int dst_h,
+                          float* map_x, float* map_y);
+int sship_rect_fixed_table(const float* map_x, const float* map_y, size_t count, int32_t* ix, int32_t* iy, uint16_t* frac);
+int sship_rect_create(int src_w, int src_h, int dst_w, int dst_h, int cameras, sship_rect** out);
+void sship_rect_destroy(sship_rect* rect);
+int sship_rect_set_maps(sship_rect* rect, int camera, const float* map_x, const float* map_y);
+int sship_rect_set_camera(sship_rect* rect, int camera, const double* K, const double* D, int n_dist, const double* R, const double* Pnew);
+int sship_rect_read_table(sship_rect* rect, int camera, int32_t* ix, int32_t* iy, uint16_t* frac);
+int sship_rect_tile_paths(const sship_rect* rect, int camera, int* staged, int* direct);
+int sship_rect_remap_batch_device(sship_rect* rect, const uint8_t* src_dev, int images, int src_stride, uint8_t* dst_dev, void* stream);
+int sship_rect_remap_host(sship_rect* rect, int camera, const uint8_t* src, int src_stride, uint8_t* dst);
+int sship_rect_bench(sship_rect* rect, int images, int path, int iters, float* avg_ms);
+
+/* ------------------------------------------------------------------------------------------------
+ * RGB-D association - the per-keypoint loop of RgbdFrontEnd::process (src/RgbdFrontEnd.cc:27-56) as a device stage.
+ * kp_dev [frames, max_keypoints, 3] f32 (x, y, score) raw keypoints as the extractor writes them, n_dev [frames] i32 (clamped to
+ * [0, max_keypoints] on the device), depth_dev [frames, h, depth_stride] with depth_stride in bytes (a multiple of the sample size),
+ * depth_type SSHIP_DEPTH_U16 or SSHIP_DEPTH_F32.  Per keypoint (u, v):
+ *   hasDist = any of dist[0..7] (k1 k2 p1 p2 k3 k4 k5 k6) is non-zero.
+ *   hasDist: cv::undistortPoints' fixed 5 iterations, fp64:  x0 = (u - cx) / fx, y0 = (v - cy) / fy, x = x0, y = y0;  each iteration
+ *     r2 = x x + y y;  ic = (1 + ((k6 r2 + k5) r2 + k4) r2) / (1 + ((k3 r2 + k2) r2 + k1) r2);  ic < 0: restore (x0, y0) and stop;
+ *     x = (x0 - (2 p1 x y + p2 (r2 + 2 x x))) ic,  y = (y0 - (p1 (r2 + 2 y y) + 2 p2 x y)) ic   (both from the x, y before the step);
+ *     u' = fx x + cx, v' = fy y + cy, rounded to fp32.    Not hasDist: (u', v') are the keypoint's own bits.
+ *   Depth is sampled at (lround(u), lround(v)) of the RAW keypoint - half away from zero; a sample outside the image, or a NaN coordinate, is 0.
+ *   Z = d / depth_factor in fp64;   has_depth = (Z > 0 && Z < max_depth), this positive form: a NaN depth gives none.
+ *   stereo = (u', has_depth ? fp32(u' - bf / Z) : quiet NaN, v')       the subtraction and the division in fp64
+ * Rows >= n are (0, NaN, 0) / 0 and every entry is written: the output convention of sship_stereo_associate_batch_device, so the result
+ * feeds sship_pose_obs_from_matches_batch_device and sship_ba_tracks_from_matches_batch_device unchanged.  kp_undist_dev (optional, NULL =
+ * not wanted) [frames, max_keypoints, 3] = (u', v', score), rows >= n zero.  One launch, asynchronous on `stream`.
+ * frames >= 1, max_keypoints in [1, 4096], h, w in [1, 16384]; fx, fy, depth_factor finite and > 0; max_depth not NaN.
+ * ---------------------------------------------------------------------------------------------- */
+#define SSHIP_DEPTH_U16 0
+#define SSHIP_DEPTH_F32 1
+typedef struct sship_rgbd_params {
+  double fx, fy, cx, cy;
+  double dist[8];       /* k1 k2 p1 p2 k3 k4 k5 k6 */
+  double bf;            /* fx * baseline (Camera.bf) */
+  double depth_factor;  /* DepthMapFactor */
+  double max_depth;
+} sship_rgbd_params;
+int sship_rgbd_associate_batch_device(const float* kp_dev, const int* n_dev, int frames, int max_keypoints, const void* depth_dev,
+                                      int depth_type, int h, int w, int depth_stride, const sship_rgbd_params* params,
+                                      float* kp_undist_dev, float* stereo_dev, uint8_t* has_depth_dev, void* stream);
+/* One frame from host arrays (the loop of RgbdFrontEnd::process as it stands): keypoints[i * kp_stride + {0, 1}] = (x, y), n in [0, 4096]
+ * (0: nothing is touched), depth [h, depth_stride bytes]; kp_undist [n, 2], stereo [n, 3], has_depth [n].  Synchronous. */
+int sship_rgbd_associate_host(const float* keypoints, int kp_stride, int n, const void* depth, int depth_type, int h, int w, int depth_stride,
+                              const sship_rgbd_params* params, float* kp_undist, float* stereo, uint8_t* has_depth);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused front-end step: what StereoFrontEnd::process asks of the two interfaces per frame
  * (src/StereoFrontEnd.cc:14,33): SuperPoint on L and R (one batch) + gather x2 + one LightGlue match,
  * for `pairs` stereo pairs at once, device-resident, no host synchronisation.  imgs_dev is

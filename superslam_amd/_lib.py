@@ -62,6 +62,11 @@ class PgParams(C.Structure):
                 ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("max_translation", C.c_double), ("max_iterations", C.c_int)]
 
 
+class RgbdParams(C.Structure):
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("dist", C.c_double * 8),
+                ("bf", C.c_double), ("depth_factor", C.c_double), ("max_depth", C.c_double)]
+
+
 _lib = None
 vp, ip, fp, dp = C.c_void_p, C.c_int, C.c_float, C.c_double
 _SIGS = {
@@ -185,6 +190,19 @@ _SIGS = {
     "sship_pg_odometry_from_poses_batch_device": (ip, [vp, vp, ip, vp, vp]),
     "sship_pg_loops_from_pose_batch_device": (ip, [vp, vp, vp, vp, vp, ip, ip, dp, vp, vp, vp, vp, vp, vp]),
     "sship_pg_bench": (ip, [vp, ip, C.POINTER(fp)]),
+    "sship_rect_build_maps": (ip, [vp, vp, ip, vp, vp, ip, ip, vp, vp]),
+    "sship_rect_fixed_table": (ip, [vp, vp, C.c_size_t, vp, vp, vp]),
+    "sship_rect_create": (ip, [ip, ip, ip, ip, ip, C.POINTER(vp)]),
+    "sship_rect_destroy": (None, [vp]),
+    "sship_rect_set_maps": (ip, [vp, ip, vp, vp]),
+    "sship_rect_set_camera": (ip, [vp, ip, vp, vp, ip, vp, vp]),
+    "sship_rect_read_table": (ip, [vp, ip, vp, vp, vp]),
+    "sship_rect_tile_paths": (ip, [vp, ip, C.POINTER(ip), C.POINTER(ip)]),
+    "sship_rect_remap_batch_device": (ip, [vp, vp, ip, ip, vp, vp]),
+    "sship_rect_remap_host": (ip, [vp, ip, vp, ip, vp]),
+    "sship_rect_bench": (ip, [vp, ip, ip, ip, C.POINTER(fp)]),
+    "sship_rgbd_associate_batch_device": (ip, [vp, vp, ip, ip, vp, ip, ip, ip, ip, C.POINTER(RgbdParams), vp, vp, vp, vp]),
+    "sship_rgbd_associate_host": (ip, [vp, ip, ip, vp, ip, ip, ip, ip, C.POINTER(RgbdParams), vp, vp, vp]),
     "sship_desc_to_host": (ip, [vp, ip, ip, vp]),
     "sship_frontend_batch_device": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_bench_layer": (ip, [vp, ip, ip, ip, ip, ip, C.POINTER(fp), C.POINTER(C.c_double)]),

@@ -3503,6 +3503,242 @@ extern "C" int sship_pg_bench(sship_pg* pg, int iters, float* avg_ms) {
 }
 
 // ====================================================================================================
+// rectification remap (sship_rect_*) and RGB-D association
+// ====================================================================================================
+struct sship_rect {
+  int src_w = 0, src_h = 0, dst_w = 0, dst_h = 0, cameras = 0, tiles = 0;   // tiles per camera
+  bool have[2] = {false, false};
+  int n_staged[2] = {0, 0}, n_direct[2] = {0, 0};
+  hipStream_t stream = nullptr;
+  DevBuf table, tile_boxes;   // [cameras][dst_h * dst_w] RectEntry, [cameras][tiles] RectTile
+  DevBuf src1, dst1;          // sship_rect_remap_host: one staged image and its result
+  DevBuf bench_src, bench_dst;
+  size_t px() const { return (size_t)dst_w * dst_h; }
+};
+static int rect_check_camera(const double* K, const double* D, int n_dist, const double* Pnew, const char* who) {
+  if (!K || !Pnew) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  if (n_dist != 0 && n_dist != 4 && n_dist != 5 && n_dist != 8) return fail(SSHIP_ERR_INVALID, std::string(who) + ": n_dist must be 0, 4, 5 or 8");
+  if (n_dist > 0 && !D) return fail(SSHIP_ERR_INVALID, std::string(who) + ": D is NULL with n_dist > 0");
+  for (int i = 0; i < 9; ++i)
+    if (!std::isfinite(K[i]) || !std::isfinite(Pnew[i])) return fail(SSHIP_ERR_INVALID, std::string(who) + ": K and Pnew must be finite");
+  for (int i = 0; i < n_dist; ++i)
+    if (!std::isfinite(D[i])) return fail(SSHIP_ERR_INVALID, std::string(who) + ": D must be finite");
+  if (!(K[0] > 0.0) || !(K[4] > 0.0)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": fx and fy of K must be > 0");
+  return SSHIP_OK;
+}
+static bool rect_size_ok(int w, int h) { return w >= 1 && h >= 1 && w <= kRectMaxSize && h <= kRectMaxSize; }
+extern "C" int sship_rect_build_maps(const double* K, const double* D, int n_dist, const double* R, const double* Pnew, int dst_w, int dst_h,
+                                     float* map_x, float* map_y) {
+  if (int rc = rect_check_camera(K, D, n_dist, Pnew, "rect_build_maps")) return rc;
+  if (!map_x || !map_y) return fail(SSHIP_ERR_INVALID, "rect_build_maps: null argument");
+  if (!rect_size_ok(dst_w, dst_h)) return fail(SSHIP_ERR_INVALID, "rect_build_maps: dst_w and dst_h must be in [1, 4096]");
+  if (R)
+    for (int i = 0; i < 9; ++i)
+      if (!std::isfinite(R[i])) return fail(SSHIP_ERR_INVALID, "rect_build_maps: R must be finite");
+  if (rect_build_maps(K, D, n_dist, R, Pnew, dst_w, dst_h, map_x, map_y)) return fail(SSHIP_ERR_INVALID, "rect_build_maps: Pnew * R is singular");
+  return SSHIP_OK;
+}
+extern "C" int sship_rect_fixed_table(const float* map_x, const float* map_y, size_t count, int32_t* ix, int32_t* iy, uint16_t* frac) {
+  if (!map_x || !map_y || !ix || !iy || !frac) return fail(SSHIP_ERR_INVALID, "rect_fixed_table: null argument");
+  rect_fixed_table(map_x, map_y, count, ix, iy, frac);
+  return SSHIP_OK;
+}
+extern "C" int sship_rect_create(int src_w, int src_h, int dst_w, int dst_h, int cameras, sship_rect** out) {
+  if (!out) return fail(SSHIP_ERR_INVALID, "rect_create: null argument");
+  *out = nullptr;
+  if (!rect_size_ok(src_w, src_h)) return fail(SSHIP_ERR_INVALID, "rect_create: src_w and src_h must be in [1, 4096]");
+  if (!rect_size_ok(dst_w, dst_h)) return fail(SSHIP_ERR_INVALID, "rect_create: dst_w and dst_h must be in [1, 4096]");
+  if (cameras != 1 && cameras != 2) return fail(SSHIP_ERR_INVALID, "rect_create: cameras must be 1 or 2");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  std::unique_ptr<sship_rect, void (*)(sship_rect*)> r(new sship_rect(), sship_rect_destroy);
+  r->src_w = src_w; r->src_h = src_h; r->dst_w = dst_w; r->dst_h = dst_h; r->cameras = cameras;
+  r->tiles = ((dst_w + kRectTileW - 1) / kRectTileW) * ((dst_h + kRectTileH - 1) / kRectTileH);
+  SSHIP_HIP_CHECK(r->table.ensure(r->px() * cameras * sizeof(RectEntry)));
+  SSHIP_HIP_CHECK(r->tile_boxes.ensure((size_t)r->tiles * cameras * sizeof(RectTile)));
+  SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&r->stream, hipStreamDefault));
+  *out = r.release();
+  return SSHIP_OK;
+}
+extern "C" void sship_rect_destroy(sship_rect* rect) {
+  if (!rect) return;
+  bind_thread();
+  (void)hipDeviceSynchronize();
+  if (rect->stream) (void)hipStreamDestroy(rect->stream);
+  delete rect;
+}
+extern "C" int sship_rect_set_maps(sship_rect* rect, int camera, const float* map_x, const float* map_y) {
+  if (!rect || !map_x || !map_y) return fail(SSHIP_ERR_INVALID, "rect_set_maps: null argument");
+  if (camera < 0 || camera >= rect->cameras) return fail(SSHIP_ERR_INVALID, "rect_set_maps: camera must be in [0, cameras)");
+  bind_thread();
+  std::vector<RectEntry> table;
+  std::vector<RectTile> tiles;
+  rect_device_table(map_x, map_y, rect->src_w, rect->src_h, rect->dst_w, rect->dst_h, table, tiles, &rect->n_staged[camera], &rect->n_direct[camera]);
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());   // a remap of an earlier table may still be running
+  SSHIP_HIP_CHECK(hipMemcpy(rect->table.as<RectEntry>() + rect->px() * camera, table.data(), table.size() * sizeof(RectEntry), hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(rect->tile_boxes.as<RectTile>() + (size_t)rect->tiles * camera, tiles.data(), tiles.size() * sizeof(RectTile), hipMemcpyHostToDevice));
+  rect->have[camera] = true;
+  return SSHIP_OK;
+}
+extern "C" int sship_rect_set_camera(sship_rect* rect, int camera, const double* K, const double* D, int n_dist, const double* R, const double* Pnew) {
+  if (!rect) return fail(SSHIP_ERR_INVALID, "rect_set_camera: null argument");
+  if (camera < 0 || camera >= rect->cameras) return fail(SSHIP_ERR_INVALID, "rect_set_camera: camera must be in [0, cameras)");
+  std::vector<float> mx(rect->px()), my(rect->px());
+  if (int rc = sship_rect_build_maps(K, D, n_dist, R, Pnew, rect->dst_w, rect->dst_h, mx.data(), my.data())) return rc;
+  return sship_rect_set_maps(rect, camera, mx.data(), my.data());
+}
+extern "C" int sship_rect_read_table(sship_rect* rect, int camera, int32_t* ix, int32_t* iy, uint16_t* frac) {
+  if (!rect || !ix || !iy || !frac) return fail(SSHIP_ERR_INVALID, "rect_read_table: null argument");
+  if (camera < 0 || camera >= rect->cameras) return fail(SSHIP_ERR_INVALID, "rect_read_table: camera must be in [0, cameras)");
+  if (!rect->have[camera]) return fail(SSHIP_ERR_INVALID, "rect_read_table: the camera has no maps");
+  bind_thread();
+  std::vector<RectEntry> table(rect->px());
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());
+  SSHIP_HIP_CHECK(hipMemcpy(table.data(), rect->table.as<RectEntry>() + rect->px() * camera, table.size() * sizeof(RectEntry), hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < table.size(); ++i) { ix[i] = table[i].ix; iy[i] = table[i].iy; frac[i] = (uint16_t)(table[i].frac_mask & kRectFracMask); }
+  return SSHIP_OK;
+}
+extern "C" int sship_rect_tile_paths(const sship_rect* rect, int camera, int* staged, int* direct) {
+  if (!rect || !staged || !direct) return fail(SSHIP_ERR_INVALID, "rect_tile_paths: null argument");
+  if (camera < 0 || camera >= rect->cameras) return fail(SSHIP_ERR_INVALID, "rect_tile_paths: camera must be in [0, cameras)");
+  if (!rect->have[camera]) return fail(SSHIP_ERR_INVALID, "rect_tile_paths: the camera has no maps");
+  *staged = rect->n_staged[camera]; *direct = rect->n_direct[camera];
+  return SSHIP_OK;
+}
+// the cameras images [0, images) starting at camera cam0 use must all have maps
+static int rect_check_maps(const sship_rect* rect, int cam0, int images, const char* who) {
+  for (int i = 0; i < std::min(images, rect->cameras); ++i)
+    if (!rect->have[(cam0 + i) % rect->cameras]) return fail(SSHIP_ERR_INVALID, std::string(who) + ": a camera the call uses has no maps (sship_rect_set_maps)");
+  return SSHIP_OK;
+}
+extern "C" int sship_rect_remap_batch_device(sship_rect* rect, const uint8_t* src, int images, int src_stride, uint8_t* dst, void* stream) {
+  if (!rect || !src || !dst) return fail(SSHIP_ERR_INVALID, "rect_remap_batch_device: null argument");
+  if (images <= 0 || images > (1 << 20)) return fail(SSHIP_ERR_INVALID, "rect_remap_batch_device: images must be in [1, 1048576]");
+  if (src_stride < rect->src_w || src_stride > (1 << 20)) return fail(SSHIP_ERR_INVALID, "rect_remap_batch_device: src_stride must be in [src_w, 1048576]");
+  if (int rc = rect_check_maps(rect, 0, images, "rect_remap_batch_device")) return rc;
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  launch_rect_remap(src, rect->src_h, src_stride, dst, rect->dst_w, rect->dst_h, rect->table.p, rect->tile_boxes.as<RectTile>(), rect->cameras, 0,
+                    images, 0, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("rect_remap", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_rect_remap_host(sship_rect* rect, int camera, const uint8_t* src, int src_stride, uint8_t* dst) {
+  if (!rect || !src || !dst) return fail(SSHIP_ERR_INVALID, "rect_remap_host: null argument");
+  if (camera < 0 || camera >= rect->cameras) return fail(SSHIP_ERR_INVALID, "rect_remap_host: camera must be in [0, cameras)");
+  if (src_stride < rect->src_w) return fail(SSHIP_ERR_INVALID, "rect_remap_host: src_stride must be >= src_w");
+  if (int rc = rect_check_maps(rect, camera, 1, "rect_remap_host")) return rc;
+  bind_thread();
+  hipStream_t s = rect->stream;
+  const int pitch = (rect->src_w + 3) & ~3;
+  SSHIP_HIP_CHECK(rect->src1.ensure((size_t)pitch * rect->src_h));
+  SSHIP_HIP_CHECK(rect->dst1.ensure(rect->px()));
+  SSHIP_HIP_CHECK(hipMemcpy2DAsync(rect->src1.p, pitch, src, src_stride, rect->src_w, rect->src_h, hipMemcpyHostToDevice, s));
+  launch_rect_remap(rect->src1.as<uint8_t>(), rect->src_h, pitch, rect->dst1.as<uint8_t>(), rect->dst_w, rect->dst_h, rect->table.p,
+                    rect->tile_boxes.as<RectTile>(), rect->cameras, camera, 1, 0, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  SSHIP_HIP_CHECK(hipMemcpyAsync(dst, rect->dst1.p, rect->px(), hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipStreamSynchronize(s));
+  return SSHIP_OK;
+}
+extern "C" int sship_rect_bench(sship_rect* rect, int images, int path, int iters, float* avg_ms) {
+  if (!rect || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "rect_bench: bad arguments");
+  if (images <= 0 || images > 65536) return fail(SSHIP_ERR_INVALID, "rect_bench: images must be in [1, 65536]");
+  if (path != SSHIP_RECT_PATH_TILE && path != SSHIP_RECT_PATH_DIRECT) return fail(SSHIP_ERR_INVALID, "rect_bench: path must be 0 (tile) or 1 (direct)");
+  if (int rc = rect_check_maps(rect, 0, images, "rect_bench")) return rc;
+  bind_thread();
+  hipStream_t s = rect->stream;
+  const size_t sb = (size_t)rect->src_w * rect->src_h * images, db = rect->px() * images;
+  SSHIP_HIP_CHECK(rect->bench_src.ensure(sb));
+  SSHIP_HIP_CHECK(rect->bench_dst.ensure(db));
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());
+  SSHIP_HIP_CHECK(hipMemsetAsync(rect->bench_src.p, 0x5a, sb, s));
+  auto run = [&]() -> hipError_t {
+    launch_rect_remap(rect->bench_src.as<uint8_t>(), rect->src_h, rect->src_w, rect->bench_dst.as<uint8_t>(), rect->dst_w, rect->dst_h,
+                      rect->table.p, rect->tile_boxes.as<RectTile>(), rect->cameras, 0, images, path == SSHIP_RECT_PATH_DIRECT ? 1 : 0, s);
+    return hipGetLastError();
+  };
+  SSHIP_HIP_CHECK(run());  // warm
+  EventPair ev;            // destroyed on every return
+  SSHIP_HIP_CHECK(hipEventCreate(&ev.e0));
+  SSHIP_HIP_CHECK(hipEventCreate(&ev.e1));
+  SSHIP_HIP_CHECK(hipEventRecord(ev.e0, s));
+  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
+  SSHIP_HIP_CHECK(hipEventRecord(ev.e1, s));
+  SSHIP_HIP_CHECK(hipEventSynchronize(ev.e1));
+  float ms = 0.f;
+  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  *avg_ms = ms / iters;
+  return SSHIP_OK;
+}
+// the checks both RGB-D entries share; fills the kernel's constants
+static int rgbd_check(int depth_type, int h, int w, int depth_stride, const sship_rgbd_params* p, RgbdK* c, const char* who) {
+  if (depth_type != SSHIP_DEPTH_U16 && depth_type != SSHIP_DEPTH_F32)
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": depth_type must be 0 (u16) or 1 (f32)");
+  const int es = depth_type == SSHIP_DEPTH_F32 ? 4 : 2;
+  if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, std::string(who) + ": h and w must be in [1, 16384]");
+  if (depth_stride < w * es || depth_stride % es) return fail(SSHIP_ERR_INVALID, std::string(who) + ": depth_stride (bytes) must be >= the row and a multiple of the sample size");
+  if (!(p->fx > 0.0) || !(p->fy > 0.0) || !std::isfinite(p->fx) || !std::isfinite(p->fy)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": fx and fy must be finite and > 0");
+  if (!(p->depth_factor > 0.0) || !std::isfinite(p->depth_factor)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": depth_factor must be finite and > 0");
+  if (!std::isfinite(p->cx) || !std::isfinite(p->cy) || !std::isfinite(p->bf) || std::isnan(p->max_depth))
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": cx, cy and bf must be finite and max_depth not NaN");
+  c->fx = p->fx; c->fy = p->fy; c->cx = p->cx; c->cy = p->cy; c->bf = p->bf; c->depth_factor = p->depth_factor; c->max_depth = p->max_depth;
+  c->has_dist = 0;
+  for (int i = 0; i < 8; ++i) {
+    if (!std::isfinite(p->dist[i])) return fail(SSHIP_ERR_INVALID, std::string(who) + ": dist must be finite");
+    c->d[i] = p->dist[i];
+    if (p->dist[i] != 0.0) c->has_dist = 1;
+  }
+  return SSHIP_OK;
+}
+extern "C" int sship_rgbd_associate_batch_device(const float* kp, const int* n, int frames, int max_keypoints, const void* depth, int depth_type,
+                                                 int h, int w, int depth_stride, const sship_rgbd_params* p, float* kp_undist, float* stereo,
+                                                 uint8_t* has_depth, void* stream) {
+  if (!kp || !n || !depth || !p || !stereo || !has_depth) return fail(SSHIP_ERR_INVALID, "rgbd_associate_batch_device: null argument");
+  if (frames <= 0 || max_keypoints <= 0 || max_keypoints > kMaxKp)
+    return fail(SSHIP_ERR_INVALID, "rgbd_associate_batch_device: frames must be positive and max_keypoints in [1, 4096]");
+  RgbdK c;
+  if (int rc = rgbd_check(depth_type, h, w, depth_stride, p, &c, "rgbd_associate_batch_device")) return rc;
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  launch_rgbd_associate(kp, n, frames, max_keypoints, depth, depth_type == SSHIP_DEPTH_F32, h, w, depth_stride, c, kp_undist, stereo, has_depth, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("rgbd_associate", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_rgbd_associate_host(const float* keypoints, int kp_stride, int n, const void* depth, int depth_type, int h, int w,
+                                         int depth_stride, const sship_rgbd_params* p, float* kp_undist, float* stereo, uint8_t* has_depth) {
+  if (n == 0) return SSHIP_OK;
+  if (!keypoints || !kp_undist) return fail(SSHIP_ERR_INVALID, "rgbd_associate_host: null argument");
+  if (n < 0 || n > kMaxKp || kp_stride < 2) return fail(SSHIP_ERR_INVALID, "rgbd_associate_host: n must be in [0, 4096] and kp_stride >= 2");
+  if (!depth || !p || !stereo || !has_depth) return fail(SSHIP_ERR_INVALID, "rgbd_associate_host: null argument");
+  RgbdK c;
+  if (int rc = rgbd_check(depth_type, h, w, depth_stride, p, &c, "rgbd_associate_host")) return rc;
+  bind_thread();
+  std::vector<float> kp((size_t)n * 3, 0.f), und((size_t)n * 3);
+  for (int i = 0; i < n; ++i) { kp[3 * i] = keypoints[(size_t)i * kp_stride]; kp[3 * i + 1] = keypoints[(size_t)i * kp_stride + 1]; }
+  const size_t kb = kp.size() * sizeof(float), db = (size_t)h * depth_stride;
+  if (int rc = require_device()) return rc;
+  DevBuf d_kp, d_n, d_depth, d_und, d_st, d_hd;
+  SSHIP_HIP_CHECK(d_kp.ensure(kb)); SSHIP_HIP_CHECK(d_n.ensure(16)); SSHIP_HIP_CHECK(d_depth.ensure(db));
+  SSHIP_HIP_CHECK(d_und.ensure(kb)); SSHIP_HIP_CHECK(d_st.ensure(kb)); SSHIP_HIP_CHECK(d_hd.ensure((size_t)n));
+  SSHIP_HIP_CHECK(hipMemcpy(d_kp.p, kp.data(), kb, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(d_n.p, &n, sizeof(int), hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(d_depth.p, depth, db, hipMemcpyHostToDevice));
+  if (int rc = sship_rgbd_associate_batch_device(d_kp.as<float>(), d_n.as<int>(), 1, n, d_depth.p, depth_type, h, w, depth_stride, p, d_und.as<float>(),
+                                                 d_st.as<float>(), d_hd.as<uint8_t>(), nullptr)) return rc;
+  SSHIP_HIP_CHECK(hipMemcpy(und.data(), d_und.p, kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launch
+  SSHIP_HIP_CHECK(hipMemcpy(stereo, d_st.p, kb, hipMemcpyDeviceToHost));
+  SSHIP_HIP_CHECK(hipMemcpy(has_depth, d_hd.p, (size_t)n, hipMemcpyDeviceToHost));
+  for (int i = 0; i < n; ++i) { kp_undist[2 * i] = und[3 * i]; kp_undist[2 * i + 1] = und[3 * i + 1]; }
+  return SSHIP_OK;
+}
+
+// ====================================================================================================
 // fused front-end step: SuperPoint(batch 2P) + select + gather + LightGlue(P)
 // ====================================================================================================
 extern "C" int sship_frontend_batch_device(sship_sp* sp, sship_lg* lg, const uint8_t* imgs, int pairs, int h, int w,

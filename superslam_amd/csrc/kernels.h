@@ -1,6 +1,7 @@
 // Internal kernel launch interface of libsuperslam_hip (not part of the C ABI).
 #pragma once
 #include "common.h"
+#include "rect_host.h"
 
 namespace sship {
 
@@ -296,5 +297,12 @@ void launch_pg_odometry(const double* pose, int max_nodes, int graphs, double* o
 void launch_pg_loops(const int32_t* from, const int32_t* to, const double* pose, const int32_t* stats, int pairs, int min_inliers,
                      double noise_base, int32_t* loop_ij, double* loop_z, double* loop_sigma, double* loop_k2, uint8_t* loop_enable,
                      hipStream_t s);
+
+// rectification remap + RGB-D association (rect_kernels.hip; the host half - tables and tile boxes - is rect_host.h)
+struct RgbdK { double fx, fy, cx, cy, d[8], bf, depth_factor, max_depth; int has_dist; };
+void launch_rect_remap(const uint8_t* src, int src_h, int src_stride, uint8_t* dst, int dst_w, int dst_h, const void* table,
+                       const RectTile* tiles, int cameras, int cam0, int images, int force_direct, hipStream_t s);
+void launch_rgbd_associate(const float* kp, const int* lens, int frames, int max_kp, const void* depth, int depth_f32, int h, int w,
+                           long long depth_stride, const RgbdK& c, float* kp_undist, float* stereo, uint8_t* has_depth, hipStream_t s);
 
 }  // namespace sship

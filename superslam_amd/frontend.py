@@ -58,6 +58,82 @@ def stereo_associate_batch(kp, n, matches0, min_disparity: float = 1.0, max_row_
     return stereo, has_depth
 
 
+def rgbd_params(camera, depth_factor: float, max_depth: float):
+    """camera: a mapping with fx, fy, cx, cy, bf and optionally dist (up to 8 of k1 k2 p1 p2 k3 k4 k5 k6), or the Camera.* keys of a
+    settings file (Camera.fx ... Camera.k1 Camera.k2 Camera.p1 Camera.p2 Camera.k3, Camera.bf) -> the library's sship_rgbd_params."""
+    import math
+
+    get = lambda k, d=None: camera.get(k, camera.get("Camera." + k, d))   # noqa: E731
+    dist = camera.get("dist")
+    if dist is None:
+        dist = [get(k, 0.0) for k in ("k1", "k2", "p1", "p2", "k3", "k4", "k5", "k6")]
+    dist = [float(v) for v in dist]
+    if len(dist) > 8:
+        raise ValueError("dist has at most 8 coefficients (k1 k2 p1 p2 k3 k4 k5 k6)")
+    dist += [0.0] * (8 - len(dist))
+    vals = {k: get(k) for k in ("fx", "fy", "cx", "cy", "bf")}
+    if any(v is None for v in vals.values()):
+        raise ValueError("camera needs fx, fy, cx, cy and bf")
+    vals = {k: float(v) for k, v in vals.items()}
+    if not all(math.isfinite(v) for v in (*vals.values(), *dist)):
+        raise ValueError("camera parameters must be finite")
+    if not (vals["fx"] > 0 and vals["fy"] > 0):
+        raise ValueError("fx and fy must be > 0")
+    if not (float(depth_factor) > 0 and math.isfinite(float(depth_factor))):
+        raise ValueError("depth_factor must be finite and > 0")
+    if math.isnan(float(max_depth)):
+        raise ValueError("max_depth is NaN")
+    p = _lib.RgbdParams()
+    p.fx, p.fy, p.cx, p.cy, p.bf = vals["fx"], vals["fy"], vals["cx"], vals["cy"], vals["bf"]
+    p.dist = (_lib.C.c_double * 8)(*dist)
+    p.depth_factor, p.max_depth = float(depth_factor), float(max_depth)
+    return p
+
+
+def rgbd_associate_batch(kp, n, depth, camera, depth_factor: float, max_depth: float, kp_undist=None, stereo=None, has_depth=None,
+                         return_undistorted: bool = False, stream=None):
+    """RgbdFrontEnd::process's per-keypoint loop as a device stage (sship_rgbd_associate_batch_device): kp f32 [F, K, 3] raw keypoints,
+    n i32 [F], depth u16 or f32 [F, h, w] (rows may be strided) -> stereo f32 [F, K, 3] = (u', u' - bf / Z or NaN, v'), has_depth u8 [F, K],
+    the outputs of stereo_associate_batch.  (u', v') is the undistorted keypoint (cv::undistortPoints' 5 iterations; the keypoint's own bits
+    when every coefficient is zero), Z the depth at the rounded RAW pixel over depth_factor, has_depth = 0 < Z < max_depth.
+    return_undistorted (or a kp_undist tensor): also (u', v', score) f32 [F, K, 3].  Asynchronous on `stream` (default: torch's current)."""
+    import torch
+
+    if kp.dim() != 3 or kp.shape[2] != 3 or kp.dtype != torch.float32 or not kp.is_contiguous():
+        raise ValueError("kp must be a contiguous float32 tensor [frames, max_keypoints, 3]")
+    frames, k = int(kp.shape[0]), int(kp.shape[1])
+    if n.dtype != torch.int32 or n.numel() != frames or not n.is_contiguous():
+        raise ValueError(f"n must be a contiguous int32 tensor with {frames} entries")
+    if depth.dtype == torch.uint16:
+        dtype, es = 0, 2
+    elif depth.dtype == torch.float32:
+        dtype, es = 1, 4
+    else:
+        raise ValueError("depth must be uint16 or float32")
+    if depth.dim() != 3 or depth.shape[0] != frames or depth.stride(2) != 1 or depth.stride(1) < depth.shape[2] or (
+            frames > 1 and depth.stride(0) != depth.shape[1] * depth.stride(1)):
+        raise ValueError(f"depth must be [{frames}, h, w] with unit stride along x and frames packed as [frames, h, row stride]")
+    if frames < 1 or not 1 <= k <= 4096:
+        raise ValueError("frames must be >= 1 and max_keypoints in [1, 4096]")
+    prm = rgbd_params(camera, depth_factor, max_depth)
+    if return_undistorted and kp_undist is None:
+        kp_undist = torch.empty((frames, k, 3), dtype=torch.float32, device=kp.device)
+    if stereo is None:
+        stereo = torch.empty((frames, k, 3), dtype=torch.float32, device=kp.device)
+    if has_depth is None:
+        has_depth = torch.empty((frames, k), dtype=torch.uint8, device=kp.device)
+    for name, t, shape, dt in (("kp_undist", kp_undist, (frames, k, 3), torch.float32), ("stereo", stereo, (frames, k, 3), torch.float32),
+                               ("has_depth", has_depth, (frames, k), torch.uint8)):
+        if t is not None and (tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor {list(shape)}")
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    _lib.check(_lib.lib().sship_rgbd_associate_batch_device(kp.data_ptr(), n.data_ptr(), frames, k, depth.data_ptr(), dtype, int(depth.shape[1]),
+                                                            int(depth.shape[2]), int(depth.stride(1)) * es, _lib.C.byref(prm),
+                                                            kp_undist.data_ptr() if kp_undist is not None else None, stereo.data_ptr(),
+                                                            has_depth.data_ptr(), s))
+    return (stereo, has_depth, kp_undist) if kp_undist is not None else (stereo, has_depth)
+
+
 class FrontEndBatch:
     """Device-resident throughput step: SuperPoint on 2P images + LightGlue on P pairs, no host sync."""
 
