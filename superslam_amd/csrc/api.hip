@@ -345,6 +345,63 @@ static int require_device() {
   return sship_init(-1);
 }
 
+// the two events of a measurement hook: destroyed whichever way the hook returns
+struct EventPair {
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+};
+
+// The timing every measurement hook shares: `run` once to warm up, then `iters` times between two events; *avg_ms = elapsed / iters.
+template <class Run>
+static int bench_loop(hipStream_t s, int iters, Run run, float* avg_ms) {
+  SSHIP_HIP_CHECK(run());  // warm
+  EventPair ev;
+  SSHIP_HIP_CHECK(hipEventCreate(&ev.e0));
+  SSHIP_HIP_CHECK(hipEventCreate(&ev.e1));
+  SSHIP_HIP_CHECK(hipEventRecord(ev.e0, s));
+  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
+  SSHIP_HIP_CHECK(hipEventRecord(ev.e1, s));
+  SSHIP_HIP_CHECK(hipEventSynchronize(ev.e1));
+  float ms = 0.f;
+  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+  *avg_ms = ms / iters;
+  return SSHIP_OK;
+}
+
+// What the handles with nothing but a stream and RAII members to release share (nn, index, pose, ba, pg, rect).
+template <class Handle>
+static void destroy_handle(Handle* h) {
+  if (!h) return;
+  bind_thread();
+  (void)hipDeviceSynchronize();
+  if (h->stream) (void)hipStreamDestroy(h->stream);
+  delete h;
+}
+
+// The rectified stereo camera of the pose-only solver and the window smoother; `who` is the entry's name in the messages.
+struct StereoCamera {
+  bool set = false;
+  double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;
+};
+static int camera_set(StereoCamera* cam, const char* who, double fx, double fy, double cx, double cy, double baseline) {
+  if (!cam) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null handle");
+  if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(baseline))
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": every camera value must be finite");
+  if (!(fx > 0.0) || !(fy > 0.0) || !(baseline > 0.0)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": fx, fy and baseline must be > 0");
+  *cam = StereoCamera{true, fx, fy, cx, cy, baseline};
+  return SSHIP_OK;
+}
+static int camera_get(const StereoCamera* cam, const char* who, double* fx, double* fy, double* cx, double* cy, double* baseline) {
+  if (!cam) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null handle");
+  if (!cam->set) return fail(SSHIP_ERR_INVALID, std::string(who) + ": no camera has been set");
+  if (fx) *fx = cam->fx;
+  if (fy) *fy = cam->fy;
+  if (cx) *cx = cam->cx;
+  if (cy) *cy = cam->cy;
+  if (baseline) *baseline = cam->baseline;
+  return SSHIP_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // stage timers (off by default)
 // ------------------------------------------------------------------------------------------------
@@ -1136,19 +1193,7 @@ extern "C" int sship_sp_bench_layer(sship_sp* sp, int layer, int batch, int h, i
   const double mpp[12] = {9.0 * 64, 576.0 * 64 + 9.0 * 64 /* conv1a fused */, 576.0 * 64, 576.0 * 64, 576.0 * 128, 1152.0 * 128, 1152.0 * 128,
                           1152.0 * 128, 1152.0 * 256, 256.0 * 65, 1152.0 * 256, 256.0 * 256};
   if (macs) *macs = layer < 12 ? px[layer] * mpp[layer] * batch : layer == 15 ? (px[2] * mpp[2] + px[3] * mpp[3]) * batch : 0.0;
-  SSHIP_HIP_CHECK(run());  // warm
-  hipEvent_t e0, e1;
-  SSHIP_HIP_CHECK(hipEventCreate(&e0));
-  SSHIP_HIP_CHECK(hipEventCreate(&e1));
-  SSHIP_HIP_CHECK(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
-  SSHIP_HIP_CHECK(hipEventRecord(e1, s));
-  SSHIP_HIP_CHECK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  *avg_ms = ms / iters;
-  return SSHIP_OK;
+  return bench_loop(s, iters, run, avg_ms);
 }
 
 // host-image front: upload (pinned) -> gray -> batch path into pool slots -> D2H keypoints.
@@ -2090,20 +2135,9 @@ extern "C" int sship_lg_bench_stage(sship_lg* lg, int stage, int iters, float* a
   const size_t xbytes = (size_t)d.S * d.NP * 512;
   SSHIP_HIP_CHECK(keep.ensure(xbytes));
   SSHIP_HIP_CHECK(hipMemcpyAsync(keep.p, x, xbytes, hipMemcpyDeviceToDevice, s));
-  SSHIP_HIP_CHECK(run());  // warm
-  hipEvent_t e0, e1;
-  SSHIP_HIP_CHECK(hipEventCreate(&e0));
-  SSHIP_HIP_CHECK(hipEventCreate(&e1));
-  SSHIP_HIP_CHECK(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
-  SSHIP_HIP_CHECK(hipEventRecord(e1, s));
-  SSHIP_HIP_CHECK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  if (int rc = bench_loop(s, iters, run, avg_ms)) return rc;
   SSHIP_HIP_CHECK(hipMemcpyAsync(x, keep.p, xbytes, hipMemcpyDeviceToDevice, s));
   SSHIP_HIP_CHECK(hipStreamSynchronize(s));
-  *avg_ms = ms / iters;
   return SSHIP_OK;
 }
 
@@ -2220,13 +2254,7 @@ extern "C" int sship_nn_create(int max_kp, int max_pairs, sship_nn** out) {
   *out = nn.release();
   return SSHIP_OK;
 }
-extern "C" void sship_nn_destroy(sship_nn* nn) {
-  if (!nn) return;
-  bind_thread();
-  (void)hipDeviceSynchronize();
-  if (nn->stream) (void)hipStreamDestroy(nn->stream);
-  delete nn;
-}
+extern "C" void sship_nn_destroy(sship_nn* nn) { destroy_handle(nn); }
 extern "C" int sship_nn_set_params(sship_nn* nn, float ratio_threshold, float distance_threshold, int mutual_check) {
   if (!nn) return fail(SSHIP_ERR_INVALID, "nn_set_params: null handle");
   if (std::isnan(ratio_threshold) || ratio_threshold > 1.f) return fail(SSHIP_ERR_INVALID, "nn_set_params: ratio_threshold must be <= 1");
@@ -2407,19 +2435,7 @@ extern "C" int sship_nn_bench(sship_nn* nn, int iters, float* avg_ms) {
                       nn->last_ms0, s);
     return hipGetLastError();
   };
-  SSHIP_HIP_CHECK(run());  // warm
-  hipEvent_t e0, e1;
-  SSHIP_HIP_CHECK(hipEventCreate(&e0));
-  SSHIP_HIP_CHECK(hipEventCreate(&e1));
-  SSHIP_HIP_CHECK(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
-  SSHIP_HIP_CHECK(hipEventRecord(e1, s));
-  SSHIP_HIP_CHECK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  *avg_ms = ms / iters;
-  return SSHIP_OK;
+  return bench_loop(s, iters, run, avg_ms);
 }
 
 // ====================================================================================================
@@ -2660,17 +2676,16 @@ extern "C" int sship_ep_bench(sship_ep* ep, const uint8_t* img_dev, int h, int w
   if (int rc = ep_check_image(img_dev, h, w, stride, channels, "ep_bench")) return rc;
   hipStream_t s = ep->stream;
   if (int rc = sship_ep_infer_u8_device(ep, img_dev, h, w, stride, channels, ep->d_out.as<float>(), s)) return rc;  // warm (also uploads the tables)
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  auto drop = [&](int rc) { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); return rc; };
-  if (hipEventCreate(&e0) != hipSuccess || hipEventCreate(&e1) != hipSuccess) return drop(fail(SSHIP_ERR_HIP, "ep_bench: hipEventCreate failed"));
-  if (hipEventRecord(e0, s) != hipSuccess) return drop(fail(SSHIP_ERR_HIP, "ep_bench: hipEventRecord failed"));
+  EventPair ev;
+  if (hipEventCreate(&ev.e0) != hipSuccess || hipEventCreate(&ev.e1) != hipSuccess) return fail(SSHIP_ERR_HIP, "ep_bench: hipEventCreate failed");
+  if (hipEventRecord(ev.e0, s) != hipSuccess) return fail(SSHIP_ERR_HIP, "ep_bench: hipEventRecord failed");
   for (int i = 0; i < iters; ++i)
-    if (int rc = sship_ep_infer_u8_device(ep, img_dev, h, w, stride, channels, ep->d_out.as<float>(), s)) return drop(rc);
+    if (int rc = sship_ep_infer_u8_device(ep, img_dev, h, w, stride, channels, ep->d_out.as<float>(), s)) return rc;
   float ms = 0.f;
-  if (hipEventRecord(e1, s) != hipSuccess || hipEventSynchronize(e1) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess)
-    return drop(fail(SSHIP_ERR_HIP, "ep_bench: timing failed"));
+  if (hipEventRecord(ev.e1, s) != hipSuccess || hipEventSynchronize(ev.e1) != hipSuccess || hipEventElapsedTime(&ms, ev.e0, ev.e1) != hipSuccess)
+    return fail(SSHIP_ERR_HIP, "ep_bench: timing failed");
   *avg_ms = ms / iters;
-  return drop(SSHIP_OK);
+  return SSHIP_OK;
 }
 
 // ====================================================================================================
@@ -2718,13 +2733,7 @@ extern "C" int sship_index_create(int dim, int capacity, int max_queries, int ma
   *out = ix.release();
   return SSHIP_OK;
 }
-extern "C" void sship_index_destroy(sship_index* ix) {
-  if (!ix) return;
-  bind_thread();
-  (void)hipDeviceSynchronize();
-  if (ix->stream) (void)hipStreamDestroy(ix->stream);
-  delete ix;
-}
+extern "C" void sship_index_destroy(sship_index* ix) { destroy_handle(ix); }
 extern "C" int sship_index_dim(const sship_index* ix) { return ix ? ix->dim : 0; }
 extern "C" int sship_index_capacity(const sship_index* ix) { return ix ? ix->capacity : 0; }
 extern "C" int sship_index_size(const sship_index* ix) { return ix ? ix->size : 0; }
@@ -2864,26 +2873,8 @@ extern "C" int sship_index_bench(sship_index* ix, int iters, float* avg_ms) {
                        ix->partial.as<unsigned long long>(), l.rows, l.scores, l.counts, s);
     return hipGetLastError();
   };
-  SSHIP_HIP_CHECK(run());  // warm
-  hipEvent_t e0, e1;
-  SSHIP_HIP_CHECK(hipEventCreate(&e0));
-  SSHIP_HIP_CHECK(hipEventCreate(&e1));
-  SSHIP_HIP_CHECK(hipEventRecord(e0, s));
-  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
-  SSHIP_HIP_CHECK(hipEventRecord(e1, s));
-  SSHIP_HIP_CHECK(hipEventSynchronize(e1));
-  float ms = 0.f;
-  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-  *avg_ms = ms / iters;
-  return SSHIP_OK;
+  return bench_loop(s, iters, run, avg_ms);
 }
-
-// the two events of a measurement hook: destroyed whichever way the hook returns
-struct EventPair {
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  ~EventPair() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
-};
 
 // ====================================================================================================
 // Pose-only stereo solver (include/sship.h "Pose-only stereo solver"; csrc/pose_kernels.hip)
@@ -2891,8 +2882,7 @@ struct EventPair {
 constexpr int kPoseMaxPairs = 65535;
 struct sship_pose {
   int max_obs = 0, max_pairs = 0;
-  bool has_camera = false;
-  double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;
+  StereoCamera cam;
   sship_pose_params prm{10.0, 8.0, 40.0, 7.815, 1e-5, 1e5, 1e-5, 1e-5, 3.0, 100};
   hipStream_t stream = nullptr;
   DevBuf points1, meas1, valid1, pose01, pose1, stats1, cost1, inlier1;   // sship_pose_solve_host: one staged pair and its results
@@ -2903,8 +2893,8 @@ struct sship_pose {
 };
 static PoseK pose_constants(const sship_pose* ps) {
   PoseK k;
-  k.fx = ps->fx; k.fy = ps->fy; k.cx = ps->cx; k.cy = ps->cy; k.baseline = ps->baseline;
-  k.inv_sigma_px = 1.0 / ps->prm.sigma_px; k.sigma_d0 = ps->prm.sigma_d0; k.d_cond = ps->fx * ps->baseline / ps->prm.cond_depth;
+  k.fx = ps->cam.fx; k.fy = ps->cam.fy; k.cx = ps->cam.cx; k.cy = ps->cam.cy; k.baseline = ps->cam.baseline;
+  k.inv_sigma_px = 1.0 / ps->prm.sigma_px; k.sigma_d0 = ps->prm.sigma_d0; k.d_cond = ps->cam.fx * ps->cam.baseline / ps->prm.cond_depth;
   k.k = std::sqrt(ps->prm.huber_k2); k.k2 = ps->prm.huber_k2;
   k.lambda0 = ps->prm.lambda0; k.lambda_max = ps->prm.lambda_max; k.abs_tol = ps->prm.abs_tol; k.rel_tol = ps->prm.rel_tol;
   k.inlier_px = ps->prm.inlier_px; k.max_iterations = ps->prm.max_iterations;
@@ -2934,30 +2924,12 @@ extern "C" int sship_pose_create(int max_obs, int max_pairs, sship_pose** out) {
   *out = ps.release();
   return SSHIP_OK;
 }
-extern "C" void sship_pose_destroy(sship_pose* ps) {
-  if (!ps) return;
-  bind_thread();
-  (void)hipDeviceSynchronize();
-  if (ps->stream) (void)hipStreamDestroy(ps->stream);
-  delete ps;
-}
+extern "C" void sship_pose_destroy(sship_pose* ps) { destroy_handle(ps); }
 extern "C" int sship_pose_set_camera(sship_pose* ps, double fx, double fy, double cx, double cy, double baseline) {
-  if (!ps) return fail(SSHIP_ERR_INVALID, "pose_set_camera: null handle");
-  if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(baseline))
-    return fail(SSHIP_ERR_INVALID, "pose_set_camera: every camera value must be finite");
-  if (!(fx > 0.0) || !(fy > 0.0) || !(baseline > 0.0)) return fail(SSHIP_ERR_INVALID, "pose_set_camera: fx, fy and baseline must be > 0");
-  ps->fx = fx; ps->fy = fy; ps->cx = cx; ps->cy = cy; ps->baseline = baseline; ps->has_camera = true;
-  return SSHIP_OK;
+  return camera_set(ps ? &ps->cam : nullptr, "pose_set_camera", fx, fy, cx, cy, baseline);
 }
 extern "C" int sship_pose_get_camera(const sship_pose* ps, double* fx, double* fy, double* cx, double* cy, double* baseline) {
-  if (!ps) return fail(SSHIP_ERR_INVALID, "pose_get_camera: null handle");
-  if (!ps->has_camera) return fail(SSHIP_ERR_INVALID, "pose_get_camera: no camera has been set");
-  if (fx) *fx = ps->fx;
-  if (fy) *fy = ps->fy;
-  if (cx) *cx = ps->cx;
-  if (cy) *cy = ps->cy;
-  if (baseline) *baseline = ps->baseline;
-  return SSHIP_OK;
+  return camera_get(ps ? &ps->cam : nullptr, "pose_get_camera", fx, fy, cx, cy, baseline);
 }
 extern "C" int sship_pose_set_params(sship_pose* ps, const sship_pose_params* p) {
   if (!ps || !p) return fail(SSHIP_ERR_INVALID, "pose_set_params: null argument");
@@ -2991,7 +2963,7 @@ extern "C" int sship_pose_solve_batch_device(sship_pose* ps, const float* points
                                              int pairs, double* pose, int32_t* stats, double* cost, uint8_t* inlier, void* stream) {
   if (!ps || !points || !meas || !valid || !pose || !stats || !cost) return fail(SSHIP_ERR_INVALID, "pose_solve_batch_device: null argument");
   if (pairs < 1 || pairs > ps->max_pairs) return fail(SSHIP_ERR_INVALID, "pose_solve_batch_device: pairs must be in [1, max_pairs]");
-  if (!ps->has_camera) return fail(SSHIP_ERR_INVALID, "pose_solve_batch_device: set the camera first (sship_pose_set_camera)");
+  if (!ps->cam.set) return fail(SSHIP_ERR_INVALID, "pose_solve_batch_device: set the camera first (sship_pose_set_camera)");
   bind_thread();
   hipStream_t s = static_cast<hipStream_t>(stream);
   g_timer.begin_if_idle(s);
@@ -3004,7 +2976,7 @@ extern "C" int sship_pose_solve_host(sship_pose* ps, const float* points, const 
   if (!ps || !pose_out || !stats_out || !cost_out) return fail(SSHIP_ERR_INVALID, "pose_solve_host: null argument");
   if (n_obs < 0 || n_obs > ps->max_obs) return fail(SSHIP_ERR_INVALID, "pose_solve_host: n_obs must be in [0, max_obs]");
   if (n_obs > 0 && (!points || !meas)) return fail(SSHIP_ERR_INVALID, "pose_solve_host: null argument");
-  if (!ps->has_camera) return fail(SSHIP_ERR_INVALID, "pose_solve_host: set the camera first (sship_pose_set_camera)");
+  if (!ps->cam.set) return fail(SSHIP_ERR_INVALID, "pose_solve_host: set the camera first (sship_pose_set_camera)");
   bind_thread();
   hipStream_t s = ps->stream;
   const size_t n = (size_t)ps->max_obs, m = (size_t)n_obs;
@@ -3044,7 +3016,7 @@ extern "C" int sship_pose_obs_from_matches_batch_device(const sship_pose* ps, co
     return fail(SSHIP_ERR_INVALID, "pose_obs_from_matches_batch_device: null argument");
   if (pairs < 1 || pairs > ps->max_pairs) return fail(SSHIP_ERR_INVALID, "pose_obs_from_matches_batch_device: pairs must be in [1, max_pairs]");
   if (n_stride < 1) return fail(SSHIP_ERR_INVALID, "pose_obs_from_matches_batch_device: n_stride must be >= 1");
-  if (!ps->has_camera) return fail(SSHIP_ERR_INVALID, "pose_obs_from_matches_batch_device: set the camera first (sship_pose_set_camera)");
+  if (!ps->cam.set) return fail(SSHIP_ERR_INVALID, "pose_obs_from_matches_batch_device: set the camera first (sship_pose_set_camera)");
   bind_thread();
   hipStream_t s = static_cast<hipStream_t>(stream);
   g_timer.begin_if_idle(s);
@@ -3066,18 +3038,7 @@ extern "C" int sship_pose_bench(sship_pose* ps, int iters, float* avg_ms) {
     launch_pose_solve(l.points, l.meas, l.valid, l.pose0, ps->max_obs, l.pairs, k, l.pose, l.stats, l.cost, l.inlier, s);
     return hipGetLastError();
   };
-  SSHIP_HIP_CHECK(run());  // warm
-  EventPair ev;            // destroyed on every return
-  SSHIP_HIP_CHECK(hipEventCreate(&ev.e0));
-  SSHIP_HIP_CHECK(hipEventCreate(&ev.e1));
-  SSHIP_HIP_CHECK(hipEventRecord(ev.e0, s));
-  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
-  SSHIP_HIP_CHECK(hipEventRecord(ev.e1, s));
-  SSHIP_HIP_CHECK(hipEventSynchronize(ev.e1));
-  float ms = 0.f;
-  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-  *avg_ms = ms / iters;
-  return SSHIP_OK;
+  return bench_loop(s, iters, run, avg_ms);
 }
 
 // ====================================================================================================
@@ -3086,8 +3047,7 @@ extern "C" int sship_pose_bench(sship_pose* ps, int iters, float* avg_ms) {
 constexpr int kBaMaxWindows = 65535;
 struct sship_ba {
   int K = 0, N = 0, L = 0, max_windows = 0;
-  bool has_camera = false;
-  double fx = 0, fy = 0, cx = 0, cy = 0, baseline = 0;
+  StereoCamera cam;
   sship_ba_params prm{1.0, 9.0, 1e-5, 1e5, 1e-3, 1e-3, 20};
   hipStream_t stream = nullptr;
   DevBuf workspace;
@@ -3098,7 +3058,7 @@ struct sship_ba {
 };
 static BaK ba_constants(const sship_ba* ba) {
   BaK k;
-  k.fx = ba->fx; k.fy = ba->fy; k.cx = ba->cx; k.cy = ba->cy; k.baseline = ba->baseline;
+  k.fx = ba->cam.fx; k.fy = ba->cam.fy; k.cx = ba->cam.cx; k.cy = ba->cam.cy; k.baseline = ba->cam.baseline;
   k.inv_sigma = 1.0 / ba->prm.sigma_px; k.k = std::sqrt(ba->prm.huber_k2); k.k2 = ba->prm.huber_k2;
   k.lambda0 = ba->prm.lambda0; k.lambda_max = ba->prm.lambda_max; k.abs_tol = ba->prm.abs_tol; k.rel_tol = ba->prm.rel_tol;
   k.max_iterations = ba->prm.max_iterations;
@@ -3132,30 +3092,12 @@ extern "C" int sship_ba_create(int max_keyframes, int max_obs, int max_landmarks
   *out = ba.release();
   return SSHIP_OK;
 }
-extern "C" void sship_ba_destroy(sship_ba* ba) {
-  if (!ba) return;
-  bind_thread();
-  (void)hipDeviceSynchronize();
-  if (ba->stream) (void)hipStreamDestroy(ba->stream);
-  delete ba;
-}
+extern "C" void sship_ba_destroy(sship_ba* ba) { destroy_handle(ba); }
 extern "C" int sship_ba_set_camera(sship_ba* ba, double fx, double fy, double cx, double cy, double baseline) {
-  if (!ba) return fail(SSHIP_ERR_INVALID, "ba_set_camera: null handle");
-  if (!std::isfinite(fx) || !std::isfinite(fy) || !std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(baseline))
-    return fail(SSHIP_ERR_INVALID, "ba_set_camera: every camera value must be finite");
-  if (!(fx > 0.0) || !(fy > 0.0) || !(baseline > 0.0)) return fail(SSHIP_ERR_INVALID, "ba_set_camera: fx, fy and baseline must be > 0");
-  ba->fx = fx; ba->fy = fy; ba->cx = cx; ba->cy = cy; ba->baseline = baseline; ba->has_camera = true;
-  return SSHIP_OK;
+  return camera_set(ba ? &ba->cam : nullptr, "ba_set_camera", fx, fy, cx, cy, baseline);
 }
 extern "C" int sship_ba_get_camera(const sship_ba* ba, double* fx, double* fy, double* cx, double* cy, double* baseline) {
-  if (!ba) return fail(SSHIP_ERR_INVALID, "ba_get_camera: null handle");
-  if (!ba->has_camera) return fail(SSHIP_ERR_INVALID, "ba_get_camera: no camera has been set");
-  if (fx) *fx = ba->fx;
-  if (fy) *fy = ba->fy;
-  if (cx) *cx = ba->cx;
-  if (cy) *cy = ba->cy;
-  if (baseline) *baseline = ba->baseline;
-  return SSHIP_OK;
+  return camera_get(ba ? &ba->cam : nullptr, "ba_get_camera", fx, fy, cx, cy, baseline);
 }
 extern "C" int sship_ba_set_params(sship_ba* ba, const sship_ba_params* p) {
   if (!ba || !p) return fail(SSHIP_ERR_INVALID, "ba_set_params: null argument");
@@ -3188,7 +3130,7 @@ extern "C" int sship_ba_solve_batch_device(sship_ba* ba, const float* meas, cons
                                            int windows, double* pose, int32_t* stats, double* cost, float* landmarks, void* stream) {
   if (!ba || !meas || !track || !pose0 || !pose || !stats || !cost) return fail(SSHIP_ERR_INVALID, "ba_solve_batch_device: null argument");
   if (windows < 1 || windows > ba->max_windows) return fail(SSHIP_ERR_INVALID, "ba_solve_batch_device: windows must be in [1, max_windows]");
-  if (!ba->has_camera) return fail(SSHIP_ERR_INVALID, "ba_solve_batch_device: set the camera first (sship_ba_set_camera)");
+  if (!ba->cam.set) return fail(SSHIP_ERR_INVALID, "ba_solve_batch_device: set the camera first (sship_ba_set_camera)");
   bind_thread();
   hipStream_t s = static_cast<hipStream_t>(stream);
   g_timer.begin_if_idle(s);
@@ -3200,7 +3142,7 @@ extern "C" int sship_ba_solve_host(sship_ba* ba, const float* meas, const int32_
                                    int32_t* stats_out, double* cost_out, float* landmarks_out) {
   if (!ba || !meas || !track || !pose0 || !pose_out || !stats_out || !cost_out) return fail(SSHIP_ERR_INVALID, "ba_solve_host: null argument");
   if (n_kf < 0 || n_kf > ba->K) return fail(SSHIP_ERR_INVALID, "ba_solve_host: n_kf must be in [0, max_keyframes]");
-  if (!ba->has_camera) return fail(SSHIP_ERR_INVALID, "ba_solve_host: set the camera first (sship_ba_set_camera)");
+  if (!ba->cam.set) return fail(SSHIP_ERR_INVALID, "ba_solve_host: set the camera first (sship_ba_set_camera)");
   bind_thread();
   hipStream_t s = ba->stream;
   const size_t kn = (size_t)ba->K * ba->N, k12 = (size_t)ba->K * 96, l3 = (size_t)ba->L * 12;
@@ -3256,18 +3198,7 @@ extern "C" int sship_ba_bench(sship_ba* ba, int iters, float* avg_ms) {
     launch_ba_solve(l.meas, l.track, l.n_kf, l.pose0, ba->K, ba->N, ba->L, l.windows, k, ba->workspace.p, l.pose, l.stats, l.cost, l.landmarks, s);
     return hipGetLastError();
   };
-  SSHIP_HIP_CHECK(run());  // warm
-  EventPair ev;            // destroyed on every return
-  SSHIP_HIP_CHECK(hipEventCreate(&ev.e0));
-  SSHIP_HIP_CHECK(hipEventCreate(&ev.e1));
-  SSHIP_HIP_CHECK(hipEventRecord(ev.e0, s));
-  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
-  SSHIP_HIP_CHECK(hipEventRecord(ev.e1, s));
-  SSHIP_HIP_CHECK(hipEventSynchronize(ev.e1));
-  float ms = 0.f;
-  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-  *avg_ms = ms / iters;
-  return SSHIP_OK;
+  return bench_loop(s, iters, run, avg_ms);
 }
 
 // ====================================================================================================
@@ -3340,13 +3271,7 @@ extern "C" size_t sship_pg_workspace_slice_bytes(int max_nodes, int max_loops) {
   if (max_nodes < 2 || max_nodes > kPgMaxNodes || max_loops < 0 || max_loops > kPgMaxLoops) return 0;
   return pg_workspace_bytes(max_nodes, max_loops);
 }
-extern "C" void sship_pg_destroy(sship_pg* pg) {
-  if (!pg) return;
-  bind_thread();
-  (void)hipDeviceSynchronize();
-  if (pg->stream) (void)hipStreamDestroy(pg->stream);
-  delete pg;
-}
+extern "C" void sship_pg_destroy(sship_pg* pg) { destroy_handle(pg); }
 extern "C" int sship_pg_set_params(sship_pg* pg, const sship_pg_params* p) {
   if (!pg || !p) return fail(SSHIP_ERR_INVALID, "pg_set_params: null argument");
   const double all[7] = {p->odom_sigma_rot, p->odom_sigma_trans, p->lambda0, p->lambda_max, p->abs_tol, p->rel_tol, p->max_translation};
@@ -3488,18 +3413,7 @@ extern "C" int sship_pg_bench(sship_pg* pg, int iters, float* avg_ms) {
                     k, pg->workspace.p, l.pose, l.stats, l.cost, l.chi2, s);
     return hipGetLastError();
   };
-  SSHIP_HIP_CHECK(run());  // warm
-  EventPair ev;            // destroyed on every return
-  SSHIP_HIP_CHECK(hipEventCreate(&ev.e0));
-  SSHIP_HIP_CHECK(hipEventCreate(&ev.e1));
-  SSHIP_HIP_CHECK(hipEventRecord(ev.e0, s));
-  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
-  SSHIP_HIP_CHECK(hipEventRecord(ev.e1, s));
-  SSHIP_HIP_CHECK(hipEventSynchronize(ev.e1));
-  float ms = 0.f;
-  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-  *avg_ms = ms / iters;
-  return SSHIP_OK;
+  return bench_loop(s, iters, run, avg_ms);
 }
 
 // ====================================================================================================
@@ -3560,13 +3474,7 @@ extern "C" int sship_rect_create(int src_w, int src_h, int dst_w, int dst_h, int
   *out = r.release();
   return SSHIP_OK;
 }
-extern "C" void sship_rect_destroy(sship_rect* rect) {
-  if (!rect) return;
-  bind_thread();
-  (void)hipDeviceSynchronize();
-  if (rect->stream) (void)hipStreamDestroy(rect->stream);
-  delete rect;
-}
+extern "C" void sship_rect_destroy(sship_rect* rect) { destroy_handle(rect); }
 extern "C" int sship_rect_set_maps(sship_rect* rect, int camera, const float* map_x, const float* map_y) {
   if (!rect || !map_x || !map_y) return fail(SSHIP_ERR_INVALID, "rect_set_maps: null argument");
   if (camera < 0 || camera >= rect->cameras) return fail(SSHIP_ERR_INVALID, "rect_set_maps: camera must be in [0, cameras)");
@@ -3660,18 +3568,7 @@ extern "C" int sship_rect_bench(sship_rect* rect, int images, int path, int iter
                       rect->table.p, rect->tile_boxes.as<RectTile>(), rect->cameras, 0, images, path == SSHIP_RECT_PATH_DIRECT ? 1 : 0, s);
     return hipGetLastError();
   };
-  SSHIP_HIP_CHECK(run());  // warm
-  EventPair ev;            // destroyed on every return
-  SSHIP_HIP_CHECK(hipEventCreate(&ev.e0));
-  SSHIP_HIP_CHECK(hipEventCreate(&ev.e1));
-  SSHIP_HIP_CHECK(hipEventRecord(ev.e0, s));
-  for (int i = 0; i < iters; ++i) SSHIP_HIP_CHECK(run());
-  SSHIP_HIP_CHECK(hipEventRecord(ev.e1, s));
-  SSHIP_HIP_CHECK(hipEventSynchronize(ev.e1));
-  float ms = 0.f;
-  SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
-  *avg_ms = ms / iters;
-  return SSHIP_OK;
+  return bench_loop(s, iters, run, avg_ms);
 }
 // the checks both RGB-D entries share; fills the kernel's constants
 static int rgbd_check(int depth_type, int h, int w, int depth_stride, const sship_rgbd_params* p, RgbdK* c, const char* who) {

@@ -11,14 +11,16 @@
 //                entry of S (lower triangle) and b has ONE owner thread, which walks the active landmarks in ascending l, three FMAs per
 //                entry and landmark seen by both slots (S_kk' -= Z_kl Z_k'l^T keeps S symmetric by construction; a thread owns whole rows
 //                of 6x6 blocks, and the landmarks' masks and rows are staged in LDS 128 at a time);  S lives in LDS and is factorised
-//                there column by column by the whole workgroup;  forward and back substitution likewise;  the poses and the landmarks
-//                move;  the cost at the candidate is one more pass (all threads over all rows, butterfly, waves).
+//                there column by column by the whole workgroup;  forward and back substitution likewise;  the poses (se3_retract,
+//                solver_math.h) and the landmarks move;  the cost at the candidate is one more pass (all threads over all rows,
+//                butterfly, waves).
 //                Every thread carries the scalars of the schedule (lambda, c, trials) itself, from values broadcast through LDS, so every
 //                branch of the loop is uniform.
 //   k_ba_tracks  one workgroup per window, slot after slot: the winning predecessor of a row by atomicMax in LDS.
 // No local array is indexed by a run-time value; nothing lives in scratch: profiles/ba_solve_resource_usage.txt.
 #include "../../include/sship.h"
 #include "kernels.h"
+#include "solver_math.h"
 
 namespace sship {
 
@@ -27,9 +29,6 @@ namespace {
 constexpr int kBaThreads = 256;
 constexpr int kBaNone = 0x7fffffff;
 constexpr int kBaTile = 128;
-
-__device__ __forceinline__ bool ba_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
-__device__ __forceinline__ bool ba_finitef(float v) { return fabsf(v) <= 3.4028234663852886e38f; }
 
 // One observation of point X from pose T (row-major [R | t], any address space): the whitened residual and rho; false behind the camera.
 struct BaRes { double x, y, z, iz, r0, r1, r2, w, rho; bool front; };
@@ -66,36 +65,6 @@ __device__ __forceinline__ BaGrad ba_grad(const BaRes& o, const BaK& P) {
   g.a0 = fiz; g.a2 = -fiz * o.x * o.iz; g.c2 = -fiz * (o.x - P.baseline) * o.iz;
   g.b1 = giz; g.b2 = -giz * o.y * o.iz;
   return g;
-}
-
-// Tn = T Exp(delta), delta = (omega, v): as the pose-only solver's retraction (pose_kernels.hip), no re-orthonormalisation.
-__device__ __forceinline__ void ba_retract(const double* T, const double* delta, double* Tn) {
-  const double wx = delta[0], wy = delta[1], wz = delta[2];
-  const double th2 = wx * wx + wy * wy + wz * wz;
-  double A, B, C;
-  if (th2 < 1e-12) {
-    A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0; C = 1.0 / 6.0 - th2 / 120.0;
-  } else {
-    const double th = sqrt(th2), sh = sin(0.5 * th);
-    const double st = sin(th);
-    A = st / th; B = 2.0 * sh * sh / th2; C = (th - st) / (th2 * th);
-  }
-  const double W[3][3] = {{0.0, -wz, wy}, {wz, 0.0, -wx}, {-wy, wx, 0.0}};
-  const double W2[3][3] = {{-(wy * wy + wz * wz), wx * wy, wx * wz}, {wx * wy, -(wx * wx + wz * wz), wy * wz}, {wx * wz, wy * wz, -(wx * wx + wy * wy)}};
-  double E[3][3], u[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) E[i][j] = (i == j ? 1.0 : 0.0) + A * W[i][j] + B * W2[i][j];
-    u[i] = delta[3 + i] + B * (W[i][0] * delta[3] + W[i][1] * delta[4] + W[i][2] * delta[5]) +
-           C * (W2[i][0] * delta[3] + W2[i][1] * delta[4] + W2[i][2] * delta[5]);
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) Tn[4 * i + j] = T[4 * i] * E[0][j] + T[4 * i + 1] * E[1][j] + T[4 * i + 2] * E[2][j];
-    Tn[4 * i + 3] = T[4 * i + 3] + T[4 * i] * u[0] + T[4 * i + 1] * u[1] + T[4 * i + 2] * u[2];
-  }
 }
 
 // the workspace slice of one resident workgroup (ba_workspace_bytes)
@@ -164,7 +133,7 @@ __global__ __launch_bounds__(kBaThreads) void k_ba_solve(const float* __restrict
     for (int i = tid; i < K * 12; i += kBaThreads) {
       const double t = wp0[i];
       s_T[i] = t; s_Tn[i] = t;
-      if (i < n_kf * 12 && !ba_finite(t)) atomicOr(&s_flag, 1);
+      if (i < n_kf * 12 && !solver_finite(t)) atomicOr(&s_flag, 1);
     }
     for (size_t i = tid; i < (size_t)L * K; i += kBaThreads) ws.obs_of[i] = kBaNone;
     __syncthreads();
@@ -174,7 +143,7 @@ __global__ __launch_bounds__(kBaThreads) void k_ba_solve(const float* __restrict
         const int t = wt[k * N + i];
         if ((unsigned)t >= (unsigned)L) continue;
         const float* m = wm + ((size_t)k * N + i) * 3;
-        if (ba_finitef(m[0]) && ba_finitef(m[1]) && ba_finitef(m[2])) atomicMin(&ws.obs_of[(size_t)t * K + k], i);
+        if (solver_finitef(m[0]) && solver_finitef(m[1]) && solver_finitef(m[2])) atomicMin(&ws.obs_of[(size_t)t * K + k], i);
       }
     __syncthreads();
     {
@@ -505,7 +474,7 @@ __global__ __launch_bounds__(kBaThreads) void k_ba_solve(const float* __restrict
             for (int i = 0; i < 6; ++i) delta[i] = s_b[(tid - 1) * 6 + i];
 #pragma unroll
             for (int i = 0; i < 12; ++i) Tl[i] = s_T[tid * 12 + i];
-            ba_retract(Tl, delta, Tn);
+            se3_retract(Tl, delta, Tn);
 #pragma unroll
             for (int i = 0; i < 12; ++i) s_Tn[tid * 12 + i] = Tn[i];
           }
@@ -527,7 +496,7 @@ __global__ __launch_bounds__(kBaThreads) void k_ba_solve(const float* __restrict
           }
           __syncthreads();
           const double cn = cost_at(s_Tn, ws.Xn);
-          const bool conv = ba_finite(cn) && fabs(c - cn) <= fmax(P.abs_tol, P.rel_tol * c);
+          const bool conv = solver_finite(cn) && fabs(c - cn) <= fmax(P.abs_tol, P.rel_tol * c);
           if (conv || cn < c) {  // the candidate becomes the state
             for (int i = 12 + tid; i < n_kf * 12; i += kBaThreads) s_T[i] = s_Tn[i];
             for (int j = tid; j < n_act; j += kBaThreads) {

@@ -13,14 +13,15 @@
 //                update steps, and the 78 products that the next node and the bounding separators receive.  The separator system is
 //                assembled in the workspace (one owner per entry; the loop blocks by 36 threads in ascending record index), factorised
 //                right-looking column by column by the whole workgroup (the scaled column staged in LDS, the trailing update on the
-//                VALU), solved forward and backward likewise;  the segments are back-substituted by their waves;  the poses move;  the
-//                cost at the candidate is one more pass over the edges.
+//                VALU), solved forward and backward likewise;  the segments are back-substituted by their waves;  the poses move (se3_retract,
+//                solver_math.h);  the cost at the candidate is one more pass over the edges.
 //                Every thread carries the scalars of the schedule (lambda, c, trials) itself, from values broadcast through LDS, so
 //                every branch of the loops is uniform.  A rejected trial changes only lambda: the same H and g are factorised again.
 //   k_pg_odometry, k_pg_loops   the two gather stages, one thread per slot / record.
 // No local array is indexed by a run-time value; plain vector stores only: profiles/pg_solve_resource_usage.txt.
 #include "../../include/sship.h"
 #include "kernels.h"
+#include "solver_math.h"
 
 namespace sship {
 
@@ -32,8 +33,6 @@ constexpr int kPgFac = 114;      // doubles per eliminated node: the 6 x 19 pane
 constexpr int kPgSeg = 120;      // doubles per segment: F'^T F' 36, F'^T y' 6, U'^T U' 36, U'^T F' 36, U'^T y' 6 (of its last node)
 constexpr int kPgPanelLd = 20;
 constexpr int kPgMaxOrder = 12 * kPgMaxLoops;
-
-__device__ __forceinline__ bool pg_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }
 
 // the lanes of one wave exchange data through LDS: order this wave's LDS traffic
 __device__ __forceinline__ void pg_wave_sync() {
@@ -166,36 +165,6 @@ __device__ __forceinline__ void pg_jacobians(const PgRes& o, const double* sg, d
   }
 }
 
-// Tn = T Exp(delta), delta = (omega, v): the retraction of the other two solvers (ba_kernels.hip), no re-orthonormalisation.
-__device__ __forceinline__ void pg_retract(const double* T, const double* delta, double* Tn) {
-  const double wx = delta[0], wy = delta[1], wz = delta[2];
-  const double th2 = wx * wx + wy * wy + wz * wz;
-  double A, B, C;
-  if (th2 < 1e-12) {
-    A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0; C = 1.0 / 6.0 - th2 / 120.0;
-  } else {
-    const double th = sqrt(th2), sh = sin(0.5 * th);
-    const double st = sin(th);
-    A = st / th; B = 2.0 * sh * sh / th2; C = (th - st) / (th2 * th);
-  }
-  const double W[3][3] = {{0.0, -wz, wy}, {wz, 0.0, -wx}, {-wy, wx, 0.0}};
-  const double W2[3][3] = {{-(wy * wy + wz * wz), wx * wy, wx * wz}, {wx * wy, -(wx * wx + wz * wz), wy * wz}, {wx * wz, wy * wz, -(wx * wx + wy * wy)}};
-  double E[3][3], u[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) E[i][j] = (i == j ? 1.0 : 0.0) + A * W[i][j] + B * W2[i][j];
-    u[i] = delta[3 + i] + B * (W[i][0] * delta[3] + W[i][1] * delta[4] + W[i][2] * delta[5]) +
-           C * (W2[i][0] * delta[3] + W2[i][1] * delta[4] + W2[i][2] * delta[5]);
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) Tn[4 * i + j] = T[4 * i] * E[0][j] + T[4 * i + 1] * E[1][j] + T[4 * i + 2] * E[2][j];
-    Tn[4 * i + 3] = T[4 * i + 3] + T[4 * i] * u[0] + T[4 * i + 1] * u[1] + T[4 * i + 2] * u[2];
-  }
-}
-
 // the workspace slice of one resident workgroup (pg_workspace_bytes)
 struct PgWs {
   double *edge, *T, *Tn, *D, *U, *g, *fac, *delta, *seg, *S;
@@ -278,15 +247,15 @@ __global__ __launch_bounds__(kPgThreads) void k_pg_solve(const int32_t* __restri
     for (int i = tid; i < n * 12; i += kPgThreads) {
       const double t = p0[i];
       ws.T[i] = t; ws.Tn[i] = t;
-      if (!pg_finite(t)) atomicOr(&s_flag, 1);
+      if (!solver_finite(t)) atomicOr(&s_flag, 1);
     }
     {
       int cnt = 0;
       for (int k = tid; k < n - 1; k += kPgThreads) {
         bool ok = true;
-        for (int i = 0; i < 12; ++i) ok = ok && pg_finite(oz[(size_t)k * 12 + i]);
+        for (int i = 0; i < 12; ++i) ok = ok && solver_finite(oz[(size_t)k * 12 + i]);
         if (osg)
-          for (int i = 0; i < 6; ++i) { const double sg = osg[(size_t)k * 6 + i]; ok = ok && pg_finite(sg) && sg > 0.0; }
+          for (int i = 0; i < 6; ++i) { const double sg = osg[(size_t)k * 6 + i]; ok = ok && solver_finite(sg) && sg > 0.0; }
         ws.oflag[k] = ok ? 1 : 0;
         cnt += ok ? 1 : 0;
       }
@@ -294,9 +263,9 @@ __global__ __launch_bounds__(kPgThreads) void k_pg_solve(const int32_t* __restri
     }
     for (int l = tid; l < L; l += kPgThreads) {
       const int i = lij[2 * l], j = lij[2 * l + 1];
-      bool ok = (unsigned)i < (unsigned)n && (unsigned)j < (unsigned)n && i != j && (!len || len[l] != 0) && pg_finite(lk2[l]);
-      for (int q = 0; q < 12; ++q) ok = ok && pg_finite(lz[(size_t)l * 12 + q]);
-      for (int q = 0; q < 6; ++q) { const double sg = lsg[(size_t)l * 6 + q]; ok = ok && pg_finite(sg) && sg > 0.0; }
+      bool ok = (unsigned)i < (unsigned)n && (unsigned)j < (unsigned)n && i != j && (!len || len[l] != 0) && solver_finite(lk2[l]);
+      for (int q = 0; q < 12; ++q) ok = ok && solver_finite(lz[(size_t)l * 12 + q]);
+      for (int q = 0; q < 6; ++q) { const double sg = lsg[(size_t)l * 6 + q]; ok = ok && solver_finite(sg) && sg > 0.0; }
       s_li[l] = i; s_lj[l] = j; s_lstat[l] = ok ? 1 : 0; s_lpres[l] = ok ? 1 : 0;
     }
     __syncthreads();
@@ -638,13 +607,13 @@ __global__ __launch_bounds__(kPgThreads) void k_pg_solve(const int32_t* __restri
               for (int i = 0; i < 6; ++i) delta[i] = ws.delta[(size_t)k * 6 + i];
 #pragma unroll
               for (int i = 0; i < 12; ++i) Tl[i] = ws.T[(size_t)k * 12 + i];
-              pg_retract(Tl, delta, Tn);
+              se3_retract(Tl, delta, Tn);
 #pragma unroll
               for (int i = 0; i < 12; ++i) ws.Tn[(size_t)k * 12 + i] = Tn[i];
             }
             __syncthreads();
             const double cn = cost_at(ws.Tn);
-            const bool conv = pg_finite(cn) && fabs(c - cn) <= fmax(P.abs_tol, P.rel_tol * c);
+            const bool conv = solver_finite(cn) && fabs(c - cn) <= fmax(P.abs_tol, P.rel_tol * c);
             if (conv || cn < c) {  // the candidate becomes the state
               for (int i = 12 + tid; i < n * 12; i += kPgThreads) ws.T[i] = ws.Tn[i];
               c = cn;
@@ -664,7 +633,7 @@ __global__ __launch_bounds__(kPgThreads) void k_pg_solve(const int32_t* __restri
         __syncthreads();
         for (int k = tid; k < n; k += kPgThreads) {
           bool ok = true;
-          for (int i = 0; i < 12; ++i) ok = ok && pg_finite(ws.T[(size_t)k * 12 + i]);
+          for (int i = 0; i < 12; ++i) ok = ok && solver_finite(ws.T[(size_t)k * 12 + i]);
           const double tx = ws.T[(size_t)k * 12 + 3], ty = ws.T[(size_t)k * 12 + 7], tz = ws.T[(size_t)k * 12 + 11];
           ok = ok && sqrt(tx * tx + ty * ty + tz * tz) <= P.max_translation;
           if (!ok) atomicOr(&s_flag, 1);
@@ -739,7 +708,7 @@ __global__ __launch_bounds__(256) void k_pg_loops(const int32_t* __restrict__ fr
 #pragma unroll
   for (int i = 0; i < 12; ++i) {
     const double v = pose[(size_t)p * 12 + i];
-    ok = ok && pg_finite(v);
+    ok = ok && solver_finite(v);
     loop_z[(size_t)p * 12 + i] = v;
   }
   double sr = 0.02, st_ = 0.20;

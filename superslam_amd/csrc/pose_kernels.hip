@@ -5,13 +5,15 @@
 //                  the cost, the 21 unique entries of H and the 6 of g together, all in fp64.  28 sums: per thread over its observations
 //                  in index order, then a butterfly over the 64 lanes, then the 4 waves in wave order by thread 0 - one fixed order,
 //                  and a workgroup sees nothing of the other pairs, so a pair's bits do not depend on the batch.  Thread 0 holds the
-//                  state (T, H, g, c, lambda), solves the 6x6 Cholesky system, applies the SE(3) exponential and decides; the others wait
-//                  at a barrier.  Two barriers per trial.  The grid is `pairs` workgroups, whatever the CU count.
+//                  state (T, H, g, c, lambda), solves the 6x6 Cholesky system, applies the SE(3) exponential (se3_retract,
+//                  solver_math.h) and decides; the others wait at a barrier.  Two barriers per trial.  The grid is `pairs` workgroups,
+//                  whatever the CU count.
 //   k_pose_gather  one thread per keyframe keypoint: the observation list out of two frames' stereo points and matches0.
 // No local array is indexed by a run-time value (every loop over the 8 observation slots and the 6x6 system is fully unrolled), so that
 // nothing lives in scratch: profiles/pose_solve_resource_usage.txt.
 #include "../../include/sship.h"
 #include "kernels.h"
+#include "solver_math.h"
 
 namespace sship {
 
@@ -20,9 +22,6 @@ namespace {
 constexpr int kPoseThreads = 256;
 constexpr int kPoseSlots = kPoseMaxObs / kPoseThreads;  // 8
 constexpr int kPoseSums = 28;                            // c, H (21, upper triangle by rows), g (6)
-
-__device__ __forceinline__ bool pose_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }  // false for NaN and +-Inf
-__device__ __forceinline__ bool pose_finitef(float v) { return fabsf(v) <= 3.4028234663852886e38f; }
 
 // One observation at pose T (row-major [R | t]): rho into acc[0], w J~^T J~ into acc[1..21], w J~^T r~ into acc[22..27].
 __device__ __forceinline__ void pose_accumulate(const double* T, const PoseK& K, float Xx, float Xy, float Xz, float uL, float uR, float v,
@@ -114,36 +113,6 @@ __device__ __forceinline__ bool pose_solve6(const double* H, const double* g, do
   return ok;
 }
 
-// Tn = T Exp(delta), delta = (omega, v): R' = R (I + A W + B W^2), t' = t + R (I + B W + C W^2) v, W = [omega]x.
-__device__ __forceinline__ void pose_retract(const double* T, const double* delta, double* Tn) {
-  const double wx = delta[0], wy = delta[1], wz = delta[2];
-  const double th2 = wx * wx + wy * wy + wz * wz;
-  double A, B, C;
-  if (th2 < 1e-12) {
-    A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0; C = 1.0 / 6.0 - th2 / 120.0;
-  } else {
-    const double th = sqrt(th2), sh = sin(0.5 * th);
-    const double st = sin(th);
-    A = st / th; B = 2.0 * sh * sh / th2; C = (th - st) / (th2 * th);
-  }
-  const double W[3][3] = {{0.0, -wz, wy}, {wz, 0.0, -wx}, {-wy, wx, 0.0}};
-  const double W2[3][3] = {{-(wy * wy + wz * wz), wx * wy, wx * wz}, {wx * wy, -(wx * wx + wz * wz), wy * wz}, {wx * wz, wy * wz, -(wx * wx + wy * wy)}};
-  double E[3][3], u[3];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) E[i][j] = (i == j ? 1.0 : 0.0) + A * W[i][j] + B * W2[i][j];
-    u[i] = delta[3 + i] + B * (W[i][0] * delta[3] + W[i][1] * delta[4] + W[i][2] * delta[5]) +
-           C * (W2[i][0] * delta[3] + W2[i][1] * delta[4] + W2[i][2] * delta[5]);
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 3; ++j) Tn[4 * i + j] = T[4 * i] * E[0][j] + T[4 * i + 1] * E[1][j] + T[4 * i + 2] * E[2][j];
-    Tn[4 * i + 3] = T[4 * i + 3] + T[4 * i] * u[0] + T[4 * i + 1] * u[1] + T[4 * i + 2] * u[2];
-  }
-}
-
 }  // namespace
 
 __global__ __launch_bounds__(kPoseThreads) void k_pose_solve(const float* __restrict__ points, const float* __restrict__ meas,
@@ -176,7 +145,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_solve(const float* __rest
 #pragma unroll
       for (int c = 0; c < 3; ++c) { ob[k][c] = px[c]; ob[k][3 + c] = pm[c]; }
 #pragma unroll
-      for (int c = 0; c < 6; ++c) p = p && pose_finitef(ob[k][c]);
+      for (int c = 0; c < 6; ++c) p = p && solver_finitef(ob[k][c]);
       if (p) {
         const double d = fmax((double)ob[k][3] - (double)ob[k][4], 1e-3);
         const double q = K.d_cond / d;
@@ -196,7 +165,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_solve(const float* __rest
 #pragma unroll
     for (int i = 0; i < 12; ++i) {
       T[i] = pose0 ? pose0[(size_t)pair * 12 + i] : ((i == 0 || i == 5 || i == 10) ? 1.0 : 0.0);
-      fin = fin && pose_finite(T[i]);
+      fin = fin && solver_finite(T[i]);
       s_T[i] = T[i];
     }
     if (!fin) status = SSHIP_POSE_BAD_INPUT;
@@ -254,7 +223,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_solve(const float* __rest
         take = true; c_init = S[0];
       } else {
         const double cn = S[0];
-        if (pose_finite(cn) && fabs(c - cn) <= fmax(K.abs_tol, K.rel_tol * c)) {
+        if (solver_finite(cn) && fabs(c - cn) <= fmax(K.abs_tol, K.rel_tol * c)) {
           take = true; done = true; status = SSHIP_POSE_CONVERGED;
         } else if (cn < c) {
           take = true; lambda /= 10.0;
@@ -280,7 +249,7 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_solve(const float* __rest
         ++trials;
         if (ok) {
           double Tn[12];
-          pose_retract(T, delta, Tn);
+          se3_retract(T, delta, Tn);
 #pragma unroll
           for (int i = 0; i < 12; ++i) s_T[i] = Tn[i];
           break;

@@ -16,13 +16,13 @@ the window smoother's poses and the pose solver's loop verifications.
 Arguments are validated here as the library validates them (ValueError); the device-tensor calls raise SshipError on a run-time failure."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from collections import namedtuple
 
 import numpy as np
 
 from . import _lib
+from . import _solver_base as _base
 
 MAX_NODES, MAX_LOOPS, MAX_GRAPHS, RESIDENT = 4096, 128, 65535, 256
 CONVERGED, ITER_CAP, STALLED, TOO_FEW, BAD_INPUT, DIVERGED = 0, 1, 2, 3, 4, 5
@@ -35,24 +35,7 @@ LoopRecords = namedtuple("LoopRecords", "ij z sigma k2 enable")
 
 
 def validate_params(p: dict) -> dict:
-    unknown = set(p) - set(DEFAULTS)
-    if unknown:
-        raise ValueError(f"unknown parameters: {sorted(unknown)}")
-    p = dict(DEFAULTS, **p)
-    for k, v in p.items():
-        if k != "max_iterations" and math.isnan(float(v)):
-            raise ValueError(f"{k} is NaN")
-    for k in ("odom_sigma_rot", "odom_sigma_trans", "max_translation"):
-        if not (p[k] > 0 and math.isfinite(p[k])):
-            raise ValueError(f"{k} must be finite and > 0")
-    if not p["lambda0"] > 0 or p["lambda_max"] < p["lambda0"] or math.isinf(p["lambda_max"]):
-        raise ValueError("lambda0 must be > 0 and lambda_max finite and >= lambda0")
-    for k in ("abs_tol", "rel_tol"):
-        if p[k] < 0:
-            raise ValueError(f"{k} is negative")
-    if int(p["max_iterations"]) < 1:
-        raise ValueError("max_iterations must be >= 1")
-    return p
+    return _base.validate_params(p, DEFAULTS, ("odom_sigma_rot", "odom_sigma_trans", "max_translation"), ("abs_tol", "rel_tol"))
 
 
 def validate_sizes(max_nodes, max_loops, max_graphs):
@@ -74,57 +57,16 @@ def workspace_slice_bytes(max_nodes: int, max_loops: int) -> int:
     return (b + 15) // 16 * 16
 
 
-class PoseGraph:
+class PoseGraph(_base.SolverBase):
+    _prefix, _params_struct, _batch = "pg", _lib.PgParams, ("G", "graphs")
+
     def __init__(self, max_nodes: int, max_loops: int, max_graphs: int = 1, **params):
+        super().__init__()
         self.max_nodes, self.max_loops, self.max_graphs = validate_sizes(max_nodes, max_loops, max_graphs)
         self.params = validate_params(params)
-        self._h = None
-        self.last_error = ""
 
-    def initialize(self) -> bool:
-        try:
-            if not _lib._inited:
-                _lib.init()
-            L = _lib.lib()
-            h = C.c_void_p()
-            _lib.check(L.sship_pg_create(self.max_nodes, self.max_loops, self.max_graphs, C.byref(h)))
-            self._h = h
-            p = _lib.PgParams(*[self.params[k] for k, _ in _lib.PgParams._fields_[:-1]], int(self.params["max_iterations"]))
-            _lib.check(L.sship_pg_set_params(h, C.byref(p)))
-            return True
-        except _lib.SshipError as e:
-            self.last_error = str(e)
-            self.close()
-            return False
-
-    def close(self):
-        if self._h is not None:
-            _lib.lib().sship_pg_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _need(self, who):
-        if self._h is None:
-            raise _lib.SshipError(_lib.ERR_INVALID, f"PoseGraph.{who}: not initialised")
-
-    def _graphs(self, t, tail, dtype, name):
-        if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or t.dtype != dtype:
-            raise ValueError(f"{name} must be {dtype} [G, {', '.join(str(v) for v in tail)}], got {t.dtype} {tuple(t.shape)}")
-        g = int(t.shape[0])
-        if not 1 <= g <= self.max_graphs:
-            raise ValueError(f"graphs must be in [1, {self.max_graphs}], got {g}")
-        return g
-
-    @staticmethod
-    def _device(tensors):
-        for t in tensors:
-            if t is not None and not (t.is_cuda and t.is_contiguous()):
-                raise ValueError("the tensors must be contiguous CUDA tensors")
+    def _create_args(self):
+        return self.max_nodes, self.max_loops, self.max_graphs
 
     @staticmethod
     def _is(t, shape, dtype, name, optional=False):
@@ -141,7 +83,7 @@ class PoseGraph:
         import torch
 
         N, L = self.max_nodes, self.max_loops
-        g = self._graphs(pose0, (N, 12), torch.float64, "pose0")
+        g = self._batch_of(pose0, (N, 12), torch.float64, "pose0")
         self._is(odom_z, (g, N - 1, 12), torch.float64, "odom_z")
         self._is(odom_sigma, (g, N - 1, 6), torch.float64, "odom_sigma", optional=True)
         self._is(n_nodes, (g,), torch.int32, "n_nodes", optional=True)
@@ -203,7 +145,7 @@ class PoseGraph:
         """pose f64 [G, N, 12] (the window smoother's output) -> odom_z f64 [G, N - 1, 12].  Asynchronous, one launch."""
         import torch
 
-        g = self._graphs(pose, (self.max_nodes, 12), torch.float64, "pose")
+        g = self._batch_of(pose, (self.max_nodes, 12), torch.float64, "pose")
         self._device((pose,))
         self._need("odometry_from_poses")
         out = torch.empty((g, self.max_nodes - 1, 12), dtype=torch.float64, device=pose.device)
@@ -219,7 +161,7 @@ class PoseGraph:
         L = self.max_loops
         if L < 1:
             raise ValueError("the handle has max_loops == 0")
-        g = self._graphs(frm, (L,), torch.int32, "frm")
+        g = self._batch_of(frm, (L,), torch.int32, "frm")
         self._is(to, (g, L), torch.int32, "to")
         self._is(pose, (g, L, 12), torch.float64, "pose")
         self._is(stats, (g, L, 4), torch.int32, "stats")
@@ -238,13 +180,6 @@ class PoseGraph:
                                                                     int(min_inliers), float(noise_base), out.ij.data_ptr(), out.z.data_ptr(),
                                                                     out.sigma.data_ptr(), out.k2.data_ptr(), out.enable.data_ptr(), s))
         return out
-
-    def bench(self, iters: int = 20) -> float:
-        """Mean milliseconds of the last solve call's launch (sship_pg_bench)."""
-        self._need("bench")
-        ms = C.c_float()
-        _lib.check(_lib.lib().sship_pg_bench(self._h, int(iters), C.byref(ms)))
-        return ms.value
 
 
 def close_loops_batch(pg: PoseGraph, window_pose, frm, to, loop_pose, loop_stats, n_nodes=None, min_inliers: int = 30,

@@ -13,13 +13,13 @@ front-end leaves on the device.
 Arguments are validated here as the library validates them (ValueError); the device-tensor calls raise SshipError on a run-time failure."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass
 
 import numpy as np
 
 from . import _lib
+from . import _solver_base as _base
 
 MAX_OBS, MAX_PAIRS = 2048, 65535
 CONVERGED, ITER_CAP, STALLED, TOO_FEW, BAD_INPUT = 0, 1, 2, 3, 4
@@ -59,28 +59,14 @@ def validate_camera(camera):
 
 
 def validate_params(p: dict) -> dict:
-    unknown = set(p) - set(DEFAULTS)
-    if unknown:
-        raise ValueError(f"unknown parameters: {sorted(unknown)}")
-    p = dict(DEFAULTS, **p)
-    for k, v in p.items():
-        if k != "max_iterations" and math.isnan(float(v)):
-            raise ValueError(f"{k} is NaN")
-    for k in ("sigma_px", "sigma_d0", "cond_depth", "huber_k2"):
-        if not (p[k] > 0 and math.isfinite(p[k])):
-            raise ValueError(f"{k} must be finite and > 0")
-    if not p["lambda0"] > 0 or p["lambda_max"] < p["lambda0"] or math.isinf(p["lambda_max"]):
-        raise ValueError("lambda0 must be > 0 and lambda_max finite and >= lambda0")
-    for k in ("abs_tol", "rel_tol", "inlier_px"):
-        if p[k] < 0:
-            raise ValueError(f"{k} is negative")
-    if int(p["max_iterations"]) < 1:
-        raise ValueError("max_iterations must be >= 1")
-    return p
+    return _base.validate_params(p, DEFAULTS, ("sigma_px", "sigma_d0", "cond_depth", "huber_k2"), ("abs_tol", "rel_tol", "inlier_px"))
 
 
-class PoseSolver:
+class PoseSolver(_base.SolverBase):
+    _prefix, _params_struct, _batch = "pose", _lib.PoseParams, ("P", "pairs")
+
     def __init__(self, camera, max_obs: int, max_pairs: int = 1, **params):
+        super().__init__()
         self.camera = validate_camera(camera)
         self.max_obs, self.max_pairs = int(max_obs), int(max_pairs)
         if not 1 <= self.max_obs <= MAX_OBS:
@@ -88,40 +74,9 @@ class PoseSolver:
         if not 1 <= self.max_pairs <= MAX_PAIRS:
             raise ValueError(f"max_pairs must be in [1, {MAX_PAIRS}], got {max_pairs}")
         self.params = validate_params(params)
-        self._h = None
-        self.last_error = ""
 
-    def initialize(self) -> bool:
-        try:
-            if not _lib._inited:
-                _lib.init()
-            L = _lib.lib()
-            h = C.c_void_p()
-            _lib.check(L.sship_pose_create(self.max_obs, self.max_pairs, C.byref(h)))
-            self._h = h
-            _lib.check(L.sship_pose_set_camera(h, *self.camera))
-            p = _lib.PoseParams(*[self.params[k] for k, _ in _lib.PoseParams._fields_[:-1]], int(self.params["max_iterations"]))
-            _lib.check(L.sship_pose_set_params(h, C.byref(p)))
-            return True
-        except _lib.SshipError as e:
-            self.last_error = str(e)
-            self.close()
-            return False
-
-    def close(self):
-        if self._h is not None:
-            _lib.lib().sship_pose_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _need(self, who):
-        if self._h is None:
-            raise _lib.SshipError(_lib.ERR_INVALID, f"PoseSolver.{who}: not initialised")
+    def _create_args(self):
+        return self.max_obs, self.max_pairs
 
     def solve_batch(self, points, meas, valid, pose0=None, stream=None, inliers: bool = True) -> PoseBatch:
         """Asynchronous on `stream` (default: torch's current stream); every output entry is written."""
@@ -136,9 +91,7 @@ class PoseSolver:
             raise ValueError(f"points / meas must be float32 and valid uint8 [{pairs}, {self.max_obs}]")
         if pose0 is not None and (pose0.dtype != torch.float64 or tuple(pose0.shape) != (pairs, 12)):
             raise ValueError(f"pose0 must be float64 [{pairs}, 12]")
-        for t in (points, meas, valid) + (() if pose0 is None else (pose0,)):
-            if not (t.is_cuda and t.is_contiguous()):
-                raise ValueError("the tensors must be contiguous CUDA tensors")
+        self._device((points, meas, valid, pose0))
         self._need("solve_batch")
         dev = points.device
         out = PoseBatch(torch.empty((pairs, 12), dtype=torch.float64, device=dev), torch.empty((pairs, 4), dtype=torch.int32, device=dev),
@@ -187,9 +140,7 @@ class PoseSolver:
             raise ValueError(f"pairs must be in [1, {self.max_pairs}], got {pairs}")
         if n0.dtype != torch.int32 or n1.dtype != torch.int32 or n0.numel() != n1.numel() or n0.numel() not in (pairs, 2 * pairs):
             raise ValueError(f"n0 and n1 must be int32 with {pairs} or {2 * pairs} entries")
-        for t in (stereo0, has_depth0, stereo1, has_depth1, matches0, n0, n1):
-            if not (t.is_cuda and t.is_contiguous()):
-                raise ValueError("the tensors must be contiguous CUDA tensors")
+        self._device((stereo0, has_depth0, stereo1, has_depth1, matches0, n0, n1))
         self._need("obs_from_matches")
         dev = matches0.device
         points, meas = torch.empty(shape3, dtype=torch.float32, device=dev), torch.empty(shape3, dtype=torch.float32, device=dev)
@@ -200,13 +151,6 @@ class PoseSolver:
                                                                        n0.numel() // pairs, pairs, points.data_ptr(), meas.data_ptr(),
                                                                        valid.data_ptr(), s))
         return points, meas, valid
-
-    def bench(self, iters: int = 20) -> float:
-        """Mean milliseconds of the last solve call's launch (sship_pose_bench)."""
-        self._need("bench")
-        ms = C.c_float()
-        _lib.check(_lib.lib().sship_pose_bench(self._h, int(iters), C.byref(ms)))
-        return ms.value
 
 
 def track_batch(solver: PoseSolver, kp_key, n_key, m_key, kp_frame, n_frame, m_frame, matches0, pose0=None, min_disparity: float = 1.0,

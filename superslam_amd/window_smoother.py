@@ -13,13 +13,12 @@ bookkeeping that builds its track ids from what the front-end leaves on the devi
 Arguments are validated here as the library validates them (ValueError); the device-tensor calls raise SshipError on a run-time failure."""
 from __future__ import annotations
 
-import ctypes as C
-import math
 from collections import namedtuple
 
 import numpy as np
 
 from . import _lib
+from . import _solver_base as _base
 from .pose_solver import validate_camera  # the same camera, the same refusals
 
 MAX_KEYFRAMES, MAX_OBS, MAX_LANDMARKS, MAX_WINDOWS = 16, 2048, 32768, 65535
@@ -31,24 +30,7 @@ WindowResult = namedtuple("WindowResult", "pose n_obs n_landmarks trials status 
 
 
 def validate_params(p: dict) -> dict:
-    unknown = set(p) - set(DEFAULTS)
-    if unknown:
-        raise ValueError(f"unknown parameters: {sorted(unknown)}")
-    p = dict(DEFAULTS, **p)
-    for k, v in p.items():
-        if k != "max_iterations" and math.isnan(float(v)):
-            raise ValueError(f"{k} is NaN")
-    for k in ("sigma_px", "huber_k2"):
-        if not (p[k] > 0 and math.isfinite(p[k])):
-            raise ValueError(f"{k} must be finite and > 0")
-    if not p["lambda0"] > 0 or p["lambda_max"] < p["lambda0"] or math.isinf(p["lambda_max"]):
-        raise ValueError("lambda0 must be > 0 and lambda_max finite and >= lambda0")
-    for k in ("abs_tol", "rel_tol"):
-        if p[k] < 0:
-            raise ValueError(f"{k} is negative")
-    if int(p["max_iterations"]) < 1:
-        raise ValueError("max_iterations must be >= 1")
-    return p
+    return _base.validate_params(p, DEFAULTS, ("sigma_px", "huber_k2"), ("abs_tol", "rel_tol"))
 
 
 def validate_sizes(max_keyframes, max_obs, max_landmarks, max_windows):
@@ -65,66 +47,24 @@ def validate_sizes(max_keyframes, max_obs, max_landmarks, max_windows):
     return K, N, L, W
 
 
-class WindowSmoother:
+class WindowSmoother(_base.SolverBase):
+    _prefix, _params_struct, _batch = "ba", _lib.BaParams, ("W", "windows")
+
     def __init__(self, camera, max_keyframes: int = 8, max_obs: int = 600, max_landmarks=None, max_windows: int = 1, **params):
+        super().__init__()
         self.camera = validate_camera(camera)
         self.max_keyframes, self.max_obs, self.max_landmarks, self.max_windows = validate_sizes(max_keyframes, max_obs, max_landmarks, max_windows)
         self.params = validate_params(params)
-        self._h = None
-        self.last_error = ""
 
-    def initialize(self) -> bool:
-        try:
-            if not _lib._inited:
-                _lib.init()
-            L = _lib.lib()
-            h = C.c_void_p()
-            _lib.check(L.sship_ba_create(self.max_keyframes, self.max_obs, self.max_landmarks, self.max_windows, C.byref(h)))
-            self._h = h
-            _lib.check(L.sship_ba_set_camera(h, *self.camera))
-            p = _lib.BaParams(*[self.params[k] for k, _ in _lib.BaParams._fields_[:-1]], int(self.params["max_iterations"]))
-            _lib.check(L.sship_ba_set_params(h, C.byref(p)))
-            return True
-        except _lib.SshipError as e:
-            self.last_error = str(e)
-            self.close()
-            return False
-
-    def close(self):
-        if self._h is not None:
-            _lib.lib().sship_ba_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _need(self, who):
-        if self._h is None:
-            raise _lib.SshipError(_lib.ERR_INVALID, f"WindowSmoother.{who}: not initialised")
-
-    def _windows(self, t, tail, dtype, name):
-        if t.dim() != 1 + len(tail) or tuple(t.shape[1:]) != tail or t.dtype != dtype:
-            raise ValueError(f"{name} must be {dtype} [W, {', '.join(str(v) for v in tail)}], got {t.dtype} {tuple(t.shape)}")
-        w = int(t.shape[0])
-        if not 1 <= w <= self.max_windows:
-            raise ValueError(f"windows must be in [1, {self.max_windows}], got {w}")
-        return w
-
-    @staticmethod
-    def _device(tensors):
-        for t in tensors:
-            if not (t.is_cuda and t.is_contiguous()):
-                raise ValueError("the tensors must be contiguous CUDA tensors")
+    def _create_args(self):
+        return self.max_keyframes, self.max_obs, self.max_landmarks, self.max_windows
 
     def solve_batch(self, meas, track, pose0, n_kf=None, stream=None, landmarks: bool = True) -> WindowBatch:
         """Asynchronous on `stream` (default: torch's current stream); every output entry is written."""
         import torch
 
         K, N, L = self.max_keyframes, self.max_obs, self.max_landmarks
-        w = self._windows(meas, (K, N, 3), torch.float32, "meas")
+        w = self._batch_of(meas, (K, N, 3), torch.float32, "meas")
         if tuple(track.shape) != (w, K, N) or track.dtype != torch.int32:
             raise ValueError(f"track must be int32 [{w}, {K}, {N}]")
         if tuple(pose0.shape) != (w, K, 12) or pose0.dtype != torch.float64:
@@ -165,7 +105,7 @@ class WindowSmoother:
         import torch
 
         K, N = self.max_keyframes, self.max_obs
-        w = self._windows(has_depth, (K, N), torch.uint8, "has_depth")
+        w = self._batch_of(has_depth, (K, N), torch.uint8, "has_depth")
         if tuple(matches.shape) != (w, K - 1, N) or matches.dtype != torch.int32:
             raise ValueError(f"matches must be int32 [{w}, {K - 1}, {N}]")
         if tuple(n.shape) != (w, K) or n.dtype != torch.int32:
@@ -181,13 +121,6 @@ class WindowSmoother:
         _lib.check(_lib.lib().sship_ba_tracks_from_matches_batch_device(self._h, has_depth.data_ptr(), matches.data_ptr(), n.data_ptr(),
                                                                         None if n_kf is None else n_kf.data_ptr(), w, track.data_ptr(), s))
         return track
-
-    def bench(self, iters: int = 20) -> float:
-        """Mean milliseconds of the last solve call's launch (sship_ba_bench)."""
-        self._need("bench")
-        ms = C.c_float()
-        _lib.check(_lib.lib().sship_ba_bench(self._h, int(iters), C.byref(ms)))
-        return ms.value
 
 
 def smooth_batch(ws: WindowSmoother, stereo, has_depth, n, matches, pose0, n_kf=None, stream=None):

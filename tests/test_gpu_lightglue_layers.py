@@ -278,6 +278,24 @@ def test_counts_above_capacity_are_clamped(lg):
     assert torch.equal(ok[0], bad[0]) and torch.allclose(ok[1], bad[1])
 
 
+@pytest.mark.parametrize("n0,n1,seed", [(1, 1, 34), (7, 5, 35)])
+def test_stage_bench_hook_times_every_stage_and_leaves_the_matcher_as_it_was(hip, lg, n0, n1, seed):
+    """sship_lg_bench_stage re-launches one stage over the state of the last match: every stage id the benchmark asks for reports a time,
+    and the same match repeated after them gives the same bits (stages 3 / 4 update the residual stream in place; the hook puts it back)."""
+    import ctypes as C
+
+    from superslam_amd import _lib
+
+    k0, d0, k1, d1 = _random_sets(n0, n1, seed)
+    before = lg.match(_px(k0), d0, _px(k1), d1)
+    for stage in range(8):
+        ms = C.c_float(0)
+        _lib.check(hip.sship_lg_bench_stage(lg._h, stage, 2, C.byref(ms)))
+        assert ms.value > 0, stage
+    after = lg.match(_px(k0), d0, _px(k1), d1)
+    assert before.matches0.tobytes() == after.matches0.tobytes() and before.mscores0.tobytes() == after.mscores0.tobytes()
+
+
 def test_loader_accepts_the_raw_checkpoint_key_layout(hip, lg, weights_dir, tmp_path):
     """self_attn.{i}.* / cross_attn.{i}.* (the published .pth layout) load to the same matcher as the module names."""
     from superslam_amd import LightGlue

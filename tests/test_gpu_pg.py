@@ -140,6 +140,26 @@ def test_solve_host_equals_the_batch_call():
     pg.close()
 
 
+def test_bench_hook_reports_a_time_and_leaves_the_solve_as_it_was():
+    """sship_pg_bench re-runs the last solve call's launch: it reports a time, and the same solve repeated after it gives the same bytes."""
+    import torch
+
+    g = R.make_graph(61, 4, loops=1)
+    pg = graph(4, 1, 1)
+    args = [torch.from_numpy(np.ascontiguousarray(a[None])).cuda() for a in (g.pose0, g.odom_z, g.loop_ij, g.loop_z, g.loop_sigma, g.loop_k2)]
+
+    def solve():
+        out = pg.optimize_batch(*args)
+        torch.cuda.synchronize()
+        return [t.cpu().numpy().tobytes() for t in out]
+
+    before = solve()
+    assert np.frombuffer(before[1], np.int32)[3] == R.CONVERGED
+    assert pg.bench(2) > 0
+    assert solve() == before
+    pg.close()
+
+
 def test_no_loop_handle_and_default_n_nodes():
     import torch
 
