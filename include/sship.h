@@ -635,6 +635,80 @@ int sship_pose_obs_from_matches_batch_device(const sship_pose* ps, const float* 
 int sship_pose_bench(sship_pose* ps, int iters, float* avg_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * RANSAC pose seed and inlier gate - the hypothesise-and-verify stage between "matches" and "solve": the pose and the inlier set of
+ * `pairs` pairs per call when the seed is unknown and many matches are wrong (a loop partner metres and tens of degrees away, which
+ * src/LoopCloser.cc:72 hands to the local solve from the identity; the observations of sship_nn_*).  Device-resident, no early exit, no
+ * adaptive count.  The reference has no such stage; the rule is this library's own and is stated here in full.  Camera, observation layout
+ * and pose are the pose-only solver's: (fx, fy, cx, cy, baseline), observation k = (X, (uL, uR, v), valid), pose Twc = [R | t] row-major
+ * 3x4 with X = R Y + t for a point Y in the frame's camera.  Inputs are fp32 and are widened on load; all arithmetic is fp64, every
+ * product, quotient, square root and sum rounded once, in the order written below (no fused multiply-add).  The rule:
+ *   PRESENT as in sship_pose_*: the valid byte is non-zero and all six floats are finite.  SAMPLEABLE: present and the measured disparity
+ *     d = uL - uR >= min_disparity.  m = the number of sampleable observations; rank r is the r-th of them in ascending row order.
+ *   Y_k, the measurement back-projected in the frame's camera, with the formula of sship_pose_obs_from_matches_batch_device but kept in
+ *     fp64: Z = fx baseline / (uL - uR), Y_k = ((uL - cx) Z / fx, (v - cy) Z / fy, Z).
+ *   Sampling is counter-based, on 32-bit unsigned values (all arithmetic mod 2^32):
+ *     mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16.
+ *     u(h, j) = mix(mix(seed + 0x9e3779b9 * (3 h + j + 1))).
+ *     a = u(h, 0) % m;  b = u(h, 1) % (m - 1), b += (b >= a);  c = u(h, 2) % (m - 2), c += (c >= min(a, b)), then c += (c >= max(a, b)).
+ *     Three distinct ranks, a function of (seed, h, m) only - never of the pair's position in the batch.
+ *   Hypothesis h, from the observations of ranks (a, b, c) as (p0, p1, p2), once with p = X and once with p = Y:
+ *     d1 = p1 - p0, d2 = p2 - p0, n = d1 x d2, e1 = d1 / |d1|, e3 = n / |n|, e2 = e3 x e1;  |v|^2 = (v.x^2 + v.y^2) + v.z^2.
+ *     R = [e1 e2 e3]_X [e1 e2 e3]_Y^T, entry (i, j) = (e1X_i e1Y_j + e2X_i e2Y_j) + e3X_i e3Y_j.
+ *     t = mean(X) - R mean(Y), mean = ((p0 + p1) + p2) / 3, (R v)_i = (R_i0 v_0 + R_i1 v_1) + R_i2 v_2.
+ *     REJECTED (cost +Inf) unless |n|^2 > min_area2 for both triads and every entry of R and t is finite.
+ *   Score (MSAC) of a hypothesis that is not rejected: one running fp64 sum, from 0, over the PRESENT observations in ascending row order.
+ *     q = R^T (X - t), q_j = (R_0j d_0 + R_1j d_1) + R_2j d_2 with d = X - t.  thr2 = inlier_px^2.
+ *     !(q.z > 0): the term is thr2.  Otherwise r0 = (fx q.x) (1 / q.z) + cx - uL, r2 = (fy q.y) (1 / q.z) + cy - v, e2 = r0^2 + r2^2, and the
+ *     term is e2 if e2 < thr2, else thr2.  uR does not enter the score (as n_inliers of sship_pose_*, LoopCloser.cc:74-86).
+ *   Winner: the lowest cost; the lower h wins a tie.  pose = the winner's (R, t); the inlier mask and n_inliers are the present
+ *     observations with q.z > 0 && e2 < thr2 at the winner; stats = (n_present, n_inliers, best_h, status); cost = the winner's cost.
+ *   Statuses: OK;  TOO_FEW when m < 3;  NO_MODEL when every hypothesis is rejected.  In the last two the pose is the identity, the mask is
+ *     zero, n_inliers is 0, best_h is -1 and the cost is +Inf; n_present is still counted.
+ *   Exactly num_hypotheses hypotheses, h = 0 .. num_hypotheses - 1, are evaluated.
+ *   Defaults: inlier_px 3 (the reference's LoopParams); min_disparity 1, min_area2 1e-8 m^4, seed 1 and num_hypotheses 512 are this
+ *     library's own choices.
+ *   A hypothesis's cost depends on nothing but (the pair's observations, the camera, the parameters, h): a pair gives the same bits alone,
+ *     at any position of any batch, and however the hypotheses are spread over workgroups; a winner below the smaller of two
+ *     num_hypotheses that both keep it is the same for both.
+ * Handle: sship_ransac_create(max_obs 1..2048, max_pairs 1..65535).  The camera must be set before a solve.
+ * Bad arguments are refused with SSHIP_ERR_INVALID and a message before any device is touched, the handle unchanged: a NULL handle or
+ * pointer, max_obs / max_pairs / pairs / n_obs out of range, fx, fy or baseline not > 0 (or any camera value not finite), a NaN or an
+ * infinity in the params, a negative inlier_px, min_disparity or min_area2, num_hypotheses outside 1..65536.
+ * Valid create arguments without a GPU give SSHIP_ERR_NO_DEVICE.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sship_ransac sship_ransac;
+typedef struct sship_ransac_params {
+  double inlier_px, min_disparity, min_area2;
+  uint32_t seed;
+  int num_hypotheses;
+} sship_ransac_params;
+#define SSHIP_RANSAC_OK 0
+#define SSHIP_RANSAC_TOO_FEW 1
+#define SSHIP_RANSAC_NO_MODEL 2
+int sship_ransac_create(int max_obs, int max_pairs, sship_ransac** out);
+void sship_ransac_destroy(sship_ransac* rs);
+int sship_ransac_set_camera(sship_ransac* rs, double fx, double fy, double cx, double cy, double baseline);
+int sship_ransac_get_camera(const sship_ransac* rs, double* fx, double* fy, double* cx, double* cy, double* baseline); /* any output may be NULL */
+int sship_ransac_set_params(sship_ransac* rs, const sship_ransac_params* params);   /* may grow the handle's workspace: not during a solve */
+int sship_ransac_get_params(const sship_ransac* rs, sship_ransac_params* params);
+/* Throughput path, two launches (score, then argmin and mask), asynchronous on `stream` (NULL = the legacy default stream), no host
+ * synchronisation inside: points_dev / meas_dev [pairs, max_obs, 3] f32 and valid_dev [pairs, max_obs] u8 as sship_pose_solve_batch_device
+ * takes them;  pose_dev [pairs, 12] f64 and inlier_dev [pairs, max_obs] u8 (or NULL) in exactly the layouts that call takes as pose0_dev
+ * and valid_dev, so the two chain without a kernel in between;  stats_dev [pairs, 4] i32 = (n_present, n_inliers, best_h, status),
+ * cost_dev [pairs] f64.  Every entry of the outputs is written.  The handle's workspace carries the partial results between the two
+ * launches: calls on one handle must be ordered on one stream. */
+int sship_ransac_solve_batch_device(sship_ransac* rs, const float* points_dev, const float* meas_dev, const uint8_t* valid_dev, int pairs,
+                                    double* pose_dev, int32_t* stats_dev, double* cost_dev, uint8_t* inlier_dev, void* stream);
+/* One pair from host arrays: points / meas [n_obs, 3], valid [n_obs] or NULL = all; pose_out [12], stats_out [4], cost_out [1],
+ * inlier_out [n_obs] or NULL.  n_obs in 0..max_obs.  Synchronous on the handle's own stream; the same launches as the batch call with
+ * pairs = 1, hence the same bits. */
+int sship_ransac_solve_host(sship_ransac* rs, const float* points, const float* meas, const uint8_t* valid, int n_obs, double* pose_out,
+                            int32_t* stats_out, double* cost_out, uint8_t* inlier_out);
+/* Measurement hook: re-run the last solve call's launches on this handle `iters` times (over the same buffers, which the caller of a batch
+ * call keeps alive), timed with hipEvents on the handle's stream; *avg_ms = mean duration of one call's two launches. */
+int sship_ransac_bench(sship_ransac* rs, int iters, float* avg_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * Window smoother - sliding-window stereo bundle adjustment: what VoEstimator::track does at every keyframe with smoother_.optimize()
  * (src/VoEstimator.cc:316-323, src/WindowSmoother.cc): a fixed-lag window of the last keyframe poses re-optimised against all stereo
  * observations of the landmarks they share, the landmarks eliminated.  `windows` windows per call, device-resident, no GTSAM.  The
@@ -678,7 +752,8 @@ int sship_pose_bench(sship_pose* ps, int iters, float* avg_ms);
  *     point that fits both rays.  Its observations keep a Huber pull of k on the poses and its point drifts far away (finite, up to 1e7 m on
  *     the tests' scenes) while the window still ends CONVERGED or at ITER_CAP; with a fifth of the two-view tracks corrupted the poses were
  *     recovered to 0.01 - 0.12 m instead of 0.01 - 0.02 m (tests/test_ba_cpu.py pins this).  A caller whose matches carry such mismatches
- *     should gate them before the solve (the keypoint-window gate, the pose-only solver's inlier mask) or leave two-view tracks out.
+ *     should gate them before the solve (the keypoint-window gate, the inlier mask of sship_ransac_* or of the pose-only solve) or leave
+ *     two-view tracks out.
  *   Determinism: every sum runs in one fixed order - the blocks of a landmark over its slots in ascending k, the sums of a slot and of
  *     the cost per thread over its rows in index order, then lanes, then waves; every entry of S and b over the active landmarks in ascending
  *     l by one thread.  A window gives the same bits alone, inside any batch, at any batch position, and on a second call.

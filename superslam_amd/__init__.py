@@ -12,11 +12,12 @@ from .place_index import PlaceIndex  # noqa: F401
 from .pose_graph import PoseGraph, close_loops_batch  # noqa: F401
 from .rectifier import Rectifier, build_maps  # noqa: F401
 from .pose_solver import PoseSolver, track_batch  # noqa: F401
+from .ransac import RansacVerifier, verify_batch  # noqa: F401
 from .pool import DescriptorPool, DeviceDescriptors  # noqa: F401
 from .superpoint import Features, SuperPoint  # noqa: F401
 from .window_smoother import WindowSmoother, smooth_batch  # noqa: F401
 
 __all__ = ["SuperPoint", "LightGlue", "LightGlueEngine", "MatchResult", "Features", "DescriptorPool",
            "DeviceDescriptors", "FrontEndBatch", "process_stereo", "stereo_associate_batch", "EigenPlaces", "NNMatcher", "PlaceIndex", "PoseSolver",
-           "track_batch", "WindowSmoother", "smooth_batch", "PoseGraph", "close_loops_batch", "Rectifier", "build_maps",
+           "track_batch", "RansacVerifier", "verify_batch", "WindowSmoother", "smooth_batch", "PoseGraph", "close_loops_batch", "Rectifier", "build_maps",
            "rgbd_associate_batch"]

@@ -52,6 +52,11 @@ class PoseParams(C.Structure):
                 ("inlier_px", C.c_double), ("max_iterations", C.c_int)]
 
 
+class RansacParams(C.Structure):
+    _fields_ = [("inlier_px", C.c_double), ("min_disparity", C.c_double), ("min_area2", C.c_double), ("seed", C.c_uint32),
+                ("num_hypotheses", C.c_int)]
+
+
 class BaParams(C.Structure):
     _fields_ = [("sigma_px", C.c_double), ("huber_k2", C.c_double), ("lambda0", C.c_double), ("lambda_max", C.c_double),
                 ("abs_tol", C.c_double), ("rel_tol", C.c_double), ("max_iterations", C.c_int)]
@@ -170,6 +175,15 @@ _SIGS = {
     "sship_pose_solve_host": (ip, [vp, vp, vp, vp, ip, vp, vp, vp, vp, vp]),
     "sship_pose_obs_from_matches_batch_device": (ip, [vp, vp, vp, vp, vp, vp, vp, vp, ip, ip, vp, vp, vp, vp]),
     "sship_pose_bench": (ip, [vp, ip, C.POINTER(fp)]),
+    "sship_ransac_create": (ip, [ip, ip, C.POINTER(vp)]),
+    "sship_ransac_destroy": (None, [vp]),
+    "sship_ransac_set_camera": (ip, [vp, dp, dp, dp, dp, dp]),
+    "sship_ransac_get_camera": (ip, [vp, C.POINTER(dp), C.POINTER(dp), C.POINTER(dp), C.POINTER(dp), C.POINTER(dp)]),
+    "sship_ransac_set_params": (ip, [vp, C.POINTER(RansacParams)]),
+    "sship_ransac_get_params": (ip, [vp, C.POINTER(RansacParams)]),
+    "sship_ransac_solve_batch_device": (ip, [vp, vp, vp, vp, ip, vp, vp, vp, vp, vp]),
+    "sship_ransac_solve_host": (ip, [vp, vp, vp, vp, ip, vp, vp, vp, vp]),
+    "sship_ransac_bench": (ip, [vp, ip, C.POINTER(fp)]),
     "sship_ba_create": (ip, [ip, ip, ip, ip, C.POINTER(vp)]),
     "sship_ba_destroy": (None, [vp]),
     "sship_ba_set_camera": (ip, [vp, dp, dp, dp, dp, dp]),

@@ -1,4 +1,4 @@
-"""What the three solver wrappers (pose_solver, window_smoother, pose_graph) share: the parameter validator and the handle's life cycle."""
+"""What the solver wrappers (pose_solver, window_smoother, pose_graph, ransac) share: the parameter validator and the handle's life cycle."""
 from __future__ import annotations
 
 import ctypes as C
@@ -7,24 +7,26 @@ import math
 from . import _lib
 
 
-def validate_params(p: dict, defaults: dict, positive, non_negative) -> dict:
-    """`p` over `defaults`, refused as the library's *_set_params refuses it: `positive` fields must be finite and > 0, `non_negative` >= 0."""
+def validate_params(p: dict, defaults: dict, positive, non_negative, schedule: bool = True, integers=("max_iterations",)) -> dict:
+    """`p` over `defaults`, refused as the library's *_set_params refuses it: `positive` fields must be finite and > 0, `non_negative` >= 0.
+    schedule: the Levenberg-Marquardt fields (lambda0, lambda_max, max_iterations) are there and are checked; `integers` are the fields
+    that are not floating-point."""
     unknown = set(p) - set(defaults)
     if unknown:
         raise ValueError(f"unknown parameters: {sorted(unknown)}")
     p = dict(defaults, **p)
     for k, v in p.items():
-        if k != "max_iterations" and math.isnan(float(v)):
+        if k not in integers and math.isnan(float(v)):
             raise ValueError(f"{k} is NaN")
     for k in positive:
         if not (p[k] > 0 and math.isfinite(p[k])):
             raise ValueError(f"{k} must be finite and > 0")
-    if not p["lambda0"] > 0 or p["lambda_max"] < p["lambda0"] or math.isinf(p["lambda_max"]):
+    if schedule and (not p["lambda0"] > 0 or p["lambda_max"] < p["lambda0"] or math.isinf(p["lambda_max"])):
         raise ValueError("lambda0 must be > 0 and lambda_max finite and >= lambda0")
     for k in non_negative:
         if p[k] < 0:
             raise ValueError(f"{k} is negative")
-    if int(p["max_iterations"]) < 1:
+    if schedule and int(p["max_iterations"]) < 1:
         raise ValueError("max_iterations must be >= 1")
     return p
 
@@ -32,8 +34,9 @@ def validate_params(p: dict, defaults: dict, positive, non_negative) -> dict:
 class SolverBase:
     """A subclass sets `_prefix` (its entries are sship_<prefix>_create / _destroy / _set_camera / _set_params / _bench), `_params_struct`,
     `_batch` (the letter and the noun of its batch dimension; max_<noun> bounds it), `self.params`, `self.camera` where the handle takes
-    one, and `_create_args()`."""
+    one, and `_create_args()`; `_int_params` names the integer fields of its params struct."""
     _prefix = _params_struct = _batch = None
+    _int_params = ("max_iterations",)
     camera = None
 
     def __init__(self):
@@ -53,7 +56,7 @@ class SolverBase:
             if self.camera is not None:
                 _lib.check(self._entry("set_camera")(h, *self.camera))
             S = self._params_struct
-            p = S(*[self.params[k] for k, _ in S._fields_[:-1]], int(self.params["max_iterations"]))
+            p = S(*[int(self.params[k]) if k in self._int_params else self.params[k] for k, _ in S._fields_])
             _lib.check(self._entry("set_params")(h, C.byref(p)))
             return True
         except _lib.SshipError as e:

@@ -368,7 +368,7 @@ static int bench_loop(hipStream_t s, int iters, Run run, float* avg_ms) {
   return SSHIP_OK;
 }
 
-// What the handles with nothing but a stream and RAII members to release share (nn, index, pose, ba, pg, rect).
+// What the handles with nothing but a stream and RAII members to release share (nn, index, pose, ransac, ba, pg, rect).
 template <class Handle>
 static void destroy_handle(Handle* h) {
   if (!h) return;
@@ -3036,6 +3036,152 @@ extern "C" int sship_pose_bench(sship_pose* ps, int iters, float* avg_ms) {
   const PoseK k = pose_constants(ps);
   auto run = [&]() -> hipError_t {
     launch_pose_solve(l.points, l.meas, l.valid, l.pose0, ps->max_obs, l.pairs, k, l.pose, l.stats, l.cost, l.inlier, s);
+    return hipGetLastError();
+  };
+  return bench_loop(s, iters, run, avg_ms);
+}
+
+// ====================================================================================================
+// RANSAC pose seed and inlier gate (include/sship.h "RANSAC pose seed and inlier gate"; csrc/ransac_kernels.hip)
+// ====================================================================================================
+struct sship_ransac {
+  int max_obs = 0, max_pairs = 0;
+  StereoCamera cam;
+  sship_ransac_params prm{3.0, 1.0, 1e-8, 1u, 512};
+  hipStream_t stream = nullptr;
+  DevBuf workspace;                                            // [max_pairs, splits] records between the two launches
+  DevBuf points1, meas1, valid1, pose1, stats1, cost1, inlier1;   // sship_ransac_solve_host: one staged pair and its results
+  PinBuf h_in, h_out;
+  // the last solve call's arguments (sship_ransac_bench re-runs its launches; the caller keeps a batch call's buffers alive until then)
+  struct Last { const float* points = nullptr; const float* meas = nullptr; const uint8_t* valid = nullptr; int pairs = 0;
+                double* pose = nullptr; int32_t* stats = nullptr; double* cost = nullptr; uint8_t* inlier = nullptr; } last;
+};
+static RansacK ransac_constants(const sship_ransac* rs) {
+  RansacK k;
+  k.fx = rs->cam.fx; k.fy = rs->cam.fy; k.cx = rs->cam.cx; k.cy = rs->cam.cy; k.baseline = rs->cam.baseline;
+  k.thr2 = rs->prm.inlier_px * rs->prm.inlier_px; k.min_disparity = rs->prm.min_disparity; k.min_area2 = rs->prm.min_area2;
+  k.seed = rs->prm.seed; k.num_hypotheses = rs->prm.num_hypotheses;
+  return k;
+}
+extern "C" int sship_ransac_create(int max_obs, int max_pairs, sship_ransac** out) {
+  if (!out) return fail(SSHIP_ERR_INVALID, "ransac_create: null argument");
+  *out = nullptr;
+  if (max_obs < 1 || max_obs > kPoseMaxObs) return fail(SSHIP_ERR_INVALID, "ransac_create: max_obs must be in [1, 2048]");
+  if (max_pairs < 1 || max_pairs > kPoseMaxPairs) return fail(SSHIP_ERR_INVALID, "ransac_create: max_pairs must be in [1, 65535]");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  std::unique_ptr<sship_ransac, void (*)(sship_ransac*)> rs(new sship_ransac(), sship_ransac_destroy);
+  rs->max_obs = max_obs; rs->max_pairs = max_pairs;
+  const size_t n = (size_t)max_obs;
+  SSHIP_HIP_CHECK(rs->workspace.ensure(ransac_workspace_bytes(max_pairs, rs->prm.num_hypotheses)));
+  SSHIP_HIP_CHECK(rs->points1.ensure(n * 12));
+  SSHIP_HIP_CHECK(rs->meas1.ensure(n * 12));
+  SSHIP_HIP_CHECK(rs->valid1.ensure(n));
+  SSHIP_HIP_CHECK(rs->inlier1.ensure(n));
+  SSHIP_HIP_CHECK(rs->pose1.ensure(96));
+  SSHIP_HIP_CHECK(rs->stats1.ensure(16));
+  SSHIP_HIP_CHECK(rs->cost1.ensure(8));
+  SSHIP_HIP_CHECK(rs->h_in.ensure(n * 25));
+  SSHIP_HIP_CHECK(rs->h_out.ensure(128 + n));
+  SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&rs->stream, hipStreamDefault));
+  *out = rs.release();
+  return SSHIP_OK;
+}
+extern "C" void sship_ransac_destroy(sship_ransac* rs) { destroy_handle(rs); }
+extern "C" int sship_ransac_set_camera(sship_ransac* rs, double fx, double fy, double cx, double cy, double baseline) {
+  return camera_set(rs ? &rs->cam : nullptr, "ransac_set_camera", fx, fy, cx, cy, baseline);
+}
+extern "C" int sship_ransac_get_camera(const sship_ransac* rs, double* fx, double* fy, double* cx, double* cy, double* baseline) {
+  return camera_get(rs ? &rs->cam : nullptr, "ransac_get_camera", fx, fy, cx, cy, baseline);
+}
+extern "C" int sship_ransac_set_params(sship_ransac* rs, const sship_ransac_params* p) {
+  if (!rs || !p) return fail(SSHIP_ERR_INVALID, "ransac_set_params: null argument");
+  const double all[3] = {p->inlier_px, p->min_disparity, p->min_area2};
+  for (double v : all)
+    if (!std::isfinite(v)) return fail(SSHIP_ERR_INVALID, "ransac_set_params: a parameter is NaN or infinite");
+  if (p->inlier_px < 0.0 || p->min_disparity < 0.0 || p->min_area2 < 0.0)
+    return fail(SSHIP_ERR_INVALID, "ransac_set_params: inlier_px, min_disparity or min_area2 is negative");
+  if (p->num_hypotheses < 1 || p->num_hypotheses > 65536) return fail(SSHIP_ERR_INVALID, "ransac_set_params: num_hypotheses must be in [1, 65536]");
+  const size_t need = ransac_workspace_bytes(rs->max_pairs, p->num_hypotheses);
+  if (need > rs->workspace.bytes) {   // the old workspace may still be read by a launch in flight
+    bind_thread();
+    SSHIP_HIP_CHECK(hipDeviceSynchronize());
+    SSHIP_HIP_CHECK(rs->workspace.ensure(need));
+  }
+  rs->prm = *p;
+  return SSHIP_OK;
+}
+extern "C" int sship_ransac_get_params(const sship_ransac* rs, sship_ransac_params* p) {
+  if (!rs || !p) return fail(SSHIP_ERR_INVALID, "ransac_get_params: null argument");
+  *p = rs->prm;
+  return SSHIP_OK;
+}
+static int ransac_launch(sship_ransac* rs, const float* points, const float* meas, const uint8_t* valid, int pairs, double* pose, int32_t* stats,
+                         double* cost, uint8_t* inlier, hipStream_t s) {
+  sship_ransac::Last& l = rs->last;
+  l.points = points; l.meas = meas; l.valid = valid; l.pairs = pairs; l.pose = pose; l.stats = stats; l.cost = cost; l.inlier = inlier;
+  launch_ransac_solve(points, meas, valid, rs->max_obs, pairs, ransac_constants(rs), rs->workspace.p, pose, stats, cost, inlier, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  return SSHIP_OK;
+}
+extern "C" int sship_ransac_solve_batch_device(sship_ransac* rs, const float* points, const float* meas, const uint8_t* valid, int pairs,
+                                               double* pose, int32_t* stats, double* cost, uint8_t* inlier, void* stream) {
+  if (!rs || !points || !meas || !valid || !pose || !stats || !cost) return fail(SSHIP_ERR_INVALID, "ransac_solve_batch_device: null argument");
+  if (pairs < 1 || pairs > rs->max_pairs) return fail(SSHIP_ERR_INVALID, "ransac_solve_batch_device: pairs must be in [1, max_pairs]");
+  if (!rs->cam.set) return fail(SSHIP_ERR_INVALID, "ransac_solve_batch_device: set the camera first (sship_ransac_set_camera)");
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  if (int rc = ransac_launch(rs, points, meas, valid, pairs, pose, stats, cost, inlier, s)) return rc;
+  g_timer.mark("ransac_solve", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_ransac_solve_host(sship_ransac* rs, const float* points, const float* meas, const uint8_t* valid, int n_obs, double* pose_out,
+                                       int32_t* stats_out, double* cost_out, uint8_t* inlier_out) {
+  if (!rs || !pose_out || !stats_out || !cost_out) return fail(SSHIP_ERR_INVALID, "ransac_solve_host: null argument");
+  if (n_obs < 0 || n_obs > rs->max_obs) return fail(SSHIP_ERR_INVALID, "ransac_solve_host: n_obs must be in [0, max_obs]");
+  if (n_obs > 0 && (!points || !meas)) return fail(SSHIP_ERR_INVALID, "ransac_solve_host: null argument");
+  if (!rs->cam.set) return fail(SSHIP_ERR_INVALID, "ransac_solve_host: set the camera first (sship_ransac_set_camera)");
+  bind_thread();
+  hipStream_t s = rs->stream;
+  const size_t n = (size_t)rs->max_obs, m = (size_t)n_obs;
+  // pinned staging: points | meas | valid, rows >= n_obs absent
+  char* hin = static_cast<char*>(rs->h_in.p);
+  float* hp = reinterpret_cast<float*>(hin);
+  float* hm = reinterpret_cast<float*>(hin + n * 12);
+  uint8_t* hv = reinterpret_cast<uint8_t*>(hin + n * 24);
+  memset(hin, 0, n * 25);
+  if (m) { memcpy(hp, points, m * 12); memcpy(hm, meas, m * 12); }
+  for (size_t i = 0; i < m; ++i) hv[i] = valid ? (valid[i] != 0) : 1;
+  SSHIP_HIP_CHECK(hipMemcpyAsync(rs->points1.p, hp, n * 12, hipMemcpyHostToDevice, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(rs->meas1.p, hm, n * 12, hipMemcpyHostToDevice, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(rs->valid1.p, hv, n, hipMemcpyHostToDevice, s));
+  if (int rc = ransac_launch(rs, rs->points1.as<float>(), rs->meas1.as<float>(), rs->valid1.as<uint8_t>(), 1, rs->pose1.as<double>(),
+                             rs->stats1.as<int32_t>(), rs->cost1.as<double>(), rs->inlier1.as<uint8_t>(), s))
+    return rc;
+  char* hout = static_cast<char*>(rs->h_out.p);   // pose (96) | cost (8) | stats (16) | inlier
+  SSHIP_HIP_CHECK(hipMemcpyAsync(hout, rs->pose1.p, 96, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(hout + 96, rs->cost1.p, 8, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(hout + 112, rs->stats1.p, 16, hipMemcpyDeviceToHost, s));
+  if (inlier_out && m) SSHIP_HIP_CHECK(hipMemcpyAsync(hout + 128, rs->inlier1.p, m, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipStreamSynchronize(s));
+  memcpy(pose_out, hout, 96);
+  memcpy(cost_out, hout + 96, 8);
+  memcpy(stats_out, hout + 112, 16);
+  if (inlier_out && m) memcpy(inlier_out, hout + 128, m);
+  return SSHIP_OK;
+}
+// Measurement hook (include/sship.h): the last solve call's two launches re-run `iters` times on the handle's stream.
+extern "C" int sship_ransac_bench(sship_ransac* rs, int iters, float* avg_ms) {
+  if (!rs || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "ransac_bench: bad arguments");
+  if (rs->last.pairs <= 0) return fail(SSHIP_ERR_INVALID, "ransac_bench: run a solve on this handle first");
+  bind_thread();
+  hipStream_t s = rs->stream;
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
+  const sship_ransac::Last& l = rs->last;
+  const RansacK k = ransac_constants(rs);
+  auto run = [&]() -> hipError_t {
+    launch_ransac_solve(l.points, l.meas, l.valid, rs->max_obs, l.pairs, k, rs->workspace.p, l.pose, l.stats, l.cost, l.inlier, s);
     return hipGetLastError();
   };
   return bench_loop(s, iters, run, avg_ms);

@@ -254,6 +254,22 @@ void launch_pose_gather(const float* stereo0, const uint8_t* hd0, const float* s
                         const int* n0, const int* n1, int n_stride, int max_obs, int pairs, const PoseK& k, float* points, float* meas,
                         uint8_t* valid, hipStream_t s);
 
+// ---- ransac_kernels.hip : RANSAC pose seed and inlier gate (sship_ransac_*) ----
+constexpr int kRansacMaxSplits = 32;   // workgroups that share one pair's hypotheses at most
+constexpr int kRansacRecord = 14;      // doubles of a workgroup's partial result: cost, h, pose
+struct RansacK {                       // the camera and the rule's constants, by value
+  double fx, fy, cx, cy, baseline;
+  double thr2, min_disparity, min_area2;
+  uint32_t seed;
+  int num_hypotheses;
+};
+int ransac_splits(int num_hypotheses);
+size_t ransac_workspace_bytes(int max_pairs, int num_hypotheses);
+// the score launch (splits x pairs workgroups) and the launch of the argmin and the winner's mask.  inlier may be null; every output
+// entry is written.
+void launch_ransac_solve(const float* points, const float* meas, const uint8_t* valid, int max_obs, int pairs, const RansacK& k,
+                         void* workspace, double* pose, int32_t* stats, double* cost, uint8_t* inlier, hipStream_t s);
+
 // ---- ba_kernels.hip : sliding-window stereo bundle adjustment (sship_ba_*) ----
 constexpr int kBaMaxKf = 16;
 constexpr int kBaMaxObs = 2048;
