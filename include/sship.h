@@ -1035,6 +1035,68 @@ int sship_rgbd_associate_host(const float* keypoints, int kp_stride, int n, cons
                               const sship_rgbd_params* params, float* kp_undist, float* stereo, uint8_t* has_depth);
 
 /* ------------------------------------------------------------------------------------------------
+ * Stereo refinement - sub-pixel uR by a short 1-D patch search in the rectified image pair, after descriptor matching.  No reference
+ * counterpart: StereoFrontEnd::process copies uR from the right image's keypoint (src/StereoFrontEnd.cc:35-47), an integer NMS peak found
+ * independently of the left one.  The rule is this library's own (zero-mean SSD, parabola through the three costs around the minimum) and
+ * is stated here in full; tests/_stereo_refine_ref.py restates this text.  All of it is integer arithmetic on u8 pixels, one fp64 division,
+ * two fp64 additions and one rounding to fp32: the result does not depend on summation order, batch position or entry point.
+ *
+ * imgs_dev [2 * pairs, h, stride] u8, the L0, R0, L1, R1, ... layout sship_rect_remap_batch_device writes: IL = image 2p, IR = image
+ * 2p + 1 of pair p.  stride is in bytes, >= w; no alignment is required of the pointer or the stride.  stereo_in_dev [pairs, max_keypoints,
+ * 3] f32 = (uL, uR, vL) and has_depth_in_dev [pairs, max_keypoints] u8 as the association stages write them.  The left count n0 of pair
+ * p is n_dev[p * n_stride] clamped to [0, max_keypoints] on the device: n_stride = 2 for an extractor's [2 * pairs] count array, 1 for
+ * a [pairs] array.  w = half_window, L = search_radius, N = (2w+1)^2.  Keypoint i of pair p, in this order:
+ *   1. i >= n0: (0, quiet NaN, 0), has_depth 0, status NONE, cost -1 - the association's convention; every entry is written.
+ *   2. has_depth_in == 0: (uL, quiet NaN, vL), has_depth 0, status NONE, cost -1.
+ *   3. Any of uL, uR, vL not finite or outside [0, 16384): status BORDER.  Otherwise, in fp64 on the fp32 value, xl = floor(uL + 0.5),
+ *      xr = floor(uR + 0.5), y = floor(vL + 0.5) - both patches use the LEFT keypoint's row - and the status is BORDER unless
+ *      xl-w >= 0, xl+w < w_img, y-w >= 0, y+w < h, xr-L-w >= 0 and xr+L+w < w_img.  BORDER is not a rejection: the output is the input's
+ *      bits, has_depth 1, cost -1.
+ *   4. For k = -L .. L over (dy, dx) in [-w, w]^2:  d = IL[y+dy, xl+dx] - IR[y+dy, xr+k+dx];  S1 = sum d, S2 = sum d^2 (int32);
+ *      C_k = N S2 - S1^2 in int64 (N^2 times the zero-mean variance of the difference: invariant to a brightness offset; it reaches
+ *      3 291 825 600 at w = 7).
+ *   5. k* = the smallest k attaining the minimum, cost = C_k*.  |k*| == L: status EDGE.  Otherwise, with max_rms > 0 and
+ *      t = (double)max_rms (double)N:  (double)cost > t t: status COST.
+ *   6. Otherwise den = C_{k*-1} + C_{k*+1} - 2 C_k* (>= 1, because k* is the smallest minimiser),
+ *      delta = (double)(C_{k*-1} - C_{k*+1}) / (double)(2 den)  (|delta| <= 0.5).
+ *   7. uR' = (float)(((double)uL - (double)(xl - xr - k*)) + delta).  The left patch is centred on xl, not on uL, so a fractional uL keeps
+ *      its fraction.
+ *   8. In fp32, this positive form: uL - uR' >= min_disparity -> status REFINED, output (uL, uR', vL), has_depth 1; else status DISPARITY.
+ *   9. EDGE, COST and DISPARITY are rejections: on_reject KEEP writes the input's bits with has_depth 1, DROP writes (uL, quiet NaN, vL)
+ *      with has_depth 0.  cost is reported either way.
+ * status_dev [pairs, max_keypoints] u8 and cost_dev [pairs, max_keypoints] i64 are optional (NULL = not wanted).  stereo_out_dev ==
+ * stereo_in_dev and has_depth_out_dev == has_depth_in_dev are allowed: a row is read and written by its owner only.  One launch,
+ * asynchronous on `stream`, no host synchronisation.  pairs >= 1, max_keypoints in [1, 4096], h, w in [1, 16384], half_window in [1, 7],
+ * search_radius in [1, 15], max_rms (<= 0: no cost gate) and min_disparity not NaN; anything else, a NULL required pointer or stride < w
+ * is SSHIP_ERR_INVALID before any device is touched.
+ * ---------------------------------------------------------------------------------------------- */
+#define SSHIP_REFINE_KEEP 0
+#define SSHIP_REFINE_DROP 1
+#define SSHIP_REFINE_STATUS_NONE 0
+#define SSHIP_REFINE_STATUS_REFINED 1
+#define SSHIP_REFINE_STATUS_BORDER 2
+#define SSHIP_REFINE_STATUS_EDGE 3
+#define SSHIP_REFINE_STATUS_COST 4
+#define SSHIP_REFINE_STATUS_DISPARITY 5
+typedef struct sship_stereo_refine_params {
+  int half_window;      /* w: the patch is (2w+1) x (2w+1) pixels; default 5 */
+  int search_radius;    /* L: offsets -L .. +L are searched; default 5 */
+  float max_rms;        /* cost gate on the zero-mean RMS difference in grey levels; <= 0 is off (default 0) */
+  float min_disparity;  /* smallest accepted refined disparity; default 0 */
+  int on_reject;        /* SSHIP_REFINE_KEEP (default) or SSHIP_REFINE_DROP */
+} sship_stereo_refine_params;
+int sship_stereo_refine_batch_device(const uint8_t* imgs_dev, int pairs, int h, int w, int stride, const float* stereo_in_dev,
+                                     const uint8_t* has_depth_in_dev, const int* n_dev, int n_stride, int max_keypoints,
+                                     const sship_stereo_refine_params* params, float* stereo_out_dev, uint8_t* has_depth_out_dev,
+                                     uint8_t* status_dev, int64_t* cost_dev, void* stream);
+/* One pair from host arrays, the drop-in after one StereoFrontEnd::process: left / right [h, *_stride bytes] u8, stereo [n, 3], has_depth [n],
+ * n in [0, 4096] (0: nothing is touched); stereo_out [n, 3] and has_depth_out [n] may be the inputs; status [n] and cost [n] are optional.
+ * Synchronous. */
+int sship_stereo_refine_host(const uint8_t* left, int left_stride, const uint8_t* right, int right_stride, int h, int w, const float* stereo,
+                             const uint8_t* has_depth, int n, const sship_stereo_refine_params* params, float* stereo_out,
+                             uint8_t* has_depth_out, uint8_t* status, int64_t* cost);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused front-end step: what StereoFrontEnd::process asks of the two interfaces per frame
  * (src/StereoFrontEnd.cc:14,33): SuperPoint on L and R (one batch) + gather x2 + one LightGlue match,
  * for `pairs` stereo pairs at once, device-resident, no host synchronisation.  imgs_dev is

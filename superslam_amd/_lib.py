@@ -72,6 +72,11 @@ class RgbdParams(C.Structure):
                 ("bf", C.c_double), ("depth_factor", C.c_double), ("max_depth", C.c_double)]
 
 
+class StereoRefineParams(C.Structure):
+    _fields_ = [("half_window", C.c_int), ("search_radius", C.c_int), ("max_rms", C.c_float), ("min_disparity", C.c_float),
+                ("on_reject", C.c_int)]
+
+
 _lib = None
 vp, ip, fp, dp = C.c_void_p, C.c_int, C.c_float, C.c_double
 _SIGS = {
@@ -217,6 +222,8 @@ _SIGS = {
     "sship_rect_bench": (ip, [vp, ip, ip, ip, C.POINTER(fp)]),
     "sship_rgbd_associate_batch_device": (ip, [vp, vp, ip, ip, vp, ip, ip, ip, ip, C.POINTER(RgbdParams), vp, vp, vp, vp]),
     "sship_rgbd_associate_host": (ip, [vp, ip, ip, vp, ip, ip, ip, ip, C.POINTER(RgbdParams), vp, vp, vp]),
+    "sship_stereo_refine_batch_device": (ip, [vp, ip, ip, ip, ip, vp, vp, vp, ip, ip, C.POINTER(StereoRefineParams), vp, vp, vp, vp, vp]),
+    "sship_stereo_refine_host": (ip, [vp, ip, vp, ip, ip, ip, vp, vp, ip, C.POINTER(StereoRefineParams), vp, vp, vp, vp]),
     "sship_desc_to_host": (ip, [vp, ip, ip, vp]),
     "sship_frontend_batch_device": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_bench_layer": (ip, [vp, ip, ip, ip, ip, ip, C.POINTER(fp), C.POINTER(C.c_double)]),

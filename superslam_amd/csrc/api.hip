@@ -3782,6 +3782,78 @@ extern "C" int sship_rgbd_associate_host(const float* keypoints, int kp_stride, 
 }
 
 // ====================================================================================================
+// sub-pixel disparity refinement by patch correlation (the rule is in include/sship.h)
+// ====================================================================================================
+// the checks both entries share; fills the kernel's constants
+static int refine_check(int h, int w, const sship_stereo_refine_params* p, StereoRefineK* c, const char* who) {
+  if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, std::string(who) + ": h and w must be in [1, 16384]");
+  if (p->half_window < 1 || p->half_window > 7) return fail(SSHIP_ERR_INVALID, std::string(who) + ": half_window must be in [1, 7]");
+  if (p->search_radius < 1 || p->search_radius > 15) return fail(SSHIP_ERR_INVALID, std::string(who) + ": search_radius must be in [1, 15]");
+  if (std::isnan(p->max_rms) || std::isnan(p->min_disparity)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": max_rms and min_disparity must not be NaN");
+  if (p->on_reject != SSHIP_REFINE_KEEP && p->on_reject != SSHIP_REFINE_DROP)
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": on_reject must be 0 (keep) or 1 (drop)");
+  const int pw = 2 * p->half_window + 1;
+  const double t = (double)p->max_rms * (double)(pw * pw);
+  c->gate = p->max_rms > 0.f ? 1 : 0;
+  c->gate2 = t * t;
+  c->min_disparity = p->min_disparity;
+  c->half_window = p->half_window; c->search_radius = p->search_radius;
+  c->drop = p->on_reject == SSHIP_REFINE_DROP ? 1 : 0;
+  return SSHIP_OK;
+}
+extern "C" int sship_stereo_refine_batch_device(const uint8_t* imgs, int pairs, int h, int w, int stride, const float* stereo_in,
+                                                const uint8_t* has_depth_in, const int* n, int n_stride, int max_keypoints,
+                                                const sship_stereo_refine_params* p, float* stereo_out, uint8_t* has_depth_out,
+                                                uint8_t* status, int64_t* cost, void* stream) {
+  if (!imgs || !stereo_in || !has_depth_in || !n || !p || !stereo_out || !has_depth_out)
+    return fail(SSHIP_ERR_INVALID, "stereo_refine_batch_device: null argument");
+  if (pairs <= 0 || max_keypoints <= 0 || max_keypoints > kMaxKp)
+    return fail(SSHIP_ERR_INVALID, "stereo_refine_batch_device: pairs must be positive and max_keypoints in [1, 4096]");
+  if (n_stride != 1 && n_stride != 2) return fail(SSHIP_ERR_INVALID, "stereo_refine_batch_device: n_stride must be 1 or 2");
+  StereoRefineK c;
+  if (int rc = refine_check(h, w, p, &c, "stereo_refine_batch_device")) return rc;
+  if (stride < w) return fail(SSHIP_ERR_INVALID, "stereo_refine_batch_device: stride (bytes) must be >= w");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  launch_stereo_refine(imgs, pairs, h, w, stride, stereo_in, has_depth_in, n, n_stride, max_keypoints, c, stereo_out, has_depth_out, status,
+                       reinterpret_cast<long long*>(cost), s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("stereo_refine", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_stereo_refine_host(const uint8_t* left, int left_stride, const uint8_t* right, int right_stride, int h, int w,
+                                        const float* stereo, const uint8_t* has_depth, int n, const sship_stereo_refine_params* p,
+                                        float* stereo_out, uint8_t* has_depth_out, uint8_t* status, int64_t* cost) {
+  if (!left || !right || !p) return fail(SSHIP_ERR_INVALID, "stereo_refine_host: null argument");
+  if (n < 0 || n > kMaxKp) return fail(SSHIP_ERR_INVALID, "stereo_refine_host: n must be in [0, 4096]");
+  StereoRefineK c;
+  if (int rc = refine_check(h, w, p, &c, "stereo_refine_host")) return rc;
+  if (left_stride < w || right_stride < w) return fail(SSHIP_ERR_INVALID, "stereo_refine_host: stride (bytes) must be >= w");
+  if (n == 0) return SSHIP_OK;
+  if (!stereo || !has_depth || !stereo_out || !has_depth_out) return fail(SSHIP_ERR_INVALID, "stereo_refine_host: null argument");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  const size_t img = (size_t)h * w, kb = (size_t)n * 3 * sizeof(float);
+  DevBuf d_img, d_n, d_st, d_hd, d_status, d_cost;
+  SSHIP_HIP_CHECK(d_img.ensure(2 * img)); SSHIP_HIP_CHECK(d_n.ensure(16)); SSHIP_HIP_CHECK(d_st.ensure(kb)); SSHIP_HIP_CHECK(d_hd.ensure((size_t)n));
+  SSHIP_HIP_CHECK(d_status.ensure((size_t)n)); SSHIP_HIP_CHECK(d_cost.ensure((size_t)n * sizeof(int64_t)));
+  SSHIP_HIP_CHECK(hipMemcpy2D(d_img.p, (size_t)w, left, (size_t)left_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy2D(d_img.as<uint8_t>() + img, (size_t)w, right, (size_t)right_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(d_n.p, &n, sizeof(int), hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(d_st.p, stereo, kb, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(d_hd.p, has_depth, (size_t)n, hipMemcpyHostToDevice));
+  if (int rc = sship_stereo_refine_batch_device(d_img.as<uint8_t>(), 1, h, w, w, d_st.as<float>(), d_hd.as<uint8_t>(), d_n.as<int>(), 1, n, p,
+                                                d_st.as<float>(), d_hd.as<uint8_t>(), d_status.as<uint8_t>(), d_cost.as<int64_t>(), nullptr)) return rc;
+  SSHIP_HIP_CHECK(hipMemcpy(stereo_out, d_st.p, kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launch
+  SSHIP_HIP_CHECK(hipMemcpy(has_depth_out, d_hd.p, (size_t)n, hipMemcpyDeviceToHost));
+  if (status) { SSHIP_HIP_CHECK(hipMemcpy(status, d_status.p, (size_t)n, hipMemcpyDeviceToHost)); }
+  if (cost) { SSHIP_HIP_CHECK(hipMemcpy(cost, d_cost.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost)); }
+  return SSHIP_OK;
+}
+
+// ====================================================================================================
 // fused front-end step: SuperPoint(batch 2P) + select + gather + LightGlue(P)
 // ====================================================================================================
 extern "C" int sship_frontend_batch_device(sship_sp* sp, sship_lg* lg, const uint8_t* imgs, int pairs, int h, int w,

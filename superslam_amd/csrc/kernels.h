@@ -321,4 +321,11 @@ void launch_rect_remap(const uint8_t* src, int src_h, int src_stride, uint8_t* d
 void launch_rgbd_associate(const float* kp, const int* lens, int frames, int max_kp, const void* depth, int depth_f32, int h, int w,
                            long long depth_stride, const RgbdK& c, float* kp_undist, float* stereo, uint8_t* has_depth, hipStream_t s);
 
+// sub-pixel disparity refinement (stereo_refine_kernels.hip).  gate2 = (max_rms * N)^2, computed once on the host; gate = max_rms > 0.
+struct StereoRefineK { double gate2; float min_disparity; int half_window, search_radius, gate, drop; };
+// imgs [2 * pairs, h, stride bytes] u8; status / cost may be null; stereo_out / has_depth_out may alias their inputs
+void launch_stereo_refine(const uint8_t* imgs, int pairs, int h, int w, long long stride, const float* stereo_in, const uint8_t* has_depth_in,
+                          const int* lens, int n_stride, int max_kp, const StereoRefineK& c, float* stereo_out, uint8_t* has_depth_out,
+                          uint8_t* status, long long* cost, hipStream_t s);
+
 }  // namespace sship

@@ -134,6 +134,103 @@ def rgbd_associate_batch(kp, n, depth, camera, depth_factor: float, max_depth: f
     return (stereo, has_depth, kp_undist) if kp_undist is not None else (stereo, has_depth)
 
 
+REFINE_STATUS = ("none", "refined", "border", "edge", "cost", "disparity")   # the status codes of sship_stereo_refine_*, by value
+
+
+def stereo_refine_params(half_window: int = 5, search_radius: int = 5, max_rms: float = 0.0, min_disparity: float = 0.0, on_reject="keep"):
+    """The library's sship_stereo_refine_params, checked as the library checks it.  on_reject: "keep" / "drop" (or 0 / 1)."""
+    import math
+
+    if isinstance(half_window, bool) or isinstance(search_radius, bool) or int(half_window) != half_window or int(search_radius) != search_radius:
+        raise ValueError("half_window and search_radius must be integers")
+    if not 1 <= int(half_window) <= 7:
+        raise ValueError("half_window must be in [1, 7]")
+    if not 1 <= int(search_radius) <= 15:
+        raise ValueError("search_radius must be in [1, 15]")
+    if math.isnan(float(max_rms)) or math.isnan(float(min_disparity)):
+        raise ValueError("max_rms and min_disparity must not be NaN")
+    modes = {"keep": 0, "drop": 1, 0: 0, 1: 1}
+    if isinstance(on_reject, bool) or on_reject not in modes:
+        raise ValueError('on_reject must be "keep" or "drop"')
+    return _lib.StereoRefineParams(int(half_window), int(search_radius), float(max_rms), float(min_disparity), modes[on_reject])
+
+
+def stereo_refine_batch(images, stereo, has_depth, n, *, half_window: int = 5, search_radius: int = 5, max_rms: float = 0.0,
+                        min_disparity: float = 0.0, on_reject="keep", out=None, return_status: bool = False, stream=None):
+    """Sub-pixel uR by patch correlation in the rectified pair (sship_stereo_refine_batch_device; the rule is in include/sship.h):
+    images u8 [2P, h, w] ordered L0, R0, L1, R1, ... (rows may be strided, any alignment), stereo f32 [P, K, 3] and has_depth u8 [P, K] as
+    stereo_associate_batch writes them, n i32 [2P] (an extractor's counts: the left ones are read at stride 2) or [P]
+    -> (stereo, has_depth) of the same shapes, the inputs of PoseSolver.obs_from_matches and the smoother unchanged.
+    out: a (stereo, has_depth) pair to write into - the inputs themselves are allowed.  return_status: also status u8 [P, K] (indices into
+    REFINE_STATUS) and cost i64 [P, K] (C_k*, -1 where no search ran).  Asynchronous on `stream` (default: torch's current), one launch."""
+    import torch
+
+    prm = stereo_refine_params(half_window, search_radius, max_rms, min_disparity, on_reject)
+    if stereo.dim() != 3 or stereo.shape[2] != 3 or stereo.dtype != torch.float32 or not stereo.is_contiguous():
+        raise ValueError("stereo must be a contiguous float32 tensor [pairs, max_keypoints, 3]")
+    pairs, k = int(stereo.shape[0]), int(stereo.shape[1])
+    if pairs < 1 or not 1 <= k <= 4096:
+        raise ValueError("pairs must be >= 1 and max_keypoints in [1, 4096]")
+    if tuple(has_depth.shape) != (pairs, k) or has_depth.dtype != torch.uint8 or not has_depth.is_contiguous():
+        raise ValueError(f"has_depth must be a contiguous uint8 tensor [{pairs}, {k}]")
+    if n.dtype != torch.int32 or n.dim() != 1 or n.numel() not in (pairs, 2 * pairs) or not n.is_contiguous():
+        raise ValueError(f"n must be a contiguous int32 tensor with {pairs} or {2 * pairs} entries")
+    if images.dtype != torch.uint8 or images.dim() != 3 or images.shape[0] != 2 * pairs:
+        raise ValueError(f"images must be uint8 [{2 * pairs}, h, w]")
+    h, w = int(images.shape[1]), int(images.shape[2])
+    if not (1 <= h <= 16384 and 1 <= w <= 16384):
+        raise ValueError("h and w must be in [1, 16384]")
+    if (w > 1 and images.stride(2) != 1) or (h > 1 and images.stride(1) < w) or images.stride(0) != h * images.stride(1):
+        raise ValueError("images must have unit stride along x, a row stride >= w and be packed as [2 * pairs, h, row stride]")
+    if out is None:
+        out = (torch.empty_like(stereo), torch.empty_like(has_depth))
+    so, ho = out
+    for name, t, like in (("out[0]", so, stereo), ("out[1]", ho, has_depth)):
+        if tuple(t.shape) != tuple(like.shape) or t.dtype != like.dtype or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous tensor with the shape and dtype of its input")
+    if not all(t.is_cuda for t in (images, stereo, has_depth, n, so, ho)):
+        raise ValueError("images, stereo, has_depth, n and out must be device tensors")
+    status = torch.empty((pairs, k), dtype=torch.uint8, device=stereo.device) if return_status else None
+    cost = torch.empty((pairs, k), dtype=torch.int64, device=stereo.device) if return_status else None
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    _lib.check(_lib.lib().sship_stereo_refine_batch_device(images.data_ptr(), pairs, h, w, int(images.stride(1)) if h > 1 else w,
+                                                           stereo.data_ptr(), has_depth.data_ptr(), n.data_ptr(), n.numel() // pairs, k,
+                                                           _lib.C.byref(prm), so.data_ptr(), ho.data_ptr(),
+                                                           status.data_ptr() if return_status else None,
+                                                           cost.data_ptr() if return_status else None, s))
+    return (so, ho, status, cost) if return_status else (so, ho)
+
+
+def stereo_refine(left: np.ndarray, right: np.ndarray, stereo: np.ndarray, has_depth: np.ndarray, *, half_window: int = 5,
+                  search_radius: int = 5, max_rms: float = 0.0, min_disparity: float = 0.0, on_reject="keep", return_status: bool = False):
+    """One pair from host arrays (sship_stereo_refine_host), the step after one process_stereo: left / right u8 [h, w] (rows may be
+    strided), stereo f32 [n, 3] = (uL, uR or NaN, vL), has_depth u8 [n] -> (stereo, has_depth) as new arrays; return_status: also
+    status u8 [n] and cost i64 [n].  Synchronous."""
+    prm = stereo_refine_params(half_window, search_radius, max_rms, min_disparity, on_reject)
+    for name, im in (("left", left), ("right", right)):
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 2:
+            raise ValueError(f"{name} must be a uint8 array [h, w]")
+    if left.shape != right.shape:
+        raise ValueError("left and right must have the same shape")
+    h, w = left.shape
+    if not (1 <= h <= 16384 and 1 <= w <= 16384):
+        raise ValueError("h and w must be in [1, 16384]")
+    left, right = (im if (im.strides[1] == 1 or w == 1) and (im.strides[0] >= w or h == 1) else np.ascontiguousarray(im) for im in (left, right))
+    st = np.ascontiguousarray(stereo, np.float32)
+    hd = np.ascontiguousarray(has_depth, np.uint8).reshape(-1)
+    if st.ndim != 2 or st.shape[1] != 3 or len(hd) != len(st):
+        raise ValueError("stereo must be [n, 3] and has_depth [n]")
+    n = len(st)
+    if n > 4096:
+        raise ValueError("n must be at most 4096")
+    so, ho = np.empty_like(st), np.empty_like(hd)
+    status, cost = np.zeros(n, np.uint8), np.full(n, -1, np.int64)
+    row = lambda im: int(im.strides[0]) if h > 1 else w   # noqa: E731
+    _lib.check(_lib.lib().sship_stereo_refine_host(left.ctypes.data, row(left), right.ctypes.data, row(right), h, w, st.ctypes.data, hd.ctypes.data,
+                                                   n, _lib.C.byref(prm), so.ctypes.data, ho.ctypes.data, status.ctypes.data, cost.ctypes.data))
+    return (so, ho, status, cost) if return_status else (so, ho)
+
+
 class FrontEndBatch:
     """Device-resident throughput step: SuperPoint on 2P images + LightGlue on P pairs, no host sync."""
 
