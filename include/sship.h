@@ -490,6 +490,30 @@ int sship_ep_infer_u8(sship_ep* ep, const uint8_t* img, int h, int w, int stride
 int sship_ep_infer_u8_device(sship_ep* ep, const uint8_t* img_dev, int h, int w, int stride, int channels, float* desc_out_dev, void* stream);
 /* Measurement hook: `iters` back-to-back sship_ep_infer_u8_device calls on the handle's stream over a resident image; average ms. */
 int sship_ep_bench(sship_ep* ep, const uint8_t* img_dev, int h, int w, int stride, int channels, int iters, float* avg_ms);
+/* Test-only: per-stage capture of the network's activations.  The block activations live in four ping-pong buffers and are overwritten, so
+ * nothing can be read back after a call unless it was copied aside while the call ran.  Used by the parity suite to compare every layer with
+ * an fp64 convolution of the stage it read (tests/test_gpu_ep_layers.py); the product never calls it.
+ * sship_ep_debug_capture(ep, on): off is the default and costs nothing (no allocation, no launch, no kernel knows about it).  Switched on,
+ *   the per-stage buffers are allocated (once per handle) and every later call of the handle enqueues, on the call's own stream and right
+ *   after the launch that produces it, a device-to-device copy of every stage's output; the descriptor's bits are unchanged.  Switching
+ *   forgets what was captured.
+ * sship_ep_debug_activation(ep, stage, out_host, bytes): copies one stage of the LAST call to the host, raw, device-synchronising.
+ *   SSHIP_ERR_INVALID for a stage that does not exist, for bytes larger than the stage, and while capture is off or no call has run since it
+ *   was switched on.
+ * Stages (H x W the engine size; h1 = ceil(H / 4) by the chain h -> (h - 1) / 2 + 1 twice, h2 = ceil(h1 / 2), h3 = ceil(h2 / 2),
+ * h4 = ceil(h3 / 2), likewise w; fp16 maps are channels-last [h][w][c]):
+ *    0        the preprocessed input, fp32 [3][H][W]
+ *    1        stem 7x7 / 2 + BatchNorm + ReLU + MaxPool2d(3, 2, 1), fp16 [h1][w1][64]
+ *    2 + 3 b  block b's conv1 + bn1 + ReLU               (b = 0 .. 7: layer1.0, layer1.1, layer2.0, ... layer4.1)
+ *    3 + 3 b  block b's downsample conv 1x1 + BatchNorm   (exists for b = 2, 4, 6 only: the first block of layer2 / 3 / 4)
+ *    4 + 3 b  block b's output, ReLU(conv2 + bn2 + identity or downsample)
+ *             all fp16, [h1][w1][64] for b = 0, 1; [h2][w2][128] for b = 2, 3; [h3][w3][256] for b = 4, 5; [h4][w4][512] for b = 6, 7
+ *   26        the tail's partial sums of clamp(x / ||x||, 1e-6)^p over the locations, fp32 [G][512], G = min(32, ceil(h4 w4 / 8))
+ *             workgroups (the GeM mean is their sum in ascending order, divided by h4 w4)
+ *   27        the 512 outputs of the Linear, before the final L2 normalisation, fp32
+ *   28        the descriptor, fp32 [512] */
+int sship_ep_debug_capture(sship_ep* ep, int on);
+int sship_ep_debug_activation(sship_ep* ep, int stage, void* out_host, unsigned long long bytes);
 /* EigenPlaces::preprocess (src/EigenPlaces.cc:123-145) on the host, no GPU: u8 image (1 channel or 3 = BGR, row stride in bytes) ->
  * fp32 [3, input_h, input_w]: GRAY2RGB / BGR2RGB, cv::resize INTER_LINEAR (OpenCV's 8-bit fixed-point path), x 1/255,
  * ImageNet mean / std.  Exported so that every binding shares one implementation. */

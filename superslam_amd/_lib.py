@@ -157,6 +157,8 @@ _SIGS = {
     "sship_ep_infer_u8": (ip, [vp, vp, ip, ip, ip, ip, vp]),
     "sship_ep_infer_u8_device": (ip, [vp, vp, ip, ip, ip, ip, vp, vp]),
     "sship_ep_bench": (ip, [vp, vp, ip, ip, ip, ip, ip, C.POINTER(C.c_float)]),
+    "sship_ep_debug_capture": (ip, [vp, ip]),
+    "sship_ep_debug_activation": (ip, [vp, ip, vp, C.c_ulonglong]),
     "sship_index_create": (ip, [ip, ip, ip, ip, C.POINTER(vp)]),
     "sship_index_destroy": (None, [vp]),
     "sship_index_dim": (ip, [vp]),

@@ -2460,6 +2460,11 @@ struct sship_ep {
   // the asynchronous entry point needs no device-wide synchronisation (round 5 re-used one buffer behind a hipDeviceSynchronize).
   struct Tables { int h = 0, w = 0; DevBuf d; };
   std::vector<std::unique_ptr<Tables>> tables;
+  // test-only capture (include/sship.h: sship_ep_debug_capture): one buffer per stage, allocated when capture is first switched on
+  static constexpr int kStages = 29;
+  bool capture = false, captured = false, cap_ready = false;   // captured: a call has run since capture was switched on
+  size_t cap_bytes[kStages] = {};           // 0: the stage does not exist (a block without a downsample)
+  DevBuf cap[kStages];
 };
 extern "C" void sship_ep_destroy(sship_ep* ep) {
   bind_thread();
@@ -2567,10 +2572,32 @@ extern "C" int sship_ep_preprocess(const uint8_t* img, int h, int w, int stride,
   superslam_hip::eigenplaces_preprocess(superslam_hip::Image{img, h, w, channels, stride}, input_w, input_h, chw_out);
   return SSHIP_OK;
 }
+// sizes of the capture stages of an engine (the numbering of include/sship.h), from the same ceil chain as ep_network
+static void ep_stage_bytes(const sship_ep* ep, size_t (&bytes)[sship_ep::kStages]) {
+  int h = (ep->in_h - 1) / 2 + 1, w = (ep->in_w - 1) / 2 + 1;
+  h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1;
+  bytes[0] = (size_t)3 * ep->in_h * ep->in_w * 4;
+  bytes[1] = (size_t)h * w * 64 * 2;
+  for (int i = 0; i < 8; ++i) {
+    const auto& blk = ep->blocks[i];
+    if (blk.stride == 2) { h = (h + 1) / 2; w = (w + 1) / 2; }
+    const size_t n = (size_t)h * w * blk.c2.cout * 2;
+    bytes[2 + 3 * i] = n; bytes[3 + 3 * i] = blk.has_ds ? n : 0; bytes[4 + 3 * i] = n;
+  }
+  bytes[26] = (size_t)ep_tail_pool_wgs(h * w) * 512 * 4;
+  bytes[27] = 512 * 4;
+  bytes[28] = 512 * 4;
+}
 // the network from the preprocessed fp32 [3, H, W] tensor in d_in to the descriptor in `desc_dev`, on stream s
 static int ep_network(sship_ep* ep, float* desc_dev, hipStream_t s) {
   const int H = ep->in_h, W = ep->in_w;
   int h = (H - 1) / 2 + 1, w = (W - 1) / 2 + 1;
+  // test-only capture: a stream-ordered device-to-device copy of a stage's output; off (the default) makes no call at all
+  auto cap = [&](int stage, const void* src) -> hipError_t {
+    if (!ep->capture) return hipSuccess;
+    return hipMemcpyAsync(ep->cap[stage].p, src, ep->cap_bytes[stage], hipMemcpyDeviceToDevice, s);
+  };
+  SSHIP_HIP_CHECK(cap(0, ep->d_in.p));
   _Float16* a[4] = {ep->act[0].as<_Float16>(), ep->act[1].as<_Float16>(), ep->act[2].as<_Float16>(), ep->act[3].as<_Float16>()};
   const int hp = (h - 1) / 2 + 1, wp = (w - 1) / 2 + 1;  // MaxPool2d(3, 2, 1)
 #if SSHIP_DEV_SWITCHES  // A/B: the stem of rounds 3-5 (im2col -> 1x1 GEMM -> max-pool, three launches)
@@ -2583,7 +2610,9 @@ static int ep_network(sship_ep* ep, float* desc_dev, hipStream_t s) {
 #endif
   launch_ep_stem_pool(ep->d_in.as<float>(), H, W, h, w, hp, wp, ep->stem_frag.as<_Float16>(), ep->stem_bias.as<float>(), a[1], s);
   h = hp; w = wp;
+  SSHIP_HIP_CHECK(cap(1, a[1]));
   int cur = 1;  // index of the buffer holding the block input
+  int stage = 2;  // capture stage of this block's conv1 (then its downsample, then its output)
   for (const auto& blk : ep->blocks) {
     int f[3], k = 0;
     for (int i = 0; i < 4; ++i) if (i != cur) f[k++] = i;  // three free buffers: t, ds, out
@@ -2593,15 +2622,46 @@ static int ep_network(sship_ep* ep, float* desc_dev, hipStream_t s) {
     float* ws = ep->d_ws.as<float>();
     const size_t wsb = ep->d_ws.bytes;
     SSHIP_HIP_CHECK(ep_conv(blk.c1, a[cur], a[f[0]], nullptr, h, w, true, blk.stride == 2, s, ws, wsb));
+    SSHIP_HIP_CHECK(cap(stage, a[f[0]]));
     if (blk.has_ds) {
       SSHIP_HIP_CHECK(ep_conv(blk.ds, a[cur], a[f[1]], nullptr, h, w, false, blk.stride == 2, s));
+      SSHIP_HIP_CHECK(cap(stage + 1, a[f[1]]));
       res = a[f[1]];
     }
     SSHIP_HIP_CHECK(ep_conv(blk.c2, a[f[0]], a[f[2]], res, ho, wo, true, false, s, ws, wsb));
-    cur = f[2]; h = ho; w = wo;
+    SSHIP_HIP_CHECK(cap(stage + 2, a[f[2]]));
+    cur = f[2]; h = ho; w = wo; stage += 3;
   }
   launch_ep_tail(a[cur], h * w, ep->gem_p, ep->fc_wt, ep->fc_b, ep->d_tail.as<float>(), ep->d_tail.as<int>() + ep_tail_ws_floats(), desc_dev, s);
   SSHIP_HIP_CHECK(hipGetLastError());
+  SSHIP_HIP_CHECK(cap(26, ep->d_tail.p));
+  SSHIP_HIP_CHECK(cap(27, ep->d_tail.as<float>() + ep_tail_ws_floats() - 512));
+  SSHIP_HIP_CHECK(cap(28, desc_dev));
+  if (ep->capture) ep->captured = true;
+  return SSHIP_OK;
+}
+// Test-only (include/sship.h): per-stage capture of the network's activations
+extern "C" int sship_ep_debug_capture(sship_ep* ep, int on) {
+  bind_thread();
+  if (!ep) return fail(SSHIP_ERR_INVALID, "ep_debug_capture: null handle");
+  if (on && !ep->cap_ready) {
+    ep_stage_bytes(ep, ep->cap_bytes);
+    for (int i = 0; i < sship_ep::kStages; ++i)
+      if (ep->cap_bytes[i]) SSHIP_HIP_CHECK(ep->cap[i].ensure(ep->cap_bytes[i]));
+    ep->cap_ready = true;
+  }
+  ep->capture = on != 0;
+  ep->captured = false;
+  return SSHIP_OK;
+}
+extern "C" int sship_ep_debug_activation(sship_ep* ep, int stage, void* out_host, unsigned long long bytes) {
+  bind_thread();
+  if (!ep || !out_host) return fail(SSHIP_ERR_INVALID, "ep_debug_activation: null argument");
+  if (!ep->capture || !ep->captured) return fail(SSHIP_ERR_INVALID, "ep_debug_activation: capture is off or no call has run since it was switched on");
+  if (stage < 0 || stage >= sship_ep::kStages || !ep->cap_bytes[stage] || bytes > ep->cap_bytes[stage])
+    return fail(SSHIP_ERR_INVALID, "ep_debug_activation: bad stage / size");
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());
+  SSHIP_HIP_CHECK(hipMemcpy(out_host, ep->cap[stage].p, bytes, hipMemcpyDeviceToHost));
   return SSHIP_OK;
 }
 extern "C" int sship_ep_infer(sship_ep* ep, const float* chw_host, float* desc_out) {

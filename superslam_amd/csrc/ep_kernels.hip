@@ -171,11 +171,15 @@ hipError_t ep_conv(const ConvW& w, const _Float16* in, _Float16* out, const _Flo
 // row, the two source indices and the two 11-bit coefficients (computed on the host, by the same code as the host path - they depend only
 // on the two sizes); a thread does one output pixel: horizontal pass in int, vertical pass
 //   (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2, saturate to u8,
-// then the three float operations of the host path in the same order (one multiply, one subtract, one correctly rounded divide: no
-// contraction possible).  Output fp32 CHW, bit-identical to sship_ep_preprocess.
+// then the three float operations of the host path in the same order (one multiply, one subtract, one correctly rounded divide).  The
+// multiply and the subtract must NOT be contracted into an FMA, which the device compiler does by default: contraction is switched off for
+// this kernel (the fused form differs from the host's in the last bits of 3 elements in 4, by tens of ulps where v / 255 is close to the
+// mean; the stem's fp16 rounding hid that from every descriptor test - tests/test_gpu_ep_layers.py compares the tensor itself).
+// Output fp32 CHW, bit-identical to sship_ep_preprocess.
 // tab: [4][out_w] ints (sx, sx1, ax0, ax1) then [4][out_h] (sy, sy1, by0, by1)
 __global__ __launch_bounds__(256) void k_ep_resize_norm(const uint8_t* __restrict__ src, int stride, int ch, const int* __restrict__ tab,
                                                         int out_w, int out_h, float* __restrict__ out) {
+#pragma clang fp contract(off)
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= out_w * out_h) return;
   const int y = idx / out_w, x = idx - y * out_w;
@@ -375,7 +379,7 @@ void launch_ep_stem_pool(const float* x, int H, int W, int Ho, int Wo, int Hp, i
 //     to ARRIVE (an atomic ticket - nobody waits) normalises.
 constexpr int kTailWg = 8;
 constexpr int kTailPoolWg = 32;
-static int ep_tail_pool_wgs(int npix) { const int g = (npix + 7) / 8; return g < kTailPoolWg ? g : kTailPoolWg; }  // a function of the map size only
+int ep_tail_pool_wgs(int npix) { const int g = (npix + 7) / 8; return g < kTailPoolWg ? g : kTailPoolWg; }  // a function of the map size only
 __global__ __launch_bounds__(512) void k_ep_tail_pool(const _Float16* __restrict__ feat, int npix, float p, float* __restrict__ g_part,
                                                       int* __restrict__ counters) {
   __shared__ float s_part[8 * 512];
