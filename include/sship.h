@@ -1121,6 +1121,74 @@ int sship_stereo_refine_host(const uint8_t* left, int left_stride, const uint8_t
                              uint8_t* has_depth_out, uint8_t* status, int64_t* cost);
 
 /* ------------------------------------------------------------------------------------------------
+ * Stereo search - uR for a left keypoint by a 1-D patch search along its row of the rectified right image, over the whole disparity
+ * range: no right-image extraction and no stereo matcher call are needed.  No reference counterpart: StereoFrontEnd::process extracts
+ * both images and matches them (src/StereoFrontEnd.cc:14-47).  The rule is this library's own (the zero-mean SSD and the parabola of the
+ * stereo refinement, with a texture gate, a uniqueness gate and a left-right check in front of the fit) and is stated here in full;
+ * tests/_stereo_search_ref.py restates this text.  All of it is integer arithmetic on u8 pixels up to two fp64 compares, one fp64 division,
+ * two fp64 subtractions and one rounding to fp32: the result does not depend on summation order, batch position or entry point.
+ *
+ * imgs_dev [2 * pairs, h, stride] u8, the L0, R0, L1, R1, ... layout: IL = image 2p, IR = image 2p + 1 of pair p.  stride is in bytes,
+ * >= w; no alignment is required of the pointer or the stride.  kp_dev [units, max_keypoints, 3] f32 = (x, y, score) as an extractor
+ * writes it and n_dev [units] i32; pair p reads unit p * unit_stride: unit_stride = 2 for the [2 * pairs] arrays of an extractor that ran
+ * on both images, 1 for a left-only extraction.  The count n0 of pair p is n_dev[p * unit_stride] clamped to [0, max_keypoints] on the
+ * device.  w = half_window, pw = 2w+1, N = pw^2, dlo = min_disparity, dhi = max_disparity (integers, pixels), W = the image width,
+ * u = uniqueness, mt = min_texture, lr = lr_check.  Keypoint i of pair p, in this order:
+ *   1. i >= n0: (0, quiet NaN, 0), has_depth 0, status NONE, cost -1 - the association's convention; every entry is written.
+ *   2. x or y not finite or outside [0, 16384): status BORDER.  Otherwise, in fp64 on the fp32 value, xl = floor(x + 0.5),
+ *      yl = floor(y + 0.5), and the status is BORDER unless xl-w >= 0, xl+w < W, yl-w >= 0 and yl+w < h.
+ *   3. dmax = min(dhi, xl - w): the right patch at xl - d stays inside the image.  dmax - dlo + 1 < 3: status RANGE.
+ *   4. Texture gate on the left patch A (the pixels IL[yl+dy, xl+dx], (dy, dx) in [-w, w]^2): T = N sum A^2 - (sum A)^2 in int64.  With
+ *      mt > 0 and t = (double)mt (double)N:  (double)T < t t: status TEXTURE.
+ *   5. For d = dlo .. dmax over (dy, dx) in [-w, w]^2:  e = IL[yl+dy, xl+dx] - IR[yl+dy, xl-d+dx];  S1 = sum e, S2 = sum e^2;
+ *      C_d = N S2 - S1^2 in int64 - the refinement's cost; both patches lie on the left keypoint's row.
+ *   6. d* = the smallest d attaining the minimum, cost = C_d*.  d* == dlo or d* == dmax: status EDGE.
+ *   7. With max_rms > 0 and t = (double)max_rms (double)N:  (double)cost > t t: status COST.
+ *   8. Uniqueness, with u > 0: C2 = min C_d over |d - d*| > 1.  If such a d exists and 100 cost < (100 - u) C2 does NOT hold (int64):
+ *      status AMBIGUOUS.
+ *   9. Left-right check, with lr >= 0: xr = xl - d*, emax = min(dhi, W - 1 - w - xr) (always >= d*).  For e = dlo .. emax, B_e is the
+ *      same cost between the right patch at xr and the left patch at xr + e;  e* = the smallest e attaining the minimum.
+ *      |e* - d*| > lr: status LRCHECK.
+ *  10. den = C_{d*-1} + C_{d*+1} - 2 cost (>= 1, because d* is the smallest minimiser),
+ *      delta = (double)(C_{d*-1} - C_{d*+1}) / (double)(2 den)  (|delta| <= 0.5),
+ *      uR' = (float)(((double)x - (double)d*) - delta).  The patch is centred on xl, not on x, so a fractional x keeps its fraction.
+ *      Status FOUND, output (x, uR', y) with the input's bits for x and y, has_depth 1.
+ *  11. Every status other than FOUND writes (x, quiet NaN, y) with the input's bits, has_depth 0.  cost is -1 for NONE, BORDER, RANGE
+ *      and TEXTURE and C_d* otherwise.
+ * status_dev [pairs, max_keypoints] u8 and cost_dev [pairs, max_keypoints] i64 are optional (NULL = not wanted).  One launch,
+ * asynchronous on `stream`, no host synchronisation.  pairs >= 1, max_keypoints in [1, 4096], h, w in [1, 16384], half_window in [1, 7],
+ * 0 <= min_disparity <= max_disparity, max_disparity - min_disparity + 1 in [3, 512], uniqueness in [0, 99], lr_check in [-1, 16]
+ * (-1: no check), min_texture and max_rms not NaN (<= 0: off), unit_stride 1 or 2; anything else, a NULL required pointer or
+ * stride < w is SSHIP_ERR_INVALID before any device is touched.
+ * ---------------------------------------------------------------------------------------------- */
+#define SSHIP_SEARCH_STATUS_NONE 0
+#define SSHIP_SEARCH_STATUS_FOUND 1
+#define SSHIP_SEARCH_STATUS_BORDER 2
+#define SSHIP_SEARCH_STATUS_RANGE 3
+#define SSHIP_SEARCH_STATUS_TEXTURE 4
+#define SSHIP_SEARCH_STATUS_EDGE 5
+#define SSHIP_SEARCH_STATUS_COST 6
+#define SSHIP_SEARCH_STATUS_AMBIGUOUS 7
+#define SSHIP_SEARCH_STATUS_LRCHECK 8
+typedef struct sship_stereo_search_params {
+  int half_window;    /* w: the patch is (2w+1) x (2w+1) pixels; default 5 */
+  int min_disparity;  /* dlo, pixels; default 0 */
+  int max_disparity;  /* dhi, pixels; default 128 */
+  int uniqueness;     /* u, percent: the best cost must be below (100 - u) % of the best one further than 1 px away; 0 is off; default 10 */
+  float min_texture;  /* texture gate on the standard deviation of the left patch in grey levels; <= 0 is off (default 0) */
+  float max_rms;      /* cost gate on the zero-mean RMS difference in grey levels; <= 0 is off (default 0) */
+  int lr_check;       /* largest accepted |e* - d*| of the left-right check; -1 is off; default 1 */
+} sship_stereo_search_params;
+int sship_stereo_search_batch_device(const uint8_t* imgs_dev, int pairs, int h, int w, int stride, const float* kp_dev, const int* n_dev,
+                                     int unit_stride, int max_keypoints, const sship_stereo_search_params* params, float* stereo_out_dev,
+                                     uint8_t* has_depth_out_dev, uint8_t* status_dev, int64_t* cost_dev, void* stream);
+/* One pair from host arrays: left / right [h, *_stride bytes] u8, keypoints[i * kp_stride + {0, 1}] = (x, y) with kp_stride >= 2, n in
+ * [0, 4096] (0: nothing is touched); stereo_out [n, 3], has_depth_out [n]; status [n] and cost [n] are optional.  Synchronous. */
+int sship_stereo_search_host(const uint8_t* left, int left_stride, const uint8_t* right, int right_stride, int h, int w,
+                             const float* keypoints, int kp_stride, int n, const sship_stereo_search_params* params, float* stereo_out,
+                             uint8_t* has_depth_out, uint8_t* status, int64_t* cost);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused front-end step: what StereoFrontEnd::process asks of the two interfaces per frame
  * (src/StereoFrontEnd.cc:14,33): SuperPoint on L and R (one batch) + gather x2 + one LightGlue match,
  * for `pairs` stereo pairs at once, device-resident, no host synchronisation.  imgs_dev is

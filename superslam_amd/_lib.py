@@ -77,6 +77,11 @@ class StereoRefineParams(C.Structure):
                 ("on_reject", C.c_int)]
 
 
+class StereoSearchParams(C.Structure):
+    _fields_ = [("half_window", C.c_int), ("min_disparity", C.c_int), ("max_disparity", C.c_int), ("uniqueness", C.c_int),
+                ("min_texture", C.c_float), ("max_rms", C.c_float), ("lr_check", C.c_int)]
+
+
 _lib = None
 vp, ip, fp, dp = C.c_void_p, C.c_int, C.c_float, C.c_double
 _SIGS = {
@@ -226,6 +231,8 @@ _SIGS = {
     "sship_rgbd_associate_host": (ip, [vp, ip, ip, vp, ip, ip, ip, ip, C.POINTER(RgbdParams), vp, vp, vp]),
     "sship_stereo_refine_batch_device": (ip, [vp, ip, ip, ip, ip, vp, vp, vp, ip, ip, C.POINTER(StereoRefineParams), vp, vp, vp, vp, vp]),
     "sship_stereo_refine_host": (ip, [vp, ip, vp, ip, ip, ip, vp, vp, ip, C.POINTER(StereoRefineParams), vp, vp, vp, vp]),
+    "sship_stereo_search_batch_device": (ip, [vp, ip, ip, ip, ip, vp, vp, ip, ip, C.POINTER(StereoSearchParams), vp, vp, vp, vp, vp]),
+    "sship_stereo_search_host": (ip, [vp, ip, vp, ip, ip, ip, vp, ip, ip, C.POINTER(StereoSearchParams), vp, vp, vp, vp]),
     "sship_desc_to_host": (ip, [vp, ip, ip, vp]),
     "sship_frontend_batch_device": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_bench_layer": (ip, [vp, ip, ip, ip, ip, ip, C.POINTER(fp), C.POINTER(C.c_double)]),

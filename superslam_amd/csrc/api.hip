@@ -3914,6 +3914,81 @@ extern "C" int sship_stereo_refine_host(const uint8_t* left, int left_stride, co
 }
 
 // ====================================================================================================
+// keypoint stereo depth by epipolar search (the rule is in include/sship.h)
+// ====================================================================================================
+// the checks both entries share; fills the kernel's constants
+static int search_check(int h, int w, const sship_stereo_search_params* p, StereoSearchK* c, const char* who) {
+  if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, std::string(who) + ": h and w must be in [1, 16384]");
+  if (p->half_window < 1 || p->half_window > 7) return fail(SSHIP_ERR_INVALID, std::string(who) + ": half_window must be in [1, 7]");
+  if (p->min_disparity < 0 || p->max_disparity < p->min_disparity)
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": 0 <= min_disparity <= max_disparity is required");
+  const long long cand = (long long)p->max_disparity - p->min_disparity + 1;
+  if (cand < 3 || cand > 512) return fail(SSHIP_ERR_INVALID, std::string(who) + ": max_disparity - min_disparity + 1 must be in [3, 512]");
+  if (p->uniqueness < 0 || p->uniqueness > 99) return fail(SSHIP_ERR_INVALID, std::string(who) + ": uniqueness must be in [0, 99]");
+  if (p->lr_check < -1 || p->lr_check > 16) return fail(SSHIP_ERR_INVALID, std::string(who) + ": lr_check must be in [-1, 16]");
+  if (std::isnan(p->min_texture) || std::isnan(p->max_rms)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": min_texture and max_rms must not be NaN");
+  const int pw = 2 * p->half_window + 1;
+  const double tt = (double)p->min_texture * (double)(pw * pw), tr = (double)p->max_rms * (double)(pw * pw);
+  c->tex = p->min_texture > 0.f ? 1 : 0;
+  c->tex2 = tt * tt;
+  c->gate = p->max_rms > 0.f ? 1 : 0;
+  c->gate2 = tr * tr;
+  c->half_window = p->half_window; c->dlo = p->min_disparity; c->dhi = p->max_disparity;
+  c->uniqueness = p->uniqueness; c->lr = p->lr_check;
+  return SSHIP_OK;
+}
+extern "C" int sship_stereo_search_batch_device(const uint8_t* imgs, int pairs, int h, int w, int stride, const float* kp, const int* n,
+                                                int unit_stride, int max_keypoints, const sship_stereo_search_params* p, float* stereo_out,
+                                                uint8_t* has_depth_out, uint8_t* status, int64_t* cost, void* stream) {
+  if (!imgs || !kp || !n || !p || !stereo_out || !has_depth_out) return fail(SSHIP_ERR_INVALID, "stereo_search_batch_device: null argument");
+  if (pairs <= 0 || max_keypoints <= 0 || max_keypoints > kMaxKp)
+    return fail(SSHIP_ERR_INVALID, "stereo_search_batch_device: pairs must be positive and max_keypoints in [1, 4096]");
+  if (unit_stride != 1 && unit_stride != 2) return fail(SSHIP_ERR_INVALID, "stereo_search_batch_device: unit_stride must be 1 or 2");
+  StereoSearchK c;
+  if (int rc = search_check(h, w, p, &c, "stereo_search_batch_device")) return rc;
+  if (stride < w) return fail(SSHIP_ERR_INVALID, "stereo_search_batch_device: stride (bytes) must be >= w");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  launch_stereo_search(imgs, pairs, h, w, stride, kp, n, unit_stride, max_keypoints, c, stereo_out, has_depth_out, status,
+                       reinterpret_cast<long long*>(cost), s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("stereo_search", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_stereo_search_host(const uint8_t* left, int left_stride, const uint8_t* right, int right_stride, int h, int w,
+                                        const float* keypoints, int kp_stride, int n, const sship_stereo_search_params* p, float* stereo_out,
+                                        uint8_t* has_depth_out, uint8_t* status, int64_t* cost) {
+  if (!left || !right || !p) return fail(SSHIP_ERR_INVALID, "stereo_search_host: null argument");
+  if (n < 0 || n > kMaxKp || kp_stride < 2) return fail(SSHIP_ERR_INVALID, "stereo_search_host: n must be in [0, 4096] and kp_stride >= 2");
+  StereoSearchK c;
+  if (int rc = search_check(h, w, p, &c, "stereo_search_host")) return rc;
+  if (left_stride < w || right_stride < w) return fail(SSHIP_ERR_INVALID, "stereo_search_host: stride (bytes) must be >= w");
+  if (n == 0) return SSHIP_OK;
+  if (!keypoints || !stereo_out || !has_depth_out) return fail(SSHIP_ERR_INVALID, "stereo_search_host: null argument");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  std::vector<float> kp((size_t)n * 3, 0.f);
+  for (int i = 0; i < n; ++i) { kp[3 * i] = keypoints[(size_t)i * kp_stride]; kp[3 * i + 1] = keypoints[(size_t)i * kp_stride + 1]; }
+  const size_t img = (size_t)h * w, kb = (size_t)n * 3 * sizeof(float);
+  DevBuf d_img, d_n, d_kp, d_st, d_hd, d_status, d_cost;
+  SSHIP_HIP_CHECK(d_img.ensure(2 * img)); SSHIP_HIP_CHECK(d_n.ensure(16)); SSHIP_HIP_CHECK(d_kp.ensure(kb)); SSHIP_HIP_CHECK(d_st.ensure(kb));
+  SSHIP_HIP_CHECK(d_hd.ensure((size_t)n)); SSHIP_HIP_CHECK(d_status.ensure((size_t)n)); SSHIP_HIP_CHECK(d_cost.ensure((size_t)n * sizeof(int64_t)));
+  SSHIP_HIP_CHECK(hipMemcpy2D(d_img.p, (size_t)w, left, (size_t)left_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy2D(d_img.as<uint8_t>() + img, (size_t)w, right, (size_t)right_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(d_n.p, &n, sizeof(int), hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(d_kp.p, kp.data(), kb, hipMemcpyHostToDevice));
+  if (int rc = sship_stereo_search_batch_device(d_img.as<uint8_t>(), 1, h, w, w, d_kp.as<float>(), d_n.as<int>(), 1, n, p, d_st.as<float>(),
+                                                d_hd.as<uint8_t>(), d_status.as<uint8_t>(), d_cost.as<int64_t>(), nullptr)) return rc;
+  SSHIP_HIP_CHECK(hipMemcpy(stereo_out, d_st.p, kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launch
+  SSHIP_HIP_CHECK(hipMemcpy(has_depth_out, d_hd.p, (size_t)n, hipMemcpyDeviceToHost));
+  if (status) { SSHIP_HIP_CHECK(hipMemcpy(status, d_status.p, (size_t)n, hipMemcpyDeviceToHost)); }
+  if (cost) { SSHIP_HIP_CHECK(hipMemcpy(cost, d_cost.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost)); }
+  return SSHIP_OK;
+}
+
+// ====================================================================================================
 // fused front-end step: SuperPoint(batch 2P) + select + gather + LightGlue(P)
 // ====================================================================================================
 extern "C" int sship_frontend_batch_device(sship_sp* sp, sship_lg* lg, const uint8_t* imgs, int pairs, int h, int w,

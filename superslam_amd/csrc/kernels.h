@@ -329,4 +329,12 @@ void launch_stereo_refine(const uint8_t* imgs, int pairs, int h, int w, long lon
                           const int* lens, int n_stride, int max_kp, const StereoRefineK& c, float* stereo_out, uint8_t* has_depth_out,
                           uint8_t* status, long long* cost, hipStream_t s);
 
+// keypoint stereo depth by epipolar search (stereo_search_kernels.hip).  tex2 = (min_texture * N)^2 and gate2 = (max_rms * N)^2, computed once
+// on the host; tex / gate = the gate is on.
+struct StereoSearchK { double tex2, gate2; int half_window, dlo, dhi, uniqueness, lr, tex, gate; };
+// imgs [2 * pairs, h, stride bytes] u8; pair p reads kp / lens of unit p * unit_stride; status / cost may be null
+void launch_stereo_search(const uint8_t* imgs, int pairs, int h, int w, long long stride, const float* kp, const int* lens, int unit_stride,
+                          int max_kp, const StereoSearchK& c, float* stereo_out, uint8_t* has_depth_out, uint8_t* status, long long* cost,
+                          hipStream_t s);
+
 }  // namespace sship

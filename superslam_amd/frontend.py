@@ -231,6 +231,111 @@ def stereo_refine(left: np.ndarray, right: np.ndarray, stereo: np.ndarray, has_d
     return (so, ho, status, cost) if return_status else (so, ho)
 
 
+# the status codes of sship_stereo_search_*, by value
+SEARCH_STATUS = ("none", "found", "border", "range", "texture", "edge", "cost", "ambiguous", "lrcheck")
+
+
+def stereo_search_params(half_window: int = 5, min_disparity: int = 0, max_disparity: int = 128, uniqueness: int = 10,
+                         min_texture: float = 0.0, max_rms: float = 0.0, lr_check: int = 1):
+    """The library's sship_stereo_search_params, checked as the library checks it."""
+    import math
+
+    ints = dict(half_window=half_window, min_disparity=min_disparity, max_disparity=max_disparity, uniqueness=uniqueness, lr_check=lr_check)
+    for name, v in ints.items():
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} must be an integer")
+    if not 1 <= int(half_window) <= 7:
+        raise ValueError("half_window must be in [1, 7]")
+    if not 0 <= int(min_disparity) <= int(max_disparity):
+        raise ValueError("0 <= min_disparity <= max_disparity is required")
+    if not 3 <= int(max_disparity) - int(min_disparity) + 1 <= 512:
+        raise ValueError("max_disparity - min_disparity + 1 must be in [3, 512]")
+    if not 0 <= int(uniqueness) <= 99:
+        raise ValueError("uniqueness must be in [0, 99]")
+    if not -1 <= int(lr_check) <= 16:
+        raise ValueError("lr_check must be in [-1, 16]")
+    if math.isnan(float(min_texture)) or math.isnan(float(max_rms)):
+        raise ValueError("min_texture and max_rms must not be NaN")
+    return _lib.StereoSearchParams(int(half_window), int(min_disparity), int(max_disparity), int(uniqueness), float(min_texture),
+                                   float(max_rms), int(lr_check))
+
+
+def stereo_search_batch(images, kp, n, *, half_window: int = 5, min_disparity: int = 0, max_disparity: int = 128, uniqueness: int = 10,
+                        min_texture: float = 0.0, max_rms: float = 0.0, lr_check: int = 1, out=None, return_status: bool = False,
+                        stream=None):
+    """uR for left keypoints by a patch search along their row of the rectified right image (sship_stereo_search_batch_device; the rule
+    is in include/sship.h): images u8 [2P, h, w] ordered L0, R0, L1, R1, ... (rows may be strided, any alignment), kp f32 [U, K, 3] =
+    (x, y, score) and n i32 [U] as an extractor writes them, U = P (left-only extraction) or 2P (both images: the left units are read at
+    stride 2) -> stereo f32 [P, K, 3] = (x, uR or NaN, y) and has_depth u8 [P, K], the inputs of PoseSolver.obs_from_matches, the RANSAC
+    seed and the smoother unchanged.  out: a (stereo, has_depth) pair to write into.  return_status: also status u8 [P, K] (indices into
+    SEARCH_STATUS) and cost i64 [P, K] (C_d*, -1 where no search ran).  Asynchronous on `stream` (default: torch's current), one launch."""
+    import torch
+
+    prm = stereo_search_params(half_window, min_disparity, max_disparity, uniqueness, min_texture, max_rms, lr_check)
+    if images.dtype != torch.uint8 or images.dim() != 3 or images.shape[0] < 2 or images.shape[0] % 2:
+        raise ValueError("images must be uint8 [2 * pairs, h, w]")
+    pairs = int(images.shape[0]) // 2
+    if kp.dim() != 3 or kp.shape[2] != 3 or kp.dtype != torch.float32 or not kp.is_contiguous() or kp.shape[0] not in (pairs, 2 * pairs):
+        raise ValueError(f"kp must be a contiguous float32 tensor [{pairs} or {2 * pairs}, max_keypoints, 3]")
+    units, k = int(kp.shape[0]), int(kp.shape[1])
+    if not 1 <= k <= 4096:
+        raise ValueError("max_keypoints must be in [1, 4096]")
+    if n.dtype != torch.int32 or n.dim() != 1 or n.numel() != units or not n.is_contiguous():
+        raise ValueError(f"n must be a contiguous int32 tensor with {units} entries, one per unit of kp")
+    h, w = int(images.shape[1]), int(images.shape[2])
+    if not (1 <= h <= 16384 and 1 <= w <= 16384):
+        raise ValueError("h and w must be in [1, 16384]")
+    if (w > 1 and images.stride(2) != 1) or (h > 1 and images.stride(1) < w) or images.stride(0) != h * images.stride(1):
+        raise ValueError("images must have unit stride along x, a row stride >= w and be packed as [2 * pairs, h, row stride]")
+    if out is None:
+        out = (torch.empty((pairs, k, 3), dtype=torch.float32, device=kp.device), torch.empty((pairs, k), dtype=torch.uint8, device=kp.device))
+    so, ho = out
+    for name, t, shape, dt in (("out[0]", so, (pairs, k, 3), torch.float32), ("out[1]", ho, (pairs, k), torch.uint8)):
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor {list(shape)}")
+    if not all(t.is_cuda for t in (images, kp, n, so, ho)):
+        raise ValueError("images, kp, n and out must be device tensors")
+    status = torch.empty((pairs, k), dtype=torch.uint8, device=kp.device) if return_status else None
+    cost = torch.empty((pairs, k), dtype=torch.int64, device=kp.device) if return_status else None
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    _lib.check(_lib.lib().sship_stereo_search_batch_device(images.data_ptr(), pairs, h, w, int(images.stride(1)) if h > 1 else w, kp.data_ptr(),
+                                                           n.data_ptr(), units // pairs, k, _lib.C.byref(prm), so.data_ptr(), ho.data_ptr(),
+                                                           status.data_ptr() if return_status else None,
+                                                           cost.data_ptr() if return_status else None, s))
+    return (so, ho, status, cost) if return_status else (so, ho)
+
+
+def stereo_search(left: np.ndarray, right: np.ndarray, keypoints: np.ndarray, *, half_window: int = 5, min_disparity: int = 0,
+                  max_disparity: int = 128, uniqueness: int = 10, min_texture: float = 0.0, max_rms: float = 0.0, lr_check: int = 1,
+                  return_status: bool = False):
+    """One pair from host arrays (sship_stereo_search_host): left / right u8 [h, w] (rows may be strided), keypoints f32 [n, >= 2] with
+    (x, y) in the first two columns -> (stereo f32 [n, 3] = (x, uR or NaN, y), has_depth u8 [n]); return_status: also status u8 [n] and
+    cost i64 [n].  Synchronous."""
+    prm = stereo_search_params(half_window, min_disparity, max_disparity, uniqueness, min_texture, max_rms, lr_check)
+    for name, im in (("left", left), ("right", right)):
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 2:
+            raise ValueError(f"{name} must be a uint8 array [h, w]")
+    if left.shape != right.shape:
+        raise ValueError("left and right must have the same shape")
+    h, w = left.shape
+    if not (1 <= h <= 16384 and 1 <= w <= 16384):
+        raise ValueError("h and w must be in [1, 16384]")
+    left, right = (im if (im.strides[1] == 1 or w == 1) and (im.strides[0] >= w or h == 1) else np.ascontiguousarray(im) for im in (left, right))
+    kp = np.ascontiguousarray(keypoints, np.float32)
+    if kp.ndim != 2 or kp.shape[1] < 2:
+        raise ValueError("keypoints must be [n, >= 2]")
+    n = len(kp)
+    if n > 4096:
+        raise ValueError("n must be at most 4096")
+    so, ho = np.empty((n, 3), np.float32), np.empty(n, np.uint8)
+    status, cost = np.zeros(n, np.uint8), np.full(n, -1, np.int64)
+    row = lambda im: int(im.strides[0]) if h > 1 else w   # noqa: E731
+    _lib.check(_lib.lib().sship_stereo_search_host(left.ctypes.data, row(left), right.ctypes.data, row(right), h, w, kp.ctypes.data,
+                                                   int(kp.shape[1]), n, _lib.C.byref(prm), so.ctypes.data, ho.ctypes.data, status.ctypes.data,
+                                                   cost.ctypes.data))
+    return (so, ho, status, cost) if return_status else (so, ho)
+
+
 class FrontEndBatch:
     """Device-resident throughput step: SuperPoint on 2P images + LightGlue on P pairs, no host sync."""
 
