@@ -17,6 +17,7 @@
 #include "../../include/sship.h"
 #include "../../include/superslam_hip/place_recognizer.hpp"
 #include "kernels.h"
+#include "stage_layout.h"
 
 namespace sship {
 
@@ -72,6 +73,23 @@ struct PinBuf {
     return e;
   }
   template <class T> T* as() const { return static_cast<T*>(p); }
+};
+// One staged item (csrc/stage_layout.h): the layout's input region, then its output region from `out` on, in one device block.  A handle
+// mirrors it slot for slot in one pinned block, so an offset names the same field on both sides; a per-call arena has no mirror.
+struct StageArena {
+  DevBuf d;
+  PinBuf h;
+  size_t out = 0;
+  hipError_t create(size_t in_bytes, size_t out_bytes, bool pinned = true) {
+    out = StageLayout{in_bytes}.add(0);
+    hipError_t e = d.ensure(out + out_bytes);
+    if (e == hipSuccess && pinned) e = h.ensure(out + out_bytes);
+    return e;
+  }
+  template <class T> T* dev(size_t off) const { return reinterpret_cast<T*>(d.as<char>() + off); }
+  template <class T> T* host(size_t off) const { return reinterpret_cast<T*>(h.as<char>() + off); }
+  hipError_t upload(size_t off, size_t bytes, hipStream_t s) const { return hipMemcpyAsync(dev<char>(off), host<char>(off), bytes, hipMemcpyHostToDevice, s); }
+  hipError_t download(size_t off, size_t bytes, hipStream_t s) const { return hipMemcpyAsync(host<char>(off), dev<char>(off), bytes, hipMemcpyDeviceToHost, s); }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -365,6 +383,28 @@ static int bench_loop(hipStream_t s, int iters, Run run, float* avg_ms) {
   float ms = 0.f;
   SSHIP_HIP_CHECK(hipEventElapsedTime(&ms, ev.e0, ev.e1));
   *avg_ms = ms / iters;
+  return SSHIP_OK;
+}
+
+// The measurement hook of the handles that keep their last call's arguments in `last` (nn, index, pose, ransac, ba, pg): `run` holds the
+// handle's only launch call and is re-run on the handle's stream.  `who` is the entry's name, `verb` what the caller has to run first.
+template <class Handle>
+static int bench_last(Handle* h, int iters, float* avg_ms, const char* who, const char* verb,
+                      hipError_t (*run)(const Handle*, const typename Handle::Last&, hipStream_t)) {
+  if (!h || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": bad arguments");
+  if (h->last.items <= 0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": run a " + verb + " on this handle first");
+  bind_thread();
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
+  return bench_loop(h->stream, iters, [&]() { return run(h, h->last, h->stream); }, avg_ms);
+}
+// the two parameter checks the iterative solvers (pose, ba, pg) word alike
+static int check_lambda(const char* who, double lambda0, double lambda_max) {
+  if (!(lambda0 > 0.0) || lambda_max < lambda0 || std::isinf(lambda_max))
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": lambda0 must be > 0 and lambda_max finite and >= lambda0");
+  return SSHIP_OK;
+}
+static int check_max_iterations(const char* who, int max_iterations) {
+  if (max_iterations < 1) return fail(SSHIP_ERR_INVALID, std::string(who) + ": max_iterations must be >= 1");
   return SSHIP_OK;
 }
 
@@ -2219,15 +2259,11 @@ struct sship_nn {
   int gate_on = 0;
   float gate[4] = {-INFINITY, INFINITY, -INFINITY, INFINITY};
   hipStream_t stream = nullptr;
-  DevBuf ws, desc_stage, kp_stage, lens, m0, ms0;
-  PinBuf h_lens, h_m0, h_ms0, h_desc, h_kp;
+  DevBuf ws;
+  StageArena one;   // the single-pair entries: one staged pair and its results (nn_stage)
   // the last call's launch arguments (sship_nn_bench re-runs them; the caller keeps a batch call's buffers alive until then)
-  const int* last_n = nullptr;
-  const _Float16* last_desc = nullptr;
-  const float* last_kp = nullptr;  // non-null: the last call was gated
-  int32_t* last_m0 = nullptr;
-  float* last_ms0 = nullptr;
-  int last_pairs = 0;
+  struct Last { const int* n = nullptr; const _Float16* desc = nullptr; const float* kp = nullptr;  // kp non-null: the last call was gated
+                int items = 0; int32_t* m0 = nullptr; float* ms0 = nullptr; } last;
 };
 extern "C" int sship_nn_create(int max_kp, int max_pairs, sship_nn** out) {
   if (!out) return fail(SSHIP_ERR_INVALID, "nn_create: null argument");
@@ -2238,18 +2274,9 @@ extern "C" int sship_nn_create(int max_kp, int max_pairs, sship_nn** out) {
   std::unique_ptr<sship_nn, void (*)(sship_nn*)> nn(new sship_nn(), sship_nn_destroy);
   nn->max_kp = max_kp; nn->max_pairs = max_pairs;
   SSHIP_HIP_CHECK(nn->ws.ensure(nn_workspace_floats(max_kp, max_pairs) * 4));
-  SSHIP_HIP_CHECK(nn->desc_stage.ensure(2 * (size_t)max_kp * 256 * 2));
-  SSHIP_HIP_CHECK(nn->kp_stage.ensure(2 * (size_t)max_kp * 3 * 4));
-  SSHIP_HIP_CHECK(nn->lens.ensure(2 * 4));
-  SSHIP_HIP_CHECK(nn->m0.ensure((size_t)max_kp * 4));
-  SSHIP_HIP_CHECK(nn->ms0.ensure((size_t)max_kp * 4));
-  SSHIP_HIP_CHECK(nn->h_lens.ensure(2 * 4));
-  SSHIP_HIP_CHECK(nn->h_m0.ensure((size_t)max_kp * 4));
-  SSHIP_HIP_CHECK(nn->h_ms0.ensure((size_t)max_kp * 4));
-  SSHIP_HIP_CHECK(nn->h_desc.ensure(2 * (size_t)max_kp * 256 * 2));
-  SSHIP_HIP_CHECK(nn->h_kp.ensure(2 * (size_t)max_kp * 3 * 4));
-  SSHIP_HIP_CHECK(hipMemset(nn->desc_stage.p, 0, nn->desc_stage.bytes));
-  SSHIP_HIP_CHECK(hipMemset(nn->kp_stage.p, 0, nn->kp_stage.bytes));
+  const NnStage st = nn_stage(max_kp);
+  SSHIP_HIP_CHECK(nn->one.create(st.in_bytes, st.out_bytes));
+  SSHIP_HIP_CHECK(hipMemset(nn->one.dev<char>(st.desc), 0, st.in_bytes - st.desc));   // the descriptor and keypoint slots: rows never staged are zero
   SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&nn->stream, hipStreamDefault));
   *out = nn.release();
   return SSHIP_OK;
@@ -2287,11 +2314,14 @@ extern "C" int sship_nn_get_gate(const sship_nn* nn, int* enabled, float* dx_lo,
   return SSHIP_OK;
 }
 // kp == nullptr: the plain launches (a handle without a gate); otherwise the gated ones with the handle's window
+static hipError_t nn_run(const sship_nn* nn, const sship_nn::Last& l, hipStream_t s) {
+  if (l.kp) launch_nn_match_gated(l.desc, l.kp, l.n, nn->max_kp, l.items, nn->ws.as<float>(), nn->ratio, nn->dist, nn->mutual, nn->gate, l.m0, l.ms0, s);
+  else launch_nn_match(l.desc, l.n, nn->max_kp, l.items, nn->ws.as<float>(), nn->ratio, nn->dist, nn->mutual, l.m0, l.ms0, s);
+  return hipGetLastError();
+}
 static int nn_launch(sship_nn* nn, const int* n, const _Float16* desc, const float* kp, int pairs, int32_t* m0, float* ms0, hipStream_t s) {
-  if (kp) launch_nn_match_gated(desc, kp, n, nn->max_kp, pairs, nn->ws.as<float>(), nn->ratio, nn->dist, nn->mutual, nn->gate, m0, ms0, s);
-  else launch_nn_match(desc, n, nn->max_kp, pairs, nn->ws.as<float>(), nn->ratio, nn->dist, nn->mutual, m0, ms0, s);
-  SSHIP_HIP_CHECK(hipGetLastError());
-  nn->last_n = n; nn->last_desc = desc; nn->last_kp = kp; nn->last_m0 = m0; nn->last_ms0 = ms0; nn->last_pairs = pairs;
+  nn->last = {n, desc, kp, pairs, m0, ms0};
+  SSHIP_HIP_CHECK(nn_run(nn, nn->last, s));
   return SSHIP_OK;
 }
 static const char kNnGatedMsg[] = ": the handle's gate is enabled - use the _gated entry point (keypoints are needed)";
@@ -2332,29 +2362,27 @@ extern "C" int sship_stereo_associate_batch_device(const float* kp, const int* n
   g_timer.mark("stereo_associate", s);
   return SSHIP_OK;
 }
-// one pair out of the handle's own staging buffers (descriptors already enqueued into desc_stage on the handle's stream)
-// gated (kp0 != nullptr): the host keypoints go into kp_stage as [2][max_kp][3] (x, y, 0) first
+// one pair out of the handle's arena (descriptors already enqueued into its desc slot on the handle's stream)
+// gated (kp0 != nullptr): the host keypoints go into the kp slot as [2][max_kp][3] (x, y, 0) first
 static int nn_match_common(sship_nn* nn, int n0, int n1, int32_t* matches0, float* mscores0, const float* kp0 = nullptr, int st0 = 0,
                            const float* kp1 = nullptr, int st1 = 0) {
   hipStream_t s = nn->stream;
-  nn->h_lens.as<int>()[0] = n0; nn->h_lens.as<int>()[1] = n1;
-  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->lens.p, nn->h_lens.p, 8, hipMemcpyHostToDevice, s));
+  const StageArena& a = nn->one;
+  const NnStage st = nn_stage(nn->max_kp);
+  nn_pack_lens(a.host<char>(0), st, n0, n1);
+  SSHIP_HIP_CHECK(a.upload(st.lens, 2 * sizeof(int), s));
   if (kp0) {
-    float* hk = nn->h_kp.as<float>();
-    float* hk1 = hk + (size_t)nn->max_kp * 3;
-    for (int i = 0; i < n0; ++i) { hk[3 * i] = kp0[(size_t)i * st0]; hk[3 * i + 1] = kp0[(size_t)i * st0 + 1]; hk[3 * i + 2] = 0.f; }
-    for (int i = 0; i < n1; ++i) { hk1[3 * i] = kp1[(size_t)i * st1]; hk1[3 * i + 1] = kp1[(size_t)i * st1 + 1]; hk1[3 * i + 2] = 0.f; }
-    SSHIP_HIP_CHECK(hipMemcpyAsync(nn->kp_stage.p, hk, (size_t)n0 * 12, hipMemcpyHostToDevice, s));
-    SSHIP_HIP_CHECK(hipMemcpyAsync(nn->kp_stage.as<float>() + (size_t)nn->max_kp * 3, hk1, (size_t)n1 * 12, hipMemcpyHostToDevice, s));
+    nn_pack_kp(a.host<char>(0), st, kp0, st0, n0, kp1, st1, n1);
+    SSHIP_HIP_CHECK(a.upload(st.kp, (size_t)n0 * 3 * sizeof(float), s));
+    SSHIP_HIP_CHECK(a.upload(st.kp1, (size_t)n1 * 3 * sizeof(float), s));
   }
-  if (int rc = nn_launch(nn, nn->lens.as<int>(), nn->desc_stage.as<_Float16>(), kp0 ? nn->kp_stage.as<float>() : nullptr, 1,
-                         nn->m0.as<int32_t>(), nn->ms0.as<float>(), s))
+  if (int rc = nn_launch(nn, a.dev<int>(st.lens), a.dev<_Float16>(st.desc), kp0 ? a.dev<float>(st.kp) : nullptr, 1, a.dev<int32_t>(a.out + st.m0),
+                         a.dev<float>(a.out + st.ms0), s))
     return rc;
-  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->h_m0.p, nn->m0.p, (size_t)n0 * 4, hipMemcpyDeviceToHost, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->h_ms0.p, nn->ms0.p, (size_t)n0 * 4, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(a.download(a.out + st.m0, (size_t)n0 * sizeof(int32_t), s));
+  SSHIP_HIP_CHECK(a.download(a.out + st.ms0, (size_t)n0 * sizeof(float), s));
   SSHIP_HIP_CHECK(hipStreamSynchronize(s));
-  memcpy(matches0, nn->h_m0.p, (size_t)n0 * 4);
-  memcpy(mscores0, nn->h_ms0.p, (size_t)n0 * 4);
+  nn_unpack(a.host<char>(a.out), st, n0, matches0, mscores0);
   return SSHIP_OK;
 }
 static int nn_check_pair(const sship_nn* nn, int n0, const void* d0, int n1, const void* d1, const void* m0, const void* ms0, const char* who) {
@@ -2371,9 +2399,9 @@ static int nn_check_kp(const sship_nn* nn, const float* kp0, int st0, const floa
   return SSHIP_OK;
 }
 static int nn_stage_device(sship_nn* nn, int n0, const void* desc0, int n1, const void* desc1) {
-  hipStream_t s = nn->stream;
-  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->desc_stage.p, desc0, (size_t)n0 * 512, hipMemcpyDeviceToDevice, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->desc_stage.as<_Float16>() + (size_t)nn->max_kp * 256, desc1, (size_t)n1 * 512, hipMemcpyDeviceToDevice, s));
+  const NnStage st = nn_stage(nn->max_kp);
+  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->one.dev<char>(st.desc), desc0, (size_t)n0 * 256 * sizeof(_Float16), hipMemcpyDeviceToDevice, nn->stream));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->one.dev<char>(st.desc1), desc1, (size_t)n1 * 256 * sizeof(_Float16), hipMemcpyDeviceToDevice, nn->stream));
   return SSHIP_OK;
 }
 static int nn_stage_host(sship_nn* nn, int n0, const float* desc0, int n1, const float* desc1);
@@ -2410,33 +2438,14 @@ extern "C" int sship_nn_match_host(sship_nn* nn, int n0, const float* desc0, int
   return nn_match_common(nn, n0, n1, matches0, mscores0);
 }
 static int nn_stage_host(sship_nn* nn, int n0, const float* desc0, int n1, const float* desc1) {
-  hipStream_t s = nn->stream;
-  _Float16* hd = nn->h_desc.as<_Float16>();  // CV_32F -> fp16 on the host, as sship_lg_match_host
-  for (size_t i = 0; i < (size_t)n0 * 256; ++i) hd[i] = (_Float16)desc0[i];
-  for (size_t i = 0; i < (size_t)n1 * 256; ++i) hd[(size_t)nn->max_kp * 256 + i] = (_Float16)desc1[i];
-  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->desc_stage.p, hd, (size_t)n0 * 512, hipMemcpyHostToDevice, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(nn->desc_stage.as<_Float16>() + (size_t)nn->max_kp * 256, hd + (size_t)nn->max_kp * 256, (size_t)n1 * 512,
-                                 hipMemcpyHostToDevice, s));
+  const NnStage st = nn_stage(nn->max_kp);
+  nn_pack_desc(nn->one.host<char>(0), st, n0, desc0, n1, desc1);
+  SSHIP_HIP_CHECK(nn->one.upload(st.desc, (size_t)n0 * 256 * sizeof(_Float16), nn->stream));
+  SSHIP_HIP_CHECK(nn->one.upload(st.desc1, (size_t)n1 * 256 * sizeof(_Float16), nn->stream));
   return SSHIP_OK;
 }
-// Measurement hook (include/sship.h): the last call's two launches re-run `iters` times on the handle's stream.
-extern "C" int sship_nn_bench(sship_nn* nn, int iters, float* avg_ms) {
-  if (!nn || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "nn_bench: bad arguments");
-  if (nn->last_pairs <= 0) return fail(SSHIP_ERR_INVALID, "nn_bench: run a match on this handle first");
-  bind_thread();
-  hipStream_t s = nn->stream;
-  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
-  auto run = [&]() -> hipError_t {  // the gated launches after a gated call
-    if (nn->last_kp)
-      launch_nn_match_gated(nn->last_desc, nn->last_kp, nn->last_n, nn->max_kp, nn->last_pairs, nn->ws.as<float>(), nn->ratio, nn->dist,
-                            nn->mutual, nn->gate, nn->last_m0, nn->last_ms0, s);
-    else
-      launch_nn_match(nn->last_desc, nn->last_n, nn->max_kp, nn->last_pairs, nn->ws.as<float>(), nn->ratio, nn->dist, nn->mutual, nn->last_m0,
-                      nn->last_ms0, s);
-    return hipGetLastError();
-  };
-  return bench_loop(s, iters, run, avg_ms);
-}
+// Measurement hook (include/sship.h): the last call's two launches (the gated ones after a gated call) re-run `iters` times on the handle's stream.
+extern "C" int sship_nn_bench(sship_nn* nn, int iters, float* avg_ms) { return bench_last(nn, iters, avg_ms, "nn_bench", "match", nn_run); }
 
 // ====================================================================================================
 // EigenPlaces place recogniser: include/EigenPlaces.h:19-40, src/EigenPlaces.cc:47-174
@@ -2758,10 +2767,9 @@ struct sship_index {
   std::vector<int64_t> ids;     // [size] keyframe ids
   hipStream_t stream = nullptr;
   DevBuf db, qn, partial;       // [capacity][dim] stored rows; [ceil16(max_queries)][dim] normalised queries; chunk partials
-  DevBuf q1, rows1, scores1, count1;   // the per-query calls: one staged query and its results
-  PinBuf h_q, h_rows, h_scores, h_count;
+  StageArena one;               // the per-query calls: one staged query and its results (index_stage)
   // the last query call's arguments (sship_index_bench re-runs its launches; the caller keeps a batch call's buffers alive until then)
-  struct Last { const float* q = nullptr; long long q_stride = 0; int nq = 0; const int* limits = nullptr; int limit_all = 0, top_k = 0, size = 0;
+  struct Last { const float* q = nullptr; long long q_stride = 0; int items = 0; const int* limits = nullptr; int limit_all = 0, top_k = 0, size = 0;
                 float min_score = 0.f; int* rows = nullptr; float* scores = nullptr; int* counts = nullptr; } last;
 };
 extern "C" int sship_index_create(int dim, int capacity, int max_queries, int max_top_k, sship_index** out) {
@@ -2781,14 +2789,8 @@ extern "C" int sship_index_create(int dim, int capacity, int max_queries, int ma
   SSHIP_HIP_CHECK(ix->db.ensure((size_t)capacity * dim * 4));
   SSHIP_HIP_CHECK(ix->qn.ensure(qpad * dim * 4));
   SSHIP_HIP_CHECK(ix->partial.ensure(chunks * max_queries * max_top_k * 8));
-  SSHIP_HIP_CHECK(ix->q1.ensure((size_t)dim * 4));
-  SSHIP_HIP_CHECK(ix->rows1.ensure((size_t)max_top_k * 4));
-  SSHIP_HIP_CHECK(ix->scores1.ensure((size_t)max_top_k * 4));
-  SSHIP_HIP_CHECK(ix->count1.ensure(4));
-  SSHIP_HIP_CHECK(ix->h_q.ensure((size_t)dim * 4));
-  SSHIP_HIP_CHECK(ix->h_rows.ensure((size_t)max_top_k * 4));
-  SSHIP_HIP_CHECK(ix->h_scores.ensure((size_t)max_top_k * 4));
-  SSHIP_HIP_CHECK(ix->h_count.ensure(4));
+  const IndexStage st = index_stage(dim, max_top_k);
+  SSHIP_HIP_CHECK(ix->one.create(st.in_bytes, st.out_bytes));
   SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&ix->stream, hipStreamDefault));
   *out = ix.release();
   return SSHIP_OK;
@@ -2854,15 +2856,15 @@ static int index_check_query(const sship_index* ix, int exclude_recent, int top_
   if (std::isnan(min_score)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": min_score is NaN");
   return SSHIP_OK;
 }
+static hipError_t index_run(const sship_index* ix, const sship_index::Last& l, hipStream_t s) {
+  launch_index_query(ix->db.as<float>(), ix->dim, l.size, l.q, l.q_stride, l.items, l.limits, l.limit_all, l.top_k, l.min_score, ix->qn.as<float>(),
+                     ix->partial.as<unsigned long long>(), l.rows, l.scores, l.counts, s);
+  return hipGetLastError();
+}
 static int index_launch(sship_index* ix, const float* q, long long q_stride, int nq, const int* limits, int exclude_recent, int top_k, float min_score,
                         int* rows, float* scores, int* counts, hipStream_t s) {
-  sship_index::Last& l = ix->last;
-  l.q = q; l.q_stride = q_stride; l.nq = nq; l.limits = limits; l.top_k = top_k; l.min_score = min_score; l.size = ix->size;
-  l.limit_all = exclude_recent >= ix->size ? 0 : ix->size - exclude_recent;
-  l.rows = rows; l.scores = scores; l.counts = counts;
-  launch_index_query(ix->db.as<float>(), ix->dim, l.size, q, q_stride, nq, limits, l.limit_all, top_k, min_score, ix->qn.as<float>(),
-                     ix->partial.as<unsigned long long>(), rows, scores, counts, s);
-  SSHIP_HIP_CHECK(hipGetLastError());
+  ix->last = {q, q_stride, nq, limits, exclude_recent >= ix->size ? 0 : ix->size - exclude_recent, top_k, ix->size, min_score, rows, scores, counts};
+  SSHIP_HIP_CHECK(index_run(ix, ix->last, s));
   return SSHIP_OK;
 }
 extern "C" int sship_index_query_batch_device(sship_index* ix, const float* q_dev, int num_queries, int q_stride, const int32_t* limits_dev,
@@ -2879,25 +2881,19 @@ extern "C" int sship_index_query_batch_device(sship_index* ix, const float* q_de
   g_timer.mark("index_query:stream_final", s);
   return SSHIP_OK;
 }
-// one query, already enqueued into q1 on the handle's stream: the batch launches with Q = 1, results mapped to ids on the host
+// one query, already enqueued into the arena's q slot on the handle's stream: the batch launches with Q = 1, results mapped to ids on the host
 static int index_query_one(sship_index* ix, int exclude_recent, int top_k, float min_score, int64_t* ids_out, float* scores_out, int* count_out) {
   hipStream_t s = ix->stream;
-  if (int rc = index_launch(ix, ix->q1.as<float>(), ix->dim, 1, nullptr, exclude_recent, top_k, min_score, ix->rows1.as<int>(), ix->scores1.as<float>(),
-                            ix->count1.as<int>(), s))
+  const StageArena& a = ix->one;
+  const IndexStage st = index_stage(ix->dim, ix->max_top_k);
+  if (int rc = index_launch(ix, a.dev<float>(st.q), ix->dim, 1, nullptr, exclude_recent, top_k, min_score, a.dev<int>(a.out + st.rows),
+                            a.dev<float>(a.out + st.scores), a.dev<int>(a.out + st.count), s))
     return rc;
-  SSHIP_HIP_CHECK(hipMemcpyAsync(ix->h_rows.p, ix->rows1.p, (size_t)top_k * 4, hipMemcpyDeviceToHost, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(ix->h_scores.p, ix->scores1.p, (size_t)top_k * 4, hipMemcpyDeviceToHost, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(ix->h_count.p, ix->count1.p, 4, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(a.download(a.out, st.out_bytes, s));
   SSHIP_HIP_CHECK(hipStreamSynchronize(s));
-  const int n = ix->h_count.as<int>()[0];
-  if (n < 0 || n > top_k) return fail(SSHIP_ERR_HIP, "index_query: the device returned an impossible count");
-  for (int i = 0; i < n; ++i) {
-    const int row = ix->h_rows.as<int>()[i];
-    if (row < 0 || row >= ix->size) return fail(SSHIP_ERR_HIP, "index_query: the device returned a row outside the index");
-    ids_out[i] = ix->ids[row];
-    scores_out[i] = ix->h_scores.as<float>()[i];
-  }
-  *count_out = n;
+  const int bad = index_unpack(a.host<char>(a.out), st, top_k, ix->ids.data(), ix->size, ids_out, scores_out, count_out);
+  if (bad == 1) return fail(SSHIP_ERR_HIP, "index_query: the device returned an impossible count");
+  if (bad == 2) return fail(SSHIP_ERR_HIP, "index_query: the device returned a row outside the index");
   return SSHIP_OK;
 }
 static int index_check_one(const sship_index* ix, const float* desc, int exclude_recent, int top_k, float min_score, const int64_t* ids_out,
@@ -2909,32 +2905,21 @@ extern "C" int sship_index_query_host(sship_index* ix, const float* desc, int ex
                                       float* scores_out, int* count_out) {
   if (int rc = index_check_one(ix, desc, exclude_recent, top_k, min_score, ids_out, scores_out, count_out, "index_query_host")) return rc;
   bind_thread();
-  memcpy(ix->h_q.p, desc, (size_t)ix->dim * 4);
-  SSHIP_HIP_CHECK(hipMemcpyAsync(ix->q1.p, ix->h_q.p, (size_t)ix->dim * 4, hipMemcpyHostToDevice, ix->stream));
+  const IndexStage st = index_stage(ix->dim, ix->max_top_k);
+  index_pack(ix->one.host<char>(0), st, ix->dim, desc);
+  SSHIP_HIP_CHECK(ix->one.upload(st.q, st.in_bytes - st.q, ix->stream));
   return index_query_one(ix, exclude_recent, top_k, min_score, ids_out, scores_out, count_out);
 }
 extern "C" int sship_index_query_device(sship_index* ix, const float* desc_dev, int exclude_recent, int top_k, float min_score, int64_t* ids_out,
                                         float* scores_out, int* count_out) {
   if (int rc = index_check_one(ix, desc_dev, exclude_recent, top_k, min_score, ids_out, scores_out, count_out, "index_query_device")) return rc;
   bind_thread();
-  SSHIP_HIP_CHECK(hipMemcpyAsync(ix->q1.p, desc_dev, (size_t)ix->dim * 4, hipMemcpyDeviceToDevice, ix->stream));
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ix->one.dev<float>(index_stage(ix->dim, ix->max_top_k).q), desc_dev, (size_t)ix->dim * sizeof(float), hipMemcpyDeviceToDevice,
+                                 ix->stream));
   return index_query_one(ix, exclude_recent, top_k, min_score, ids_out, scores_out, count_out);
 }
 // Measurement hook (include/sship.h): the last query call's launches (normalise, scan, merge) re-run `iters` times on the handle's stream.
-extern "C" int sship_index_bench(sship_index* ix, int iters, float* avg_ms) {
-  if (!ix || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "index_bench: bad arguments");
-  if (ix->last.nq <= 0) return fail(SSHIP_ERR_INVALID, "index_bench: run a query on this handle first");
-  bind_thread();
-  hipStream_t s = ix->stream;
-  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
-  const sship_index::Last& l = ix->last;
-  auto run = [&]() -> hipError_t {
-    launch_index_query(ix->db.as<float>(), ix->dim, l.size, l.q, l.q_stride, l.nq, l.limits, l.limit_all, l.top_k, l.min_score, ix->qn.as<float>(),
-                       ix->partial.as<unsigned long long>(), l.rows, l.scores, l.counts, s);
-    return hipGetLastError();
-  };
-  return bench_loop(s, iters, run, avg_ms);
-}
+extern "C" int sship_index_bench(sship_index* ix, int iters, float* avg_ms) { return bench_last(ix, iters, avg_ms, "index_bench", "query", index_run); }
 
 // ====================================================================================================
 // Pose-only stereo solver (include/sship.h "Pose-only stereo solver"; csrc/pose_kernels.hip)
@@ -2945,10 +2930,9 @@ struct sship_pose {
   StereoCamera cam;
   sship_pose_params prm{10.0, 8.0, 40.0, 7.815, 1e-5, 1e5, 1e-5, 1e-5, 3.0, 100};
   hipStream_t stream = nullptr;
-  DevBuf points1, meas1, valid1, pose01, pose1, stats1, cost1, inlier1;   // sship_pose_solve_host: one staged pair and its results
-  PinBuf h_in, h_out;
+  StageArena one;   // sship_pose_solve_host: one staged pair and its results (pose_stage)
   // the last solve call's arguments (sship_pose_bench re-runs its launch; the caller keeps a batch call's buffers alive until then)
-  struct Last { const float* points = nullptr; const float* meas = nullptr; const uint8_t* valid = nullptr; const double* pose0 = nullptr; int pairs = 0;
+  struct Last { const float* points = nullptr; const float* meas = nullptr; const uint8_t* valid = nullptr; const double* pose0 = nullptr; int items = 0;
                 double* pose = nullptr; int32_t* stats = nullptr; double* cost = nullptr; uint8_t* inlier = nullptr; } last;
 };
 static PoseK pose_constants(const sship_pose* ps) {
@@ -2969,17 +2953,8 @@ extern "C" int sship_pose_create(int max_obs, int max_pairs, sship_pose** out) {
   if (int rc = require_device()) return rc;
   std::unique_ptr<sship_pose, void (*)(sship_pose*)> ps(new sship_pose(), sship_pose_destroy);
   ps->max_obs = max_obs; ps->max_pairs = max_pairs;
-  const size_t n = (size_t)max_obs;
-  SSHIP_HIP_CHECK(ps->points1.ensure(n * 12));
-  SSHIP_HIP_CHECK(ps->meas1.ensure(n * 12));
-  SSHIP_HIP_CHECK(ps->valid1.ensure(n));
-  SSHIP_HIP_CHECK(ps->inlier1.ensure(n));
-  SSHIP_HIP_CHECK(ps->pose01.ensure(96));
-  SSHIP_HIP_CHECK(ps->pose1.ensure(96));
-  SSHIP_HIP_CHECK(ps->stats1.ensure(16));
-  SSHIP_HIP_CHECK(ps->cost1.ensure(16));
-  SSHIP_HIP_CHECK(ps->h_in.ensure(n * 25 + 96));
-  SSHIP_HIP_CHECK(ps->h_out.ensure(128 + n));
+  const ObsStage st = pose_stage(max_obs);
+  SSHIP_HIP_CHECK(ps->one.create(st.in_bytes, st.out_bytes));
   SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&ps->stream, hipStreamDefault));
   *out = ps.release();
   return SSHIP_OK;
@@ -2999,10 +2974,9 @@ extern "C" int sship_pose_set_params(sship_pose* ps, const sship_pose_params* p)
   if (!(p->sigma_px > 0.0) || !(p->sigma_d0 > 0.0) || !(p->cond_depth > 0.0) || !(p->huber_k2 > 0.0) || std::isinf(p->sigma_px) ||
       std::isinf(p->sigma_d0) || std::isinf(p->cond_depth) || std::isinf(p->huber_k2))
     return fail(SSHIP_ERR_INVALID, "pose_set_params: sigma_px, sigma_d0, cond_depth and huber_k2 must be finite and > 0");
-  if (!(p->lambda0 > 0.0) || p->lambda_max < p->lambda0 || std::isinf(p->lambda_max))
-    return fail(SSHIP_ERR_INVALID, "pose_set_params: lambda0 must be > 0 and lambda_max finite and >= lambda0");
+  if (int rc = check_lambda("pose_set_params", p->lambda0, p->lambda_max)) return rc;
   if (p->abs_tol < 0.0 || p->rel_tol < 0.0 || p->inlier_px < 0.0) return fail(SSHIP_ERR_INVALID, "pose_set_params: a tolerance or inlier_px is negative");
-  if (p->max_iterations < 1) return fail(SSHIP_ERR_INVALID, "pose_set_params: max_iterations must be >= 1");
+  if (int rc = check_max_iterations("pose_set_params", p->max_iterations)) return rc;
   ps->prm = *p;
   return SSHIP_OK;
 }
@@ -3011,12 +2985,14 @@ extern "C" int sship_pose_get_params(const sship_pose* ps, sship_pose_params* p)
   *p = ps->prm;
   return SSHIP_OK;
 }
+static hipError_t pose_run(const sship_pose* ps, const sship_pose::Last& l, hipStream_t s) {
+  launch_pose_solve(l.points, l.meas, l.valid, l.pose0, ps->max_obs, l.items, pose_constants(ps), l.pose, l.stats, l.cost, l.inlier, s);
+  return hipGetLastError();
+}
 static int pose_launch(sship_pose* ps, const float* points, const float* meas, const uint8_t* valid, const double* pose0, int pairs, double* pose,
                        int32_t* stats, double* cost, uint8_t* inlier, hipStream_t s) {
-  sship_pose::Last& l = ps->last;
-  l.points = points; l.meas = meas; l.valid = valid; l.pose0 = pose0; l.pairs = pairs; l.pose = pose; l.stats = stats; l.cost = cost; l.inlier = inlier;
-  launch_pose_solve(points, meas, valid, pose0, ps->max_obs, pairs, pose_constants(ps), pose, stats, cost, inlier, s);
-  SSHIP_HIP_CHECK(hipGetLastError());
+  ps->last = {points, meas, valid, pose0, pairs, pose, stats, cost, inlier};
+  SSHIP_HIP_CHECK(pose_run(ps, ps->last, s));
   return SSHIP_OK;
 }
 extern "C" int sship_pose_solve_batch_device(sship_pose* ps, const float* points, const float* meas, const uint8_t* valid, const double* pose0,
@@ -3039,34 +3015,17 @@ extern "C" int sship_pose_solve_host(sship_pose* ps, const float* points, const 
   if (!ps->cam.set) return fail(SSHIP_ERR_INVALID, "pose_solve_host: set the camera first (sship_pose_set_camera)");
   bind_thread();
   hipStream_t s = ps->stream;
-  const size_t n = (size_t)ps->max_obs, m = (size_t)n_obs;
-  // pinned staging: points | meas | pose0 | valid, rows >= n_obs absent
-  char* hin = static_cast<char*>(ps->h_in.p);
-  float* hp = reinterpret_cast<float*>(hin);
-  float* hm = reinterpret_cast<float*>(hin + n * 12);
-  double* h0 = reinterpret_cast<double*>(hin + n * 24);
-  uint8_t* hv = reinterpret_cast<uint8_t*>(hin + n * 24 + 96);
-  memset(hin, 0, n * 25 + 96);
-  if (m) { memcpy(hp, points, m * 12); memcpy(hm, meas, m * 12); }
-  for (size_t i = 0; i < m; ++i) hv[i] = valid ? (valid[i] != 0) : 1;
-  if (pose0) memcpy(h0, pose0, 96);
-  SSHIP_HIP_CHECK(hipMemcpyAsync(ps->points1.p, hp, n * 12, hipMemcpyHostToDevice, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(ps->meas1.p, hm, n * 12, hipMemcpyHostToDevice, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(ps->valid1.p, hv, n, hipMemcpyHostToDevice, s));
-  if (pose0) SSHIP_HIP_CHECK(hipMemcpyAsync(ps->pose01.p, h0, 96, hipMemcpyHostToDevice, s));
-  if (int rc = pose_launch(ps, ps->points1.as<float>(), ps->meas1.as<float>(), ps->valid1.as<uint8_t>(), pose0 ? ps->pose01.as<double>() : nullptr, 1,
-                           ps->pose1.as<double>(), ps->stats1.as<int32_t>(), ps->cost1.as<double>(), ps->inlier1.as<uint8_t>(), s))
+  const StageArena& a = ps->one;
+  const ObsStage st = pose_stage(ps->max_obs);
+  obs_pack(a.host<char>(0), st, points, meas, valid, n_obs, pose0);
+  SSHIP_HIP_CHECK(a.upload(0, st.in_bytes, s));
+  if (int rc = pose_launch(ps, a.dev<float>(st.points), a.dev<float>(st.meas), a.dev<uint8_t>(st.valid), pose0 ? a.dev<double>(st.pose0) : nullptr, 1,
+                           a.dev<double>(a.out + st.pose), a.dev<int32_t>(a.out + st.stats), a.dev<double>(a.out + st.cost),
+                           a.dev<uint8_t>(a.out + st.inlier), s))
     return rc;
-  char* hout = static_cast<char*>(ps->h_out.p);   // pose (96) | cost (16) | stats (16) | inlier
-  SSHIP_HIP_CHECK(hipMemcpyAsync(hout, ps->pose1.p, 96, hipMemcpyDeviceToHost, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(hout + 96, ps->cost1.p, 16, hipMemcpyDeviceToHost, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(hout + 112, ps->stats1.p, 16, hipMemcpyDeviceToHost, s));
-  if (inlier_out && m) SSHIP_HIP_CHECK(hipMemcpyAsync(hout + 128, ps->inlier1.p, m, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(a.download(a.out, st.out_bytes, s));
   SSHIP_HIP_CHECK(hipStreamSynchronize(s));
-  memcpy(pose_out, hout, 96);
-  memcpy(cost_out, hout + 96, 16);
-  memcpy(stats_out, hout + 112, 16);
-  if (inlier_out && m) memcpy(inlier_out, hout + 128, m);
+  obs_unpack(a.host<char>(a.out), st, n_obs, pose_out, stats_out, cost_out, inlier_out);
   return SSHIP_OK;
 }
 extern "C" int sship_pose_obs_from_matches_batch_device(const sship_pose* ps, const float* stereo0, const uint8_t* hd0, const float* stereo1,
@@ -3086,20 +3045,7 @@ extern "C" int sship_pose_obs_from_matches_batch_device(const sship_pose* ps, co
   return SSHIP_OK;
 }
 // Measurement hook (include/sship.h): the last solve call's launch re-run `iters` times on the handle's stream.
-extern "C" int sship_pose_bench(sship_pose* ps, int iters, float* avg_ms) {
-  if (!ps || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "pose_bench: bad arguments");
-  if (ps->last.pairs <= 0) return fail(SSHIP_ERR_INVALID, "pose_bench: run a solve on this handle first");
-  bind_thread();
-  hipStream_t s = ps->stream;
-  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
-  const sship_pose::Last& l = ps->last;
-  const PoseK k = pose_constants(ps);
-  auto run = [&]() -> hipError_t {
-    launch_pose_solve(l.points, l.meas, l.valid, l.pose0, ps->max_obs, l.pairs, k, l.pose, l.stats, l.cost, l.inlier, s);
-    return hipGetLastError();
-  };
-  return bench_loop(s, iters, run, avg_ms);
-}
+extern "C" int sship_pose_bench(sship_pose* ps, int iters, float* avg_ms) { return bench_last(ps, iters, avg_ms, "pose_bench", "solve", pose_run); }
 
 // ====================================================================================================
 // RANSAC pose seed and inlier gate (include/sship.h "RANSAC pose seed and inlier gate"; csrc/ransac_kernels.hip)
@@ -3110,10 +3056,9 @@ struct sship_ransac {
   sship_ransac_params prm{3.0, 1.0, 1e-8, 1u, 512};
   hipStream_t stream = nullptr;
   DevBuf workspace;                                            // [max_pairs, splits] records between the two launches
-  DevBuf points1, meas1, valid1, pose1, stats1, cost1, inlier1;   // sship_ransac_solve_host: one staged pair and its results
-  PinBuf h_in, h_out;
+  StageArena one;                                              // sship_ransac_solve_host: one staged pair and its results (ransac_stage)
   // the last solve call's arguments (sship_ransac_bench re-runs its launches; the caller keeps a batch call's buffers alive until then)
-  struct Last { const float* points = nullptr; const float* meas = nullptr; const uint8_t* valid = nullptr; int pairs = 0;
+  struct Last { const float* points = nullptr; const float* meas = nullptr; const uint8_t* valid = nullptr; int items = 0;
                 double* pose = nullptr; int32_t* stats = nullptr; double* cost = nullptr; uint8_t* inlier = nullptr; } last;
 };
 static RansacK ransac_constants(const sship_ransac* rs) {
@@ -3132,17 +3077,9 @@ extern "C" int sship_ransac_create(int max_obs, int max_pairs, sship_ransac** ou
   if (int rc = require_device()) return rc;
   std::unique_ptr<sship_ransac, void (*)(sship_ransac*)> rs(new sship_ransac(), sship_ransac_destroy);
   rs->max_obs = max_obs; rs->max_pairs = max_pairs;
-  const size_t n = (size_t)max_obs;
+  const ObsStage st = ransac_stage(max_obs);
   SSHIP_HIP_CHECK(rs->workspace.ensure(ransac_workspace_bytes(max_pairs, rs->prm.num_hypotheses)));
-  SSHIP_HIP_CHECK(rs->points1.ensure(n * 12));
-  SSHIP_HIP_CHECK(rs->meas1.ensure(n * 12));
-  SSHIP_HIP_CHECK(rs->valid1.ensure(n));
-  SSHIP_HIP_CHECK(rs->inlier1.ensure(n));
-  SSHIP_HIP_CHECK(rs->pose1.ensure(96));
-  SSHIP_HIP_CHECK(rs->stats1.ensure(16));
-  SSHIP_HIP_CHECK(rs->cost1.ensure(8));
-  SSHIP_HIP_CHECK(rs->h_in.ensure(n * 25));
-  SSHIP_HIP_CHECK(rs->h_out.ensure(128 + n));
+  SSHIP_HIP_CHECK(rs->one.create(st.in_bytes, st.out_bytes));
   SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&rs->stream, hipStreamDefault));
   *out = rs.release();
   return SSHIP_OK;
@@ -3176,12 +3113,14 @@ extern "C" int sship_ransac_get_params(const sship_ransac* rs, sship_ransac_para
   *p = rs->prm;
   return SSHIP_OK;
 }
+static hipError_t ransac_run(const sship_ransac* rs, const sship_ransac::Last& l, hipStream_t s) {
+  launch_ransac_solve(l.points, l.meas, l.valid, rs->max_obs, l.items, ransac_constants(rs), rs->workspace.p, l.pose, l.stats, l.cost, l.inlier, s);
+  return hipGetLastError();
+}
 static int ransac_launch(sship_ransac* rs, const float* points, const float* meas, const uint8_t* valid, int pairs, double* pose, int32_t* stats,
                          double* cost, uint8_t* inlier, hipStream_t s) {
-  sship_ransac::Last& l = rs->last;
-  l.points = points; l.meas = meas; l.valid = valid; l.pairs = pairs; l.pose = pose; l.stats = stats; l.cost = cost; l.inlier = inlier;
-  launch_ransac_solve(points, meas, valid, rs->max_obs, pairs, ransac_constants(rs), rs->workspace.p, pose, stats, cost, inlier, s);
-  SSHIP_HIP_CHECK(hipGetLastError());
+  rs->last = {points, meas, valid, pairs, pose, stats, cost, inlier};
+  SSHIP_HIP_CHECK(ransac_run(rs, rs->last, s));
   return SSHIP_OK;
 }
 extern "C" int sship_ransac_solve_batch_device(sship_ransac* rs, const float* points, const float* meas, const uint8_t* valid, int pairs,
@@ -3204,48 +3143,20 @@ extern "C" int sship_ransac_solve_host(sship_ransac* rs, const float* points, co
   if (!rs->cam.set) return fail(SSHIP_ERR_INVALID, "ransac_solve_host: set the camera first (sship_ransac_set_camera)");
   bind_thread();
   hipStream_t s = rs->stream;
-  const size_t n = (size_t)rs->max_obs, m = (size_t)n_obs;
-  // pinned staging: points | meas | valid, rows >= n_obs absent
-  char* hin = static_cast<char*>(rs->h_in.p);
-  float* hp = reinterpret_cast<float*>(hin);
-  float* hm = reinterpret_cast<float*>(hin + n * 12);
-  uint8_t* hv = reinterpret_cast<uint8_t*>(hin + n * 24);
-  memset(hin, 0, n * 25);
-  if (m) { memcpy(hp, points, m * 12); memcpy(hm, meas, m * 12); }
-  for (size_t i = 0; i < m; ++i) hv[i] = valid ? (valid[i] != 0) : 1;
-  SSHIP_HIP_CHECK(hipMemcpyAsync(rs->points1.p, hp, n * 12, hipMemcpyHostToDevice, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(rs->meas1.p, hm, n * 12, hipMemcpyHostToDevice, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(rs->valid1.p, hv, n, hipMemcpyHostToDevice, s));
-  if (int rc = ransac_launch(rs, rs->points1.as<float>(), rs->meas1.as<float>(), rs->valid1.as<uint8_t>(), 1, rs->pose1.as<double>(),
-                             rs->stats1.as<int32_t>(), rs->cost1.as<double>(), rs->inlier1.as<uint8_t>(), s))
+  const StageArena& a = rs->one;
+  const ObsStage st = ransac_stage(rs->max_obs);
+  obs_pack(a.host<char>(0), st, points, meas, valid, n_obs, nullptr);
+  SSHIP_HIP_CHECK(a.upload(0, st.in_bytes, s));
+  if (int rc = ransac_launch(rs, a.dev<float>(st.points), a.dev<float>(st.meas), a.dev<uint8_t>(st.valid), 1, a.dev<double>(a.out + st.pose),
+                             a.dev<int32_t>(a.out + st.stats), a.dev<double>(a.out + st.cost), a.dev<uint8_t>(a.out + st.inlier), s))
     return rc;
-  char* hout = static_cast<char*>(rs->h_out.p);   // pose (96) | cost (8) | stats (16) | inlier
-  SSHIP_HIP_CHECK(hipMemcpyAsync(hout, rs->pose1.p, 96, hipMemcpyDeviceToHost, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(hout + 96, rs->cost1.p, 8, hipMemcpyDeviceToHost, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(hout + 112, rs->stats1.p, 16, hipMemcpyDeviceToHost, s));
-  if (inlier_out && m) SSHIP_HIP_CHECK(hipMemcpyAsync(hout + 128, rs->inlier1.p, m, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(a.download(a.out, st.out_bytes, s));
   SSHIP_HIP_CHECK(hipStreamSynchronize(s));
-  memcpy(pose_out, hout, 96);
-  memcpy(cost_out, hout + 96, 8);
-  memcpy(stats_out, hout + 112, 16);
-  if (inlier_out && m) memcpy(inlier_out, hout + 128, m);
+  obs_unpack(a.host<char>(a.out), st, n_obs, pose_out, stats_out, cost_out, inlier_out);
   return SSHIP_OK;
 }
 // Measurement hook (include/sship.h): the last solve call's two launches re-run `iters` times on the handle's stream.
-extern "C" int sship_ransac_bench(sship_ransac* rs, int iters, float* avg_ms) {
-  if (!rs || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "ransac_bench: bad arguments");
-  if (rs->last.pairs <= 0) return fail(SSHIP_ERR_INVALID, "ransac_bench: run a solve on this handle first");
-  bind_thread();
-  hipStream_t s = rs->stream;
-  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
-  const sship_ransac::Last& l = rs->last;
-  const RansacK k = ransac_constants(rs);
-  auto run = [&]() -> hipError_t {
-    launch_ransac_solve(l.points, l.meas, l.valid, rs->max_obs, l.pairs, k, rs->workspace.p, l.pose, l.stats, l.cost, l.inlier, s);
-    return hipGetLastError();
-  };
-  return bench_loop(s, iters, run, avg_ms);
-}
+extern "C" int sship_ransac_bench(sship_ransac* rs, int iters, float* avg_ms) { return bench_last(rs, iters, avg_ms, "ransac_bench", "solve", ransac_run); }
 
 // ====================================================================================================
 // Window smoother: sliding-window stereo bundle adjustment (include/sship.h "Window smoother"; csrc/ba_kernels.hip)
@@ -3257,9 +3168,8 @@ struct sship_ba {
   sship_ba_params prm{1.0, 9.0, 1e-5, 1e5, 1e-3, 1e-3, 20};
   hipStream_t stream = nullptr;
   DevBuf workspace;
-  DevBuf meas1, track1, nkf1, pose01, pose1, stats1, cost1, lm1;   // sship_ba_solve_host: one staged window and its results
-  PinBuf h_in, h_out;
-  struct Last { const float* meas = nullptr; const int32_t* track = nullptr; const int32_t* n_kf = nullptr; const double* pose0 = nullptr; int windows = 0;
+  StageArena one;   // sship_ba_solve_host: one staged window and its results (ba_stage)
+  struct Last { const float* meas = nullptr; const int32_t* track = nullptr; const int32_t* n_kf = nullptr; const double* pose0 = nullptr; int items = 0;
                 double* pose = nullptr; int32_t* stats = nullptr; double* cost = nullptr; float* landmarks = nullptr; } last;
 };
 static BaK ba_constants(const sship_ba* ba) {
@@ -3281,18 +3191,9 @@ extern "C" int sship_ba_create(int max_keyframes, int max_obs, int max_landmarks
   if (int rc = require_device()) return rc;
   std::unique_ptr<sship_ba, void (*)(sship_ba*)> ba(new sship_ba(), sship_ba_destroy);
   ba->K = max_keyframes; ba->N = max_obs; ba->L = max_landmarks; ba->max_windows = max_windows;
-  const size_t kn = (size_t)max_keyframes * max_obs, l3 = (size_t)max_landmarks * 12, k12 = (size_t)max_keyframes * 96;
+  const BaStage st = ba_stage(max_keyframes, max_obs, max_landmarks);
   SSHIP_HIP_CHECK(ba->workspace.ensure(ba_workspace_bytes(max_keyframes, max_obs, max_landmarks) * (size_t)std::min(max_windows, kBaResident)));
-  SSHIP_HIP_CHECK(ba->meas1.ensure(kn * 12));
-  SSHIP_HIP_CHECK(ba->track1.ensure(kn * 4));
-  SSHIP_HIP_CHECK(ba->nkf1.ensure(16));
-  SSHIP_HIP_CHECK(ba->pose01.ensure(k12));
-  SSHIP_HIP_CHECK(ba->pose1.ensure(k12));
-  SSHIP_HIP_CHECK(ba->stats1.ensure(16));
-  SSHIP_HIP_CHECK(ba->cost1.ensure(16));
-  SSHIP_HIP_CHECK(ba->lm1.ensure(l3));
-  SSHIP_HIP_CHECK(ba->h_in.ensure(k12 + kn * 16 + 16));
-  SSHIP_HIP_CHECK(ba->h_out.ensure(k12 + 32 + l3));
+  SSHIP_HIP_CHECK(ba->one.create(st.in_bytes, st.out_bytes));
   SSHIP_HIP_CHECK(ba_solve_prepare());
   SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&ba->stream, hipStreamDefault));
   *out = ba.release();
@@ -3312,10 +3213,9 @@ extern "C" int sship_ba_set_params(sship_ba* ba, const sship_ba_params* p) {
     if (std::isnan(v)) return fail(SSHIP_ERR_INVALID, "ba_set_params: a parameter is NaN");
   if (!(p->sigma_px > 0.0) || !(p->huber_k2 > 0.0) || std::isinf(p->sigma_px) || std::isinf(p->huber_k2))
     return fail(SSHIP_ERR_INVALID, "ba_set_params: sigma_px and huber_k2 must be finite and > 0");
-  if (!(p->lambda0 > 0.0) || p->lambda_max < p->lambda0 || std::isinf(p->lambda_max))
-    return fail(SSHIP_ERR_INVALID, "ba_set_params: lambda0 must be > 0 and lambda_max finite and >= lambda0");
+  if (int rc = check_lambda("ba_set_params", p->lambda0, p->lambda_max)) return rc;
   if (p->abs_tol < 0.0 || p->rel_tol < 0.0) return fail(SSHIP_ERR_INVALID, "ba_set_params: a tolerance is negative");
-  if (p->max_iterations < 1) return fail(SSHIP_ERR_INVALID, "ba_set_params: max_iterations must be >= 1");
+  if (int rc = check_max_iterations("ba_set_params", p->max_iterations)) return rc;
   ba->prm = *p;
   return SSHIP_OK;
 }
@@ -3324,12 +3224,14 @@ extern "C" int sship_ba_get_params(const sship_ba* ba, sship_ba_params* p) {
   *p = ba->prm;
   return SSHIP_OK;
 }
+static hipError_t ba_run(const sship_ba* ba, const sship_ba::Last& l, hipStream_t s) {
+  launch_ba_solve(l.meas, l.track, l.n_kf, l.pose0, ba->K, ba->N, ba->L, l.items, ba_constants(ba), ba->workspace.p, l.pose, l.stats, l.cost, l.landmarks, s);
+  return hipGetLastError();
+}
 static int ba_launch(sship_ba* ba, const float* meas, const int32_t* track, const int32_t* n_kf, const double* pose0, int windows, double* pose,
                      int32_t* stats, double* cost, float* landmarks, hipStream_t s) {
-  sship_ba::Last& l = ba->last;
-  l.meas = meas; l.track = track; l.n_kf = n_kf; l.pose0 = pose0; l.windows = windows; l.pose = pose; l.stats = stats; l.cost = cost; l.landmarks = landmarks;
-  launch_ba_solve(meas, track, n_kf, pose0, ba->K, ba->N, ba->L, windows, ba_constants(ba), ba->workspace.p, pose, stats, cost, landmarks, s);
-  SSHIP_HIP_CHECK(hipGetLastError());
+  ba->last = {meas, track, n_kf, pose0, windows, pose, stats, cost, landmarks};
+  SSHIP_HIP_CHECK(ba_run(ba, ba->last, s));
   return SSHIP_OK;
 }
 extern "C" int sship_ba_solve_batch_device(sship_ba* ba, const float* meas, const int32_t* track, const int32_t* n_kf, const double* pose0,
@@ -3351,30 +3253,17 @@ extern "C" int sship_ba_solve_host(sship_ba* ba, const float* meas, const int32_
   if (!ba->cam.set) return fail(SSHIP_ERR_INVALID, "ba_solve_host: set the camera first (sship_ba_set_camera)");
   bind_thread();
   hipStream_t s = ba->stream;
-  const size_t kn = (size_t)ba->K * ba->N, k12 = (size_t)ba->K * 96, l3 = (size_t)ba->L * 12;
-  char* hin = static_cast<char*>(ba->h_in.p);   // pose0 | meas | track | n_kf
-  memcpy(hin, pose0, k12);
-  memcpy(hin + k12, meas, kn * 12);
-  memcpy(hin + k12 + kn * 12, track, kn * 4);
-  const int32_t nk = n_kf;
-  memcpy(hin + k12 + kn * 16, &nk, 4);
-  SSHIP_HIP_CHECK(hipMemcpyAsync(ba->pose01.p, hin, k12, hipMemcpyHostToDevice, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(ba->meas1.p, hin + k12, kn * 12, hipMemcpyHostToDevice, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(ba->track1.p, hin + k12 + kn * 12, kn * 4, hipMemcpyHostToDevice, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(ba->nkf1.p, hin + k12 + kn * 16, 4, hipMemcpyHostToDevice, s));
-  if (int rc = ba_launch(ba, ba->meas1.as<float>(), ba->track1.as<int32_t>(), ba->nkf1.as<int32_t>(), ba->pose01.as<double>(), 1,
-                         ba->pose1.as<double>(), ba->stats1.as<int32_t>(), ba->cost1.as<double>(), ba->lm1.as<float>(), s))
+  const StageArena& a = ba->one;
+  const BaStage st = ba_stage(ba->K, ba->N, ba->L);
+  ba_pack(a.host<char>(0), st, meas, track, n_kf, pose0);
+  SSHIP_HIP_CHECK(a.upload(0, st.in_bytes, s));
+  if (int rc = ba_launch(ba, a.dev<float>(st.meas), a.dev<int32_t>(st.track), a.dev<int32_t>(st.n_kf), a.dev<double>(st.pose0), 1,
+                         a.dev<double>(a.out + st.pose), a.dev<int32_t>(a.out + st.stats), a.dev<double>(a.out + st.cost),
+                         a.dev<float>(a.out + st.landmarks), s))
     return rc;
-  char* hout = static_cast<char*>(ba->h_out.p);   // pose | cost (16) | stats (16) | landmarks
-  SSHIP_HIP_CHECK(hipMemcpyAsync(hout, ba->pose1.p, k12, hipMemcpyDeviceToHost, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(hout + k12, ba->cost1.p, 16, hipMemcpyDeviceToHost, s));
-  SSHIP_HIP_CHECK(hipMemcpyAsync(hout + k12 + 16, ba->stats1.p, 16, hipMemcpyDeviceToHost, s));
-  if (landmarks_out) SSHIP_HIP_CHECK(hipMemcpyAsync(hout + k12 + 32, ba->lm1.p, l3, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(a.download(a.out, landmarks_out ? st.out_bytes : st.landmarks, s));   // the landmarks are the last slot: not fetched unless asked for
   SSHIP_HIP_CHECK(hipStreamSynchronize(s));
-  memcpy(pose_out, hout, k12);
-  memcpy(cost_out, hout + k12, 16);
-  memcpy(stats_out, hout + k12 + 16, 16);
-  if (landmarks_out) memcpy(landmarks_out, hout + k12 + 32, l3);
+  ba_unpack(a.host<char>(a.out), st, pose_out, stats_out, cost_out, landmarks_out);
   return SSHIP_OK;
 }
 extern "C" int sship_ba_tracks_from_matches_batch_device(const sship_ba* ba, const uint8_t* has_depth, const int32_t* matches, const int32_t* n,
@@ -3392,20 +3281,7 @@ extern "C" int sship_ba_tracks_from_matches_batch_device(const sship_ba* ba, con
   return SSHIP_OK;
 }
 // Measurement hook (include/sship.h): the last solve call's launch re-run `iters` times on the handle's stream.
-extern "C" int sship_ba_bench(sship_ba* ba, int iters, float* avg_ms) {
-  if (!ba || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "ba_bench: bad arguments");
-  if (ba->last.windows <= 0) return fail(SSHIP_ERR_INVALID, "ba_bench: run a solve on this handle first");
-  bind_thread();
-  hipStream_t s = ba->stream;
-  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
-  const sship_ba::Last& l = ba->last;
-  const BaK k = ba_constants(ba);
-  auto run = [&]() -> hipError_t {
-    launch_ba_solve(l.meas, l.track, l.n_kf, l.pose0, ba->K, ba->N, ba->L, l.windows, k, ba->workspace.p, l.pose, l.stats, l.cost, l.landmarks, s);
-    return hipGetLastError();
-  };
-  return bench_loop(s, iters, run, avg_ms);
-}
+extern "C" int sship_ba_bench(sship_ba* ba, int iters, float* avg_ms) { return bench_last(ba, iters, avg_ms, "ba_bench", "solve", ba_run); }
 
 // ====================================================================================================
 // Pose graph: batched pose-graph optimiser (include/sship.h "Pose graph"; csrc/pg_kernels.hip)
@@ -3416,11 +3292,10 @@ struct sship_pg {
   sship_pg_params prm{0.02, 0.05, 1e-5, 1e5, 1e-5, 1e-5, 1e6, 100};
   hipStream_t stream = nullptr;
   DevBuf workspace;
-  DevBuf in1, out1;   // sship_pg_solve_host: one staged graph and its results
-  PinBuf h_in, h_out;
+  StageArena one;   // sship_pg_solve_host: one staged graph and its results (pg_stage)
   struct Last { const int32_t* n_nodes = nullptr; const double* pose0 = nullptr; const double* odom_z = nullptr; const double* odom_sigma = nullptr;
                 const int32_t* loop_ij = nullptr; const double* loop_z = nullptr; const double* loop_sigma = nullptr; const double* loop_k2 = nullptr;
-                const uint8_t* loop_enable = nullptr; int graphs = 0;
+                const uint8_t* loop_enable = nullptr; int items = 0;
                 double* pose = nullptr; int32_t* stats = nullptr; double* cost = nullptr; double* chi2 = nullptr; } last;
 };
 static PgK pg_constants(const sship_pg* pg) {
@@ -3429,29 +3304,6 @@ static PgK pg_constants(const sship_pg* pg) {
   k.lambda0 = pg->prm.lambda0; k.lambda_max = pg->prm.lambda_max; k.abs_tol = pg->prm.abs_tol; k.rel_tol = pg->prm.rel_tol;
   k.max_translation = pg->prm.max_translation; k.max_iterations = pg->prm.max_iterations;
   return k;
-}
-// the staging of one graph, byte offsets: inputs pose0 | odom_z | odom_sigma | loop_z | loop_sigma | loop_k2 | loop_ij | n_nodes | enable
-struct PgStage { size_t pose0, oz, osg, lz, lsg, lk2, lij, nn, len, in_bytes, pose, cost, chi2, stats, out_bytes; };
-static PgStage pg_stage(int N, int L) {
-  PgStage s;
-  size_t o = 0;
-  s.pose0 = o; o += (size_t)N * 96;
-  s.oz = o; o += (size_t)(N - 1) * 96;
-  s.osg = o; o += (size_t)(N - 1) * 48;
-  s.lz = o; o += (size_t)L * 96;
-  s.lsg = o; o += (size_t)L * 48;
-  s.lk2 = o; o += (size_t)L * 8;
-  s.lij = o; o += (size_t)L * 8;
-  s.nn = o; o += 16;
-  s.len = o; o += ((size_t)L + 15) / 16 * 16;
-  s.in_bytes = o;
-  o = 0;
-  s.pose = o; o += (size_t)N * 96;
-  s.cost = o; o += 16;
-  s.chi2 = o; o += (size_t)L * 8;
-  s.stats = o; o += 16;
-  s.out_bytes = o;
-  return s;
 }
 extern "C" int sship_pg_create(int max_nodes, int max_loops, int max_graphs, sship_pg** out) {
   if (!out) return fail(SSHIP_ERR_INVALID, "pg_create: null argument");
@@ -3465,10 +3317,7 @@ extern "C" int sship_pg_create(int max_nodes, int max_loops, int max_graphs, ssh
   pg->N = max_nodes; pg->L = max_loops; pg->max_graphs = max_graphs;
   const PgStage st = pg_stage(max_nodes, max_loops);
   SSHIP_HIP_CHECK(pg->workspace.ensure(pg_workspace_bytes(max_nodes, max_loops) * (size_t)std::min(max_graphs, kPgResident)));
-  SSHIP_HIP_CHECK(pg->in1.ensure(st.in_bytes));
-  SSHIP_HIP_CHECK(pg->out1.ensure(st.out_bytes));
-  SSHIP_HIP_CHECK(pg->h_in.ensure(st.in_bytes));
-  SSHIP_HIP_CHECK(pg->h_out.ensure(st.out_bytes));
+  SSHIP_HIP_CHECK(pg->one.create(st.in_bytes, st.out_bytes));
   SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&pg->stream, hipStreamDefault));
   *out = pg.release();
   return SSHIP_OK;
@@ -3485,12 +3334,11 @@ extern "C" int sship_pg_set_params(sship_pg* pg, const sship_pg_params* p) {
     if (std::isnan(v)) return fail(SSHIP_ERR_INVALID, "pg_set_params: a parameter is NaN");
   if (!(p->odom_sigma_rot > 0.0) || !(p->odom_sigma_trans > 0.0) || std::isinf(p->odom_sigma_rot) || std::isinf(p->odom_sigma_trans))
     return fail(SSHIP_ERR_INVALID, "pg_set_params: odom_sigma_rot and odom_sigma_trans must be finite and > 0");
-  if (!(p->lambda0 > 0.0) || p->lambda_max < p->lambda0 || std::isinf(p->lambda_max))
-    return fail(SSHIP_ERR_INVALID, "pg_set_params: lambda0 must be > 0 and lambda_max finite and >= lambda0");
+  if (int rc = check_lambda("pg_set_params", p->lambda0, p->lambda_max)) return rc;
   if (p->abs_tol < 0.0 || p->rel_tol < 0.0) return fail(SSHIP_ERR_INVALID, "pg_set_params: a tolerance is negative");
   if (!(p->max_translation > 0.0) || std::isinf(p->max_translation))
     return fail(SSHIP_ERR_INVALID, "pg_set_params: max_translation must be finite and > 0");
-  if (p->max_iterations < 1) return fail(SSHIP_ERR_INVALID, "pg_set_params: max_iterations must be >= 1");
+  if (int rc = check_max_iterations("pg_set_params", p->max_iterations)) return rc;
   pg->prm = *p;
   return SSHIP_OK;
 }
@@ -3499,16 +3347,16 @@ extern "C" int sship_pg_get_params(const sship_pg* pg, sship_pg_params* p) {
   *p = pg->prm;
   return SSHIP_OK;
 }
+static hipError_t pg_run(const sship_pg* pg, const sship_pg::Last& l, hipStream_t s) {
+  launch_pg_solve(l.n_nodes, l.pose0, l.odom_z, l.odom_sigma, l.loop_ij, l.loop_z, l.loop_sigma, l.loop_k2, l.loop_enable, pg->N, pg->L, l.items,
+                  pg_constants(pg), pg->workspace.p, l.pose, l.stats, l.cost, l.chi2, s);
+  return hipGetLastError();
+}
 static int pg_launch(sship_pg* pg, const int32_t* n_nodes, const double* pose0, const double* odom_z, const double* odom_sigma,
                      const int32_t* loop_ij, const double* loop_z, const double* loop_sigma, const double* loop_k2, const uint8_t* loop_enable,
                      int graphs, double* pose, int32_t* stats, double* cost, double* chi2, hipStream_t s) {
-  sship_pg::Last& l = pg->last;
-  l.n_nodes = n_nodes; l.pose0 = pose0; l.odom_z = odom_z; l.odom_sigma = odom_sigma; l.loop_ij = loop_ij; l.loop_z = loop_z;
-  l.loop_sigma = loop_sigma; l.loop_k2 = loop_k2; l.loop_enable = loop_enable; l.graphs = graphs; l.pose = pose; l.stats = stats; l.cost = cost;
-  l.chi2 = chi2;
-  launch_pg_solve(n_nodes, pose0, odom_z, odom_sigma, loop_ij, loop_z, loop_sigma, loop_k2, loop_enable, pg->N, pg->L, graphs, pg_constants(pg),
-                  pg->workspace.p, pose, stats, cost, chi2, s);
-  SSHIP_HIP_CHECK(hipGetLastError());
+  pg->last = {n_nodes, pose0, odom_z, odom_sigma, loop_ij, loop_z, loop_sigma, loop_k2, loop_enable, graphs, pose, stats, cost, chi2};
+  SSHIP_HIP_CHECK(pg_run(pg, pg->last, s));
   return SSHIP_OK;
 }
 extern "C" int sship_pg_solve_batch_device(sship_pg* pg, const int32_t* n_nodes, const double* pose0, const double* odom_z,
@@ -3540,41 +3388,19 @@ extern "C" int sship_pg_solve_host(sship_pg* pg, int n_nodes, const double* pose
   if (n_loops > 0 && (!loop_ij || !loop_z || !loop_sigma || !loop_k2)) return fail(SSHIP_ERR_INVALID, "pg_solve_host: null argument");
   bind_thread();
   hipStream_t s = pg->stream;
-  const int N = pg->N, L = pg->L;
-  const PgStage st = pg_stage(N, L);
-  char* hin = static_cast<char*>(pg->h_in.p);
-  memset(hin, 0, st.in_bytes);   // rows past n_nodes / n_loops: zeros, and enable = 0
-  if (n_nodes > 0) memcpy(hin + st.pose0, pose0, (size_t)n_nodes * 96);
-  if (n_nodes > 1) {
-    memcpy(hin + st.oz, odom_z, (size_t)(n_nodes - 1) * 96);
-    if (odom_sigma) memcpy(hin + st.osg, odom_sigma, (size_t)(n_nodes - 1) * 48);
-  }
-  if (n_loops > 0) {
-    memcpy(hin + st.lz, loop_z, (size_t)n_loops * 96);
-    memcpy(hin + st.lsg, loop_sigma, (size_t)n_loops * 48);
-    memcpy(hin + st.lk2, loop_k2, (size_t)n_loops * 8);
-    memcpy(hin + st.lij, loop_ij, (size_t)n_loops * 8);
-    memset(hin + st.len, 1, (size_t)n_loops);
-  }
-  const int32_t nn = n_nodes;
-  memcpy(hin + st.nn, &nn, 4);
-  SSHIP_HIP_CHECK(hipMemcpyAsync(pg->in1.p, hin, st.in_bytes, hipMemcpyHostToDevice, s));
-  char* din = static_cast<char*>(pg->in1.p);
-  char* dout = static_cast<char*>(pg->out1.p);
-  auto dd = [&](size_t o) { return reinterpret_cast<const double*>(din + o); };
-  if (int rc = pg_launch(pg, reinterpret_cast<const int32_t*>(din + st.nn), dd(st.pose0), dd(st.oz), odom_sigma ? dd(st.osg) : nullptr,
-                         L ? reinterpret_cast<const int32_t*>(din + st.lij) : nullptr, L ? dd(st.lz) : nullptr, L ? dd(st.lsg) : nullptr,
-                         L ? dd(st.lk2) : nullptr, L ? reinterpret_cast<const uint8_t*>(din + st.len) : nullptr, 1,
-                         reinterpret_cast<double*>(dout + st.pose), reinterpret_cast<int32_t*>(dout + st.stats),
-                         reinterpret_cast<double*>(dout + st.cost), reinterpret_cast<double*>(dout + st.chi2), s))
+  const StageArena& a = pg->one;
+  const PgStage st = pg_stage(pg->N, pg->L);
+  const bool loops = pg->L > 0;   // a handle without loops passes null loop arrays
+  pg_pack(a.host<char>(0), st, n_nodes, pose0, odom_z, odom_sigma, n_loops, loop_ij, loop_z, loop_sigma, loop_k2);
+  SSHIP_HIP_CHECK(a.upload(0, st.in_bytes, s));
+  if (int rc = pg_launch(pg, a.dev<int32_t>(st.nn), a.dev<double>(st.pose0), a.dev<double>(st.oz), odom_sigma ? a.dev<double>(st.osg) : nullptr,
+                         loops ? a.dev<int32_t>(st.lij) : nullptr, loops ? a.dev<double>(st.lz) : nullptr, loops ? a.dev<double>(st.lsg) : nullptr,
+                         loops ? a.dev<double>(st.lk2) : nullptr, loops ? a.dev<uint8_t>(st.len) : nullptr, 1, a.dev<double>(a.out + st.pose),
+                         a.dev<int32_t>(a.out + st.stats), a.dev<double>(a.out + st.cost), a.dev<double>(a.out + st.chi2), s))
     return rc;
-  char* hout = static_cast<char*>(pg->h_out.p);
-  SSHIP_HIP_CHECK(hipMemcpyAsync(hout, dout, st.out_bytes, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(a.download(a.out, st.out_bytes, s));
   SSHIP_HIP_CHECK(hipStreamSynchronize(s));
-  if (n_nodes > 0) memcpy(pose_out, hout + st.pose, (size_t)n_nodes * 96);
-  memcpy(cost_out, hout + st.cost, 16);
-  memcpy(stats_out, hout + st.stats, 16);
-  if (loop_chi2_out && n_loops > 0) memcpy(loop_chi2_out, hout + st.chi2, (size_t)n_loops * 8);
+  pg_unpack(a.host<char>(a.out), st, n_nodes, n_loops, pose_out, stats_out, cost_out, loop_chi2_out);
   return SSHIP_OK;
 }
 extern "C" int sship_pg_odometry_from_poses_batch_device(const sship_pg* pg, const double* pose, int graphs, double* odom_z, void* stream) {
@@ -3606,21 +3432,7 @@ extern "C" int sship_pg_loops_from_pose_batch_device(const sship_pg* pg, const i
   return SSHIP_OK;
 }
 // Measurement hook (include/sship.h): the last solve call's launch re-run `iters` times on the handle's stream.
-extern "C" int sship_pg_bench(sship_pg* pg, int iters, float* avg_ms) {
-  if (!pg || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "pg_bench: bad arguments");
-  if (pg->last.graphs <= 0) return fail(SSHIP_ERR_INVALID, "pg_bench: run a solve on this handle first");
-  bind_thread();
-  hipStream_t s = pg->stream;
-  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the last call may have run on the caller's stream
-  const sship_pg::Last& l = pg->last;
-  const PgK k = pg_constants(pg);
-  auto run = [&]() -> hipError_t {
-    launch_pg_solve(l.n_nodes, l.pose0, l.odom_z, l.odom_sigma, l.loop_ij, l.loop_z, l.loop_sigma, l.loop_k2, l.loop_enable, pg->N, pg->L, l.graphs,
-                    k, pg->workspace.p, l.pose, l.stats, l.cost, l.chi2, s);
-    return hipGetLastError();
-  };
-  return bench_loop(s, iters, run, avg_ms);
-}
+extern "C" int sship_pg_bench(sship_pg* pg, int iters, float* avg_ms) { return bench_last(pg, iters, avg_ms, "pg_bench", "solve", pg_run); }
 
 // ====================================================================================================
 // rectification remap (sship_rect_*) and RGB-D association
@@ -3826,17 +3638,18 @@ extern "C" int sship_rgbd_associate_host(const float* keypoints, int kp_stride, 
   for (int i = 0; i < n; ++i) { kp[3 * i] = keypoints[(size_t)i * kp_stride]; kp[3 * i + 1] = keypoints[(size_t)i * kp_stride + 1]; }
   const size_t kb = kp.size() * sizeof(float), db = (size_t)h * depth_stride;
   if (int rc = require_device()) return rc;
-  DevBuf d_kp, d_n, d_depth, d_und, d_st, d_hd;
-  SSHIP_HIP_CHECK(d_kp.ensure(kb)); SSHIP_HIP_CHECK(d_n.ensure(16)); SSHIP_HIP_CHECK(d_depth.ensure(db));
-  SSHIP_HIP_CHECK(d_und.ensure(kb)); SSHIP_HIP_CHECK(d_st.ensure(kb)); SSHIP_HIP_CHECK(d_hd.ensure((size_t)n));
-  SSHIP_HIP_CHECK(hipMemcpy(d_kp.p, kp.data(), kb, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(d_n.p, &n, sizeof(int), hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(d_depth.p, depth, db, hipMemcpyHostToDevice));
-  if (int rc = sship_rgbd_associate_batch_device(d_kp.as<float>(), d_n.as<int>(), 1, n, d_depth.p, depth_type, h, w, depth_stride, p, d_und.as<float>(),
-                                                 d_st.as<float>(), d_hd.as<uint8_t>(), nullptr)) return rc;
-  SSHIP_HIP_CHECK(hipMemcpy(und.data(), d_und.p, kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launch
-  SSHIP_HIP_CHECK(hipMemcpy(stereo, d_st.p, kb, hipMemcpyDeviceToHost));
-  SSHIP_HIP_CHECK(hipMemcpy(has_depth, d_hd.p, (size_t)n, hipMemcpyDeviceToHost));
+  StageLayout lay;   // one device block for the call; the copies stay blocking and straight from / to the caller's memory
+  const size_t o_kp = lay.add(kb), o_n = lay.add(sizeof(int)), o_depth = lay.add(db), o_und = lay.add(kb), o_st = lay.add(kb), o_hd = lay.add((size_t)n);
+  StageArena a;
+  SSHIP_HIP_CHECK(a.create(lay.end, 0, false));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<float>(o_kp), kp.data(), kb, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<int>(o_n), &n, sizeof(int), hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<char>(o_depth), depth, db, hipMemcpyHostToDevice));
+  if (int rc = sship_rgbd_associate_batch_device(a.dev<float>(o_kp), a.dev<int>(o_n), 1, n, a.dev<char>(o_depth), depth_type, h, w, depth_stride, p,
+                                                 a.dev<float>(o_und), a.dev<float>(o_st), a.dev<uint8_t>(o_hd), nullptr)) return rc;
+  SSHIP_HIP_CHECK(hipMemcpy(und.data(), a.dev<float>(o_und), kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launch
+  SSHIP_HIP_CHECK(hipMemcpy(stereo, a.dev<float>(o_st), kb, hipMemcpyDeviceToHost));
+  SSHIP_HIP_CHECK(hipMemcpy(has_depth, a.dev<uint8_t>(o_hd), (size_t)n, hipMemcpyDeviceToHost));
   for (int i = 0; i < n; ++i) { kp_undist[2 * i] = und[3 * i]; kp_undist[2 * i + 1] = und[3 * i + 1]; }
   return SSHIP_OK;
 }
@@ -3896,20 +3709,22 @@ extern "C" int sship_stereo_refine_host(const uint8_t* left, int left_stride, co
   bind_thread();
   if (int rc = require_device()) return rc;
   const size_t img = (size_t)h * w, kb = (size_t)n * 3 * sizeof(float);
-  DevBuf d_img, d_n, d_st, d_hd, d_status, d_cost;
-  SSHIP_HIP_CHECK(d_img.ensure(2 * img)); SSHIP_HIP_CHECK(d_n.ensure(16)); SSHIP_HIP_CHECK(d_st.ensure(kb)); SSHIP_HIP_CHECK(d_hd.ensure((size_t)n));
-  SSHIP_HIP_CHECK(d_status.ensure((size_t)n)); SSHIP_HIP_CHECK(d_cost.ensure((size_t)n * sizeof(int64_t)));
-  SSHIP_HIP_CHECK(hipMemcpy2D(d_img.p, (size_t)w, left, (size_t)left_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy2D(d_img.as<uint8_t>() + img, (size_t)w, right, (size_t)right_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(d_n.p, &n, sizeof(int), hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(d_st.p, stereo, kb, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(d_hd.p, has_depth, (size_t)n, hipMemcpyHostToDevice));
-  if (int rc = sship_stereo_refine_batch_device(d_img.as<uint8_t>(), 1, h, w, w, d_st.as<float>(), d_hd.as<uint8_t>(), d_n.as<int>(), 1, n, p,
-                                                d_st.as<float>(), d_hd.as<uint8_t>(), d_status.as<uint8_t>(), d_cost.as<int64_t>(), nullptr)) return rc;
-  SSHIP_HIP_CHECK(hipMemcpy(stereo_out, d_st.p, kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launch
-  SSHIP_HIP_CHECK(hipMemcpy(has_depth_out, d_hd.p, (size_t)n, hipMemcpyDeviceToHost));
-  if (status) { SSHIP_HIP_CHECK(hipMemcpy(status, d_status.p, (size_t)n, hipMemcpyDeviceToHost)); }
-  if (cost) { SSHIP_HIP_CHECK(hipMemcpy(cost, d_cost.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost)); }
+  StageLayout lay;   // one device block for the call: the pair packed to stride w, then the per-keypoint arrays (refined in place)
+  const size_t o_left = lay.add(2 * img), o_right = o_left + img, o_n = lay.add(sizeof(int)), o_st = lay.add(kb), o_hd = lay.add((size_t)n),
+               o_status = lay.add((size_t)n), o_cost = lay.add((size_t)n * sizeof(int64_t));
+  StageArena a;
+  SSHIP_HIP_CHECK(a.create(lay.end, 0, false));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_left), (size_t)w, left, (size_t)left_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_right), (size_t)w, right, (size_t)right_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<int>(o_n), &n, sizeof(int), hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<float>(o_st), stereo, kb, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<uint8_t>(o_hd), has_depth, (size_t)n, hipMemcpyHostToDevice));
+  if (int rc = sship_stereo_refine_batch_device(a.dev<uint8_t>(o_left), 1, h, w, w, a.dev<float>(o_st), a.dev<uint8_t>(o_hd), a.dev<int>(o_n), 1, n, p,
+                                                a.dev<float>(o_st), a.dev<uint8_t>(o_hd), a.dev<uint8_t>(o_status), a.dev<int64_t>(o_cost), nullptr)) return rc;
+  SSHIP_HIP_CHECK(hipMemcpy(stereo_out, a.dev<float>(o_st), kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launch
+  SSHIP_HIP_CHECK(hipMemcpy(has_depth_out, a.dev<uint8_t>(o_hd), (size_t)n, hipMemcpyDeviceToHost));
+  if (status) { SSHIP_HIP_CHECK(hipMemcpy(status, a.dev<uint8_t>(o_status), (size_t)n, hipMemcpyDeviceToHost)); }
+  if (cost) { SSHIP_HIP_CHECK(hipMemcpy(cost, a.dev<int64_t>(o_cost), (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost)); }
   return SSHIP_OK;
 }
 
@@ -3972,19 +3787,21 @@ extern "C" int sship_stereo_search_host(const uint8_t* left, int left_stride, co
   std::vector<float> kp((size_t)n * 3, 0.f);
   for (int i = 0; i < n; ++i) { kp[3 * i] = keypoints[(size_t)i * kp_stride]; kp[3 * i + 1] = keypoints[(size_t)i * kp_stride + 1]; }
   const size_t img = (size_t)h * w, kb = (size_t)n * 3 * sizeof(float);
-  DevBuf d_img, d_n, d_kp, d_st, d_hd, d_status, d_cost;
-  SSHIP_HIP_CHECK(d_img.ensure(2 * img)); SSHIP_HIP_CHECK(d_n.ensure(16)); SSHIP_HIP_CHECK(d_kp.ensure(kb)); SSHIP_HIP_CHECK(d_st.ensure(kb));
-  SSHIP_HIP_CHECK(d_hd.ensure((size_t)n)); SSHIP_HIP_CHECK(d_status.ensure((size_t)n)); SSHIP_HIP_CHECK(d_cost.ensure((size_t)n * sizeof(int64_t)));
-  SSHIP_HIP_CHECK(hipMemcpy2D(d_img.p, (size_t)w, left, (size_t)left_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy2D(d_img.as<uint8_t>() + img, (size_t)w, right, (size_t)right_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(d_n.p, &n, sizeof(int), hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(d_kp.p, kp.data(), kb, hipMemcpyHostToDevice));
-  if (int rc = sship_stereo_search_batch_device(d_img.as<uint8_t>(), 1, h, w, w, d_kp.as<float>(), d_n.as<int>(), 1, n, p, d_st.as<float>(),
-                                                d_hd.as<uint8_t>(), d_status.as<uint8_t>(), d_cost.as<int64_t>(), nullptr)) return rc;
-  SSHIP_HIP_CHECK(hipMemcpy(stereo_out, d_st.p, kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launch
-  SSHIP_HIP_CHECK(hipMemcpy(has_depth_out, d_hd.p, (size_t)n, hipMemcpyDeviceToHost));
-  if (status) { SSHIP_HIP_CHECK(hipMemcpy(status, d_status.p, (size_t)n, hipMemcpyDeviceToHost)); }
-  if (cost) { SSHIP_HIP_CHECK(hipMemcpy(cost, d_cost.p, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost)); }
+  StageLayout lay;   // one device block for the call: the pair packed to stride w, then the per-keypoint arrays
+  const size_t o_left = lay.add(2 * img), o_right = o_left + img, o_n = lay.add(sizeof(int)), o_kp = lay.add(kb), o_st = lay.add(kb),
+               o_hd = lay.add((size_t)n), o_status = lay.add((size_t)n), o_cost = lay.add((size_t)n * sizeof(int64_t));
+  StageArena a;
+  SSHIP_HIP_CHECK(a.create(lay.end, 0, false));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_left), (size_t)w, left, (size_t)left_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_right), (size_t)w, right, (size_t)right_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<int>(o_n), &n, sizeof(int), hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<float>(o_kp), kp.data(), kb, hipMemcpyHostToDevice));
+  if (int rc = sship_stereo_search_batch_device(a.dev<uint8_t>(o_left), 1, h, w, w, a.dev<float>(o_kp), a.dev<int>(o_n), 1, n, p, a.dev<float>(o_st),
+                                                a.dev<uint8_t>(o_hd), a.dev<uint8_t>(o_status), a.dev<int64_t>(o_cost), nullptr)) return rc;
+  SSHIP_HIP_CHECK(hipMemcpy(stereo_out, a.dev<float>(o_st), kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launch
+  SSHIP_HIP_CHECK(hipMemcpy(has_depth_out, a.dev<uint8_t>(o_hd), (size_t)n, hipMemcpyDeviceToHost));
+  if (status) { SSHIP_HIP_CHECK(hipMemcpy(status, a.dev<uint8_t>(o_status), (size_t)n, hipMemcpyDeviceToHost)); }
+  if (cost) { SSHIP_HIP_CHECK(hipMemcpy(cost, a.dev<int64_t>(o_cost), (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost)); }
   return SSHIP_OK;
 }
 
