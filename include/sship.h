@@ -514,6 +514,43 @@ int sship_ep_bench(sship_ep* ep, const uint8_t* img_dev, int h, int w, int strid
  *   28        the descriptor, fp32 [512] */
 int sship_ep_debug_capture(sship_ep* ep, int on);
 int sship_ep_debug_activation(sship_ep* ep, int stage, void* out_host, unsigned long long bytes);
+/* EigenPlaces: batches.  THE RULE: descriptor b of a batch call has exactly the bits sship_ep_infer_u8_device gives for image b alone - for
+ * every batch size, at every position in the batch, on any stream, from the host or the device entry - and so has every captured stage.
+ * The batch path keeps every rounding point of the single-image path, its fp32 summation orders (the split-K grouping of the deep layers, the
+ * tail's partial sums per workgroup and per wave) and the non-contracted preprocessing; what changes with the batch is only how many images a
+ * launch covers and whether a deep layer's group sums meet in a workspace (batched split-K) or in registers (the grouped kernel), chosen
+ * from (layer shape, batch) alone - never from the device.
+ * sship_ep_reserve_batch(ep, max_batch): max_batch in 1..1024, else SSHIP_ERR_INVALID.  Allocates the activations, the preprocessed input,
+ *   the tail workspace and the split-K workspace for max_batch images (about 44 x input_w x input_h bytes per image: 11.5 MB at 512 x 512).
+ *   Synchronises the device first; not legal under stream capture.  Never shrinks: a value <= sship_ep_max_batch is a no-op returning
+ *   SSHIP_OK.  When an allocation fails (SSHIP_ERR_NOMEM) the handle keeps what it had and still works.
+ * sship_ep_max_batch(ep): 1 after create, otherwise the reserved maximum; NULL -> 0.
+ * sship_ep_batch_workspace_bytes(input_w, input_h, batch): pure host, no GPU.  The smallest byte count that holds
+ *   ksplit x batch x output pixels x cout fp32 for every convolution that runs as batched split-K at this batch; 0 when none does; 0 on bad
+ *   arguments (an engine below 32 x 32, batch outside 1..1024).
+ * sship_ep_infer_u8_batch_device: image b starts at imgs_dev + b * image_stride BYTES; stride >= w * channels, image_stride >= h * stride, no
+ *   alignment asked of either (image_stride = 2 * h * stride reads the left images of an interleaved L0, R0, L1, R1, ... buffer).  All images
+ *   share one size and one channel count.  Row b of the output starts at desc_out_dev + b * desc_stride floats, desc_stride >= 512 - the
+ *   layout sship_index_add_device and sship_index_query_batch_device take.  Asynchronous on `stream`; one call in flight per handle; the first
+ *   call with a new source size uploads that size's tables exactly as the single-image entry does.  SSHIP_ERR_INVALID before any device is
+ *   touched, the handle unchanged: batch outside 1..sship_ep_max_batch (a call never grows the reservation: no hidden allocation), a NULL
+ *   pointer, bad image arguments, a stride below its minimum.
+ * sship_ep_infer_u8_batch: the same from host images to host descriptors [batch][512]; synchronous (upload, the device entry, download) -
+ *   the drop-in for a loop of sship_ep_infer_u8.
+ * sship_ep_bench_batch: measurement hook, `iters` back-to-back batch calls on the handle's stream; *avg_ms = mean duration of ONE batch call.
+ * sship_ep_debug_capture_image(ep, image): test-only, default 0: which image (0..1023) of later BATCH calls sship_ep_debug_capture copies
+ *   aside; stage numbering and sizes unchanged, per image.  A batch call with batch <= image captures nothing and _debug_activation then
+ *   returns SSHIP_ERR_INVALID.  Capture off still makes no call and no allocation. */
+int sship_ep_reserve_batch(sship_ep* ep, int max_batch);
+int sship_ep_max_batch(const sship_ep* ep);
+size_t sship_ep_batch_workspace_bytes(int input_w, int input_h, int batch);
+int sship_ep_infer_u8_batch_device(sship_ep* ep, const uint8_t* imgs_dev, int batch, int h, int w, int stride, long long image_stride,
+                                   int channels, float* desc_out_dev, int desc_stride, void* stream);
+int sship_ep_infer_u8_batch(sship_ep* ep, const uint8_t* imgs, int batch, int h, int w, int stride, long long image_stride, int channels,
+                            float* desc_out);
+int sship_ep_bench_batch(sship_ep* ep, const uint8_t* imgs_dev, int batch, int h, int w, int stride, long long image_stride, int channels,
+                         int iters, float* avg_ms);
+int sship_ep_debug_capture_image(sship_ep* ep, int image);
 /* EigenPlaces::preprocess (src/EigenPlaces.cc:123-145) on the host, no GPU: u8 image (1 channel or 3 = BGR, row stride in bytes) ->
  * fp32 [3, input_h, input_w]: GRAY2RGB / BGR2RGB, cv::resize INTER_LINEAR (OpenCV's 8-bit fixed-point path), x 1/255,
  * ImageNet mean / std.  Exported so that every binding shares one implementation. */

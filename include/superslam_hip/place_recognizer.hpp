@@ -12,6 +12,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
@@ -104,6 +105,54 @@ public:
     n = std::sqrt(n);
     if (n > 0) for (float& v : d) v = static_cast<float>(v / n);
     return d;
+  }
+  // Batches (include/sship.h "EigenPlaces: batches"): room for up to `n` images per call (1..1024; never shrinks; synchronises the device).
+  bool reserve_batch(int n) {
+    if (!ep_) { last_error_ = "EigenPlaces: not initialised"; return false; }
+    if (sship_ep_reserve_batch(ep_, n) != SSHIP_OK) { last_error_ = sship_last_error(); return false; }
+    return true;
+  }
+  int max_batch() const { return sship_ep_max_batch(ep_); }
+  // compute_global_descriptor for images of ONE size and channel count: element b has the bits of compute_global_descriptor(images[b])
+  // (the same network output, the same normalisation per row).  Runs in chunks of max_batch() images; empty when the recogniser is not
+  // initialised, the images differ in shape, or the library fails (last_error()).
+  std::vector<GlobalDescriptor> compute_global_descriptors(const std::vector<Image>& images) {
+    std::vector<GlobalDescriptor> out;
+    if (!ep_ || images.empty()) return out;
+    const Image& f = images.front();
+    for (const Image& im : images)
+      if (!im.data || im.rows != f.rows || im.cols != f.cols || im.channels != f.channels) {
+        last_error_ = "EigenPlaces::compute_global_descriptors: all images must share one size and channel count";
+        return out;
+      }
+    const size_t row = static_cast<size_t>(f.cols) * f.channels, img_bytes = row * f.rows;
+    const size_t dim = static_cast<size_t>(sship_ep_descriptor_dim(ep_)), step = static_cast<size_t>(max_batch() > 0 ? max_batch() : 1);
+    std::vector<uint8_t> packed;
+    std::vector<float> desc;
+    for (size_t i = 0; i < images.size(); i += step) {
+      const size_t n = images.size() - i < step ? images.size() - i : step;
+      packed.resize(n * img_bytes);
+      desc.resize(n * dim);
+      for (size_t b = 0; b < n; ++b) {  // the images live in buffers of their own: dense rows, dense images for one upload
+        const Image& im = images[i + b];
+        const size_t stride = im.stride ? static_cast<size_t>(im.stride) : row;
+        for (int y = 0; y < im.rows; ++y) std::memcpy(packed.data() + b * img_bytes + y * row, im.data + y * stride, row);
+      }
+      if (sship_ep_infer_u8_batch(ep_, packed.data(), static_cast<int>(n), f.rows, f.cols, static_cast<int>(row), static_cast<long long>(img_bytes),
+                                  f.channels, desc.data()) != SSHIP_OK) {
+        last_error_ = sship_last_error();
+        return std::vector<GlobalDescriptor>();
+      }
+      for (size_t b = 0; b < n; ++b) {
+        GlobalDescriptor d(desc.begin() + b * dim, desc.begin() + (b + 1) * dim);
+        double nn = 0.0;  // cv::normalize(desc, desc, 1.0, 0.0, cv::NORM_L2), per row
+        for (float v : d) nn += static_cast<double>(v) * v;
+        nn = std::sqrt(nn);
+        if (nn > 0) for (float& v : d) v = static_cast<float>(v / nn);
+        out.push_back(std::move(d));
+      }
+    }
+    return out;
   }
   const std::string& last_error() const { return last_error_; }
 

@@ -41,6 +41,32 @@ public:
     for (size_t i = 0; i < d.size(); ++i) out.ptr<float>(0)[i] = d[i];
     return out;
   }
+  // Batches (not part of superslam::IPlaceRecognizer): reserve_batch(n) once, then one descriptor row (1 x 512, CV_32F) per image of a
+  // sequence of images of ONE size and type; row b has the bits of compute_global_descriptor(images[b]).  Empty on failure.
+  bool reserve_batch(int n) {
+    const bool ok = impl_.reserve_batch(n);
+    if (!ok) SLOG_ERROR("EigenPlaces(HIP): {}", impl_.last_error());
+    return ok;
+  }
+  std::vector<cv::Mat> compute_global_descriptors(const std::vector<cv::Mat>& images) {
+    std::vector<cv::Mat> keep;
+    std::vector<superslam_hip::Image> views;
+    for (const cv::Mat& image : images) {
+      cv::Mat k = image.isContinuous() ? image : image.clone();
+      if (k.depth() != CV_8U) k.convertTo(k, CV_8U);
+      keep.push_back(k);
+    }
+    for (const cv::Mat& k : keep) views.push_back(superslam_hip::Image{k.data, k.rows, k.cols, k.channels(), static_cast<int>(k.step)});
+    const std::vector<superslam_hip::GlobalDescriptor> ds = impl_.compute_global_descriptors(views);
+    if (ds.size() != images.size() && !images.empty()) SLOG_ERROR("EigenPlaces(HIP): {}", impl_.last_error());
+    std::vector<cv::Mat> out;
+    for (const auto& d : ds) {
+      cv::Mat row(1, static_cast<int>(d.size()), CV_32F);
+      for (size_t i = 0; i < d.size(); ++i) row.ptr<float>(0)[i] = d[i];
+      out.push_back(row);
+    }
+    return out;
+  }
   // Retrieval on the device (default off).  Switch before the first add: the two indices do not share their content, and a switch
   // starts from an empty device index of `capacity` rows.
   void set_device_index(bool on, int capacity = 16384) {

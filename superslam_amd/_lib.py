@@ -164,6 +164,13 @@ _SIGS = {
     "sship_ep_bench": (ip, [vp, vp, ip, ip, ip, ip, ip, C.POINTER(C.c_float)]),
     "sship_ep_debug_capture": (ip, [vp, ip]),
     "sship_ep_debug_activation": (ip, [vp, ip, vp, C.c_ulonglong]),
+    "sship_ep_reserve_batch": (ip, [vp, ip]),
+    "sship_ep_max_batch": (ip, [vp]),
+    "sship_ep_batch_workspace_bytes": (C.c_size_t, [ip, ip, ip]),
+    "sship_ep_infer_u8_batch_device": (ip, [vp, vp, ip, ip, ip, ip, C.c_longlong, ip, vp, ip, vp]),
+    "sship_ep_infer_u8_batch": (ip, [vp, vp, ip, ip, ip, ip, C.c_longlong, ip, vp]),
+    "sship_ep_bench_batch": (ip, [vp, vp, ip, ip, ip, ip, C.c_longlong, ip, ip, C.POINTER(C.c_float)]),
+    "sship_ep_debug_capture_image": (ip, [vp, ip]),
     "sship_index_create": (ip, [ip, ip, ip, ip, C.POINTER(vp)]),
     "sship_index_destroy": (None, [vp]),
     "sship_index_dim": (ip, [vp]),

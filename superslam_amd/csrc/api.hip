@@ -2474,7 +2474,12 @@ struct sship_ep {
   bool capture = false, captured = false, cap_ready = false;   // captured: a call has run since capture was switched on
   size_t cap_bytes[kStages] = {};           // 0: the stage does not exist (a block without a downsample)
   DevBuf cap[kStages];
+  // batch entry points (sship_ep_reserve_batch): d_in, act, d_ws, d_tail and d_out / h_out hold max_batch images ([B][...] slices; the
+  // single-image path uses slice 0 of the same buffers); cap_image = the image of a batch call the capture copies aside
+  int max_batch = 1, cap_image = 0;
 };
+// words (4 bytes) between the tail slices of two images: [kTailPoolWg * 512 | 512] floats, the arrival counter, one pad word
+static size_t ep_tail_slice() { return ep_tail_ws_floats() + 2; }
 extern "C" void sship_ep_destroy(sship_ep* ep) {
   bind_thread();
   if (!ep) return;
@@ -2581,6 +2586,7 @@ extern "C" int sship_ep_preprocess(const uint8_t* img, int h, int w, int stride,
   superslam_hip::eigenplaces_preprocess(superslam_hip::Image{img, h, w, channels, stride}, input_w, input_h, chw_out);
   return SSHIP_OK;
 }
+constexpr int kEpMaxBatch = 1024;
 // sizes of the capture stages of an engine (the numbering of include/sship.h), from the same ceil chain as ep_network
 static void ep_stage_bytes(const sship_ep* ep, size_t (&bytes)[sship_ep::kStages]) {
   int h = (ep->in_h - 1) / 2 + 1, w = (ep->in_w - 1) / 2 + 1;
@@ -2649,6 +2655,55 @@ static int ep_network(sship_ep* ep, float* desc_dev, hipStream_t s) {
   if (ep->capture) ep->captured = true;
   return SSHIP_OK;
 }
+// The same network for B images: the preprocessed [B][3][H][W] tensor in d_in -> row b of desc_dev (desc_stride floats apart).  Every map is
+// [B][h][w][c]; per image the launches compute what ep_network computes, bit for bit (include/sship.h: the batch rule).  The capture copies
+// image cap_image's slice of every stage (nothing when the batch does not hold that image).
+static int ep_network_batch(sship_ep* ep, int B, float* desc_dev, int desc_stride, hipStream_t s) {
+  const int H = ep->in_h, W = ep->in_w;
+  int h = (H - 1) / 2 + 1, w = (W - 1) / 2 + 1;
+  const bool capturing = ep->capture && ep->cap_image < B;
+  const size_t ci = (size_t)ep->cap_image;
+  auto cap = [&](int stage, const void* base, size_t image_bytes) -> hipError_t {
+    if (!capturing) return hipSuccess;
+    return hipMemcpyAsync(ep->cap[stage].p, static_cast<const char*>(base) + ci * image_bytes, ep->cap_bytes[stage], hipMemcpyDeviceToDevice, s);
+  };
+  auto cap_map = [&](int stage, const void* base) { return cap(stage, base, ep->cap_bytes[stage]); };
+  SSHIP_HIP_CHECK(cap_map(0, ep->d_in.p));
+  _Float16* a[4] = {ep->act[0].as<_Float16>(), ep->act[1].as<_Float16>(), ep->act[2].as<_Float16>(), ep->act[3].as<_Float16>()};
+  const int hp = (h - 1) / 2 + 1, wp = (w - 1) / 2 + 1;
+  launch_ep_stem_pool(ep->d_in.as<float>(), H, W, h, w, hp, wp, ep->stem_frag.as<_Float16>(), ep->stem_bias.as<float>(), a[1], s, B);
+  h = hp; w = wp;
+  SSHIP_HIP_CHECK(cap_map(1, a[1]));
+  int cur = 1, stage = 2;
+  float* ws = ep->d_ws.as<float>();
+  const size_t wsb = ep->d_ws.bytes, ws1 = ep_splitk_workspace_bytes(H, W);
+  for (const auto& blk : ep->blocks) {
+    int f[3], k = 0;
+    for (int i = 0; i < 4; ++i) if (i != cur) f[k++] = i;
+    const _Float16* res = a[cur];
+    int ho = h, wo = w;
+    if (blk.stride == 2) { ho = (h + 1) / 2; wo = (w + 1) / 2; }
+    SSHIP_HIP_CHECK(ep_conv_batch(blk.c1, a[cur], a[f[0]], nullptr, h, w, true, blk.stride == 2, B, s, ws, wsb, ws1));
+    SSHIP_HIP_CHECK(cap_map(stage, a[f[0]]));
+    if (blk.has_ds) {
+      SSHIP_HIP_CHECK(ep_conv_batch(blk.ds, a[cur], a[f[1]], nullptr, h, w, false, blk.stride == 2, B, s, nullptr, 0, 0));
+      SSHIP_HIP_CHECK(cap_map(stage + 1, a[f[1]]));
+      res = a[f[1]];
+    }
+    SSHIP_HIP_CHECK(ep_conv_batch(blk.c2, a[f[0]], a[f[2]], res, ho, wo, true, false, B, s, ws, wsb, ws1));
+    SSHIP_HIP_CHECK(cap_map(stage + 2, a[f[2]]));
+    cur = f[2]; h = ho; w = wo; stage += 3;
+  }
+  const size_t slice = ep_tail_slice();
+  launch_ep_tail(a[cur], h * w, ep->gem_p, ep->fc_wt, ep->fc_b, ep->d_tail.as<float>(), ep->d_tail.as<int>() + ep_tail_ws_floats(), desc_dev, s, B,
+                 (int)slice, desc_stride);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  SSHIP_HIP_CHECK(cap(26, ep->d_tail.p, slice * 4));
+  SSHIP_HIP_CHECK(cap(27, ep->d_tail.as<float>() + ep_tail_ws_floats() - 512, slice * 4));
+  SSHIP_HIP_CHECK(cap(28, desc_dev, (size_t)desc_stride * 4));
+  if (ep->capture) ep->captured = capturing;
+  return SSHIP_OK;
+}
 // Test-only (include/sship.h): per-stage capture of the network's activations
 extern "C" int sship_ep_debug_capture(sship_ep* ep, int on) {
   bind_thread();
@@ -2660,6 +2715,12 @@ extern "C" int sship_ep_debug_capture(sship_ep* ep, int on) {
     ep->cap_ready = true;
   }
   ep->capture = on != 0;
+  ep->captured = false;
+  return SSHIP_OK;
+}
+extern "C" int sship_ep_debug_capture_image(sship_ep* ep, int image) {
+  if (!ep || image < 0 || image >= kEpMaxBatch) return fail(SSHIP_ERR_INVALID, "ep_debug_capture_image: null handle or image outside 0..1023");
+  ep->cap_image = image;
   ep->captured = false;
   return SSHIP_OK;
 }
@@ -2755,6 +2816,112 @@ extern "C" int sship_ep_bench(sship_ep* ep, const uint8_t* img_dev, int h, int w
     return fail(SSHIP_ERR_HIP, "ep_bench: timing failed");
   *avg_ms = ms / iters;
   return SSHIP_OK;
+}
+
+// ---- batches (include/sship.h "EigenPlaces: batches") ----
+extern "C" int sship_ep_max_batch(const sship_ep* ep) { return ep ? ep->max_batch : 0; }
+extern "C" size_t sship_ep_batch_workspace_bytes(int input_w, int input_h, int batch) {
+  if (input_w < 32 || input_h < 32 || input_w > 16384 || input_h > 16384 || batch < 1 || batch > kEpMaxBatch) return 0;
+  return ep_batch_workspace_bytes(input_h, input_w, batch);
+}
+template <class Buf>
+static void swap_buf(Buf& a, Buf& b) { std::swap(a.p, b.p); std::swap(a.bytes, b.bytes); }
+extern "C" int sship_ep_reserve_batch(sship_ep* ep, int max_batch) {
+  bind_thread();
+  if (!ep || max_batch < 1 || max_batch > kEpMaxBatch) return fail(SSHIP_ERR_INVALID, "ep_reserve_batch: null handle or max_batch outside 1..1024");
+  if (max_batch <= ep->max_batch) return SSHIP_OK;   // never shrinks
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());           // nothing may still read the buffers that are about to be replaced
+  const size_t n = (size_t)max_batch;
+  const int H = ep->in_h, W = ep->in_w;
+  const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, hp = (Ho - 1) / 2 + 1, wp = (Wo - 1) / 2 + 1;
+  // the largest map of the batch path is the pooled one (the stem map never reaches HBM); slice 0 keeps the single-image path's size
+  size_t map_elems = (size_t)hp * wp * 64;
+  for (int L = 0, hh = hp, ww = wp; L < 3; ++L) {
+    hh = (hh + 1) / 2; ww = (ww + 1) / 2;
+    map_elems = std::max(map_elems, (size_t)hh * ww * (128u << L));
+  }
+  const size_t act_bytes = std::max((size_t)Ho * Wo * 64 * 2, n * map_elems * 2);
+  size_t ws_bytes = ep_splitk_workspace_bytes(H, W);
+  for (int b = 1; b <= max_batch; ++b) ws_bytes = std::max(ws_bytes, ep_batch_workspace_bytes(H, W, b));  // a layer's need drops to 0 where it turns grouped
+  // everything into fresh buffers first: a failed allocation leaves the handle as it was
+  DevBuf in, act[4], ws, tail, out;
+  PinBuf hout;
+  hipError_t e = in.ensure(n * 3 * H * W * 4);
+  for (auto& a : act) if (e == hipSuccess) e = a.ensure(act_bytes);
+  if (e == hipSuccess) e = ws.ensure(ws_bytes);
+  if (e == hipSuccess) e = tail.ensure(n * ep_tail_slice() * 4);
+  if (e == hipSuccess) e = out.ensure(n * 512 * 4);
+  if (e == hipSuccess) e = hout.ensure(n * 512 * 4);
+  if (e == hipSuccess) e = hipMemset(tail.p, 0, n * ep_tail_slice() * 4);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(SSHIP_ERR_NOMEM, std::string("ep_reserve_batch: ") + hipGetErrorString(e) + " (the handle keeps its reservation of " +
+                                     std::to_string(ep->max_batch) + ")");
+  }
+  swap_buf(ep->d_in, in);
+  for (int i = 0; i < 4; ++i) swap_buf(ep->act[i], act[i]);
+  swap_buf(ep->d_ws, ws); swap_buf(ep->d_tail, tail); swap_buf(ep->d_out, out); swap_buf(ep->h_out, hout);
+  ep->max_batch = max_batch;
+  return SSHIP_OK;
+}
+// the argument checks every batch entry shares: nothing on the device is touched and the handle is unchanged when they fail
+static int ep_check_batch(const sship_ep* ep, const void* imgs, int batch, int h, int w, int stride, long long image_stride, int channels,
+                          const char* who) {
+  if (!ep) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null handle");
+  if (batch < 1 || batch > ep->max_batch)
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": batch " + std::to_string(batch) + " outside 1.." + std::to_string(ep->max_batch) +
+                                       " (sship_ep_reserve_batch grows the reservation; a call never does)");
+  if (int rc = ep_check_image(imgs, h, w, stride, channels, who)) return rc;
+  if (image_stride < (long long)h * stride) return fail(SSHIP_ERR_INVALID, std::string(who) + ": image_stride below h * stride");
+  return SSHIP_OK;
+}
+extern "C" int sship_ep_infer_u8_batch_device(sship_ep* ep, const uint8_t* imgs_dev, int batch, int h, int w, int stride, long long image_stride,
+                                              int channels, float* desc_out_dev, int desc_stride, void* stream) {
+  bind_thread();
+  if (int rc = ep_check_batch(ep, imgs_dev, batch, h, w, stride, image_stride, channels, "ep_infer_u8_batch_device")) return rc;
+  if (!desc_out_dev || desc_stride < 512) return fail(SSHIP_ERR_INVALID, "ep_infer_u8_batch_device: null output or desc_stride below 512");
+  const int* tab = nullptr;
+  if (int rc = ep_tables(ep, h, w, &tab)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  launch_ep_resize_norm(imgs_dev, stride, channels, tab, ep->in_w, ep->in_h, ep->d_in.as<float>(), s, batch, image_stride);
+  return ep_network_batch(ep, batch, desc_out_dev, desc_stride, s);
+}
+extern "C" int sship_ep_infer_u8_batch(sship_ep* ep, const uint8_t* imgs, int batch, int h, int w, int stride, long long image_stride, int channels,
+                                       float* desc_out) {
+  bind_thread();
+  if (int rc = ep_check_batch(ep, imgs, batch, h, w, stride, image_stride, channels, "ep_infer_u8_batch")) return rc;
+  if (!desc_out) return fail(SSHIP_ERR_INVALID, "ep_infer_u8_batch: null output");
+  hipStream_t s = ep->stream;
+  const size_t row = (size_t)w * channels, img_bytes = row * h, bytes = img_bytes * batch;
+  SSHIP_HIP_CHECK(ep->h_img.ensure(bytes));
+  SSHIP_HIP_CHECK(ep->d_img.ensure(bytes));
+  for (int b = 0; b < batch; ++b)
+    for (int y = 0; y < h; ++y)   // pinned, dense rows, dense images
+      memcpy(ep->h_img.as<uint8_t>() + b * img_bytes + (size_t)y * row, imgs + (long long)b * image_stride + (size_t)y * stride, row);
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ep->d_img.p, ep->h_img.p, bytes, hipMemcpyHostToDevice, s));
+  if (int rc = sship_ep_infer_u8_batch_device(ep, ep->d_img.as<uint8_t>(), batch, h, w, (int)row, (long long)img_bytes, channels,
+                                              ep->d_out.as<float>(), 512, s))
+    return rc;
+  SSHIP_HIP_CHECK(hipMemcpyAsync(ep->h_out.p, ep->d_out.p, (size_t)batch * 512 * 4, hipMemcpyDeviceToHost, s));
+  SSHIP_HIP_CHECK(hipStreamSynchronize(s));
+  memcpy(desc_out, ep->h_out.p, (size_t)batch * 512 * 4);
+  return SSHIP_OK;
+}
+// Measurement hook: `iters` back-to-back batch calls on the handle's stream over resident images; *avg_ms = the mean duration of ONE batch call
+extern "C" int sship_ep_bench_batch(sship_ep* ep, const uint8_t* imgs_dev, int batch, int h, int w, int stride, long long image_stride, int channels,
+                                    int iters, float* avg_ms) {
+  bind_thread();
+  if (!avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "ep_bench_batch: bad arguments");
+  if (int rc = ep_check_batch(ep, imgs_dev, batch, h, w, stride, image_stride, channels, "ep_bench_batch")) return rc;
+  hipStream_t s = ep->stream;
+  float* out = ep->d_out.as<float>();
+  int rc = SSHIP_OK;
+  auto run = [&]() -> hipError_t {
+    rc = sship_ep_infer_u8_batch_device(ep, imgs_dev, batch, h, w, stride, image_stride, channels, out, 512, s);
+    return rc == SSHIP_OK ? hipSuccess : hipErrorUnknown;
+  };
+  const int brc = bench_loop(s, iters, run, avg_ms);   // the first (warm) run also uploads the tables
+  return rc != SSHIP_OK ? rc : brc;
 }
 
 // ====================================================================================================

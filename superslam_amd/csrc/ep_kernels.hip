@@ -90,17 +90,18 @@ static int ep_ksplit(const ConvW& w, int H, int W, int th) {
   while (k * 2 <= nchunk && wgs * k * 2 <= kEpSplitTargetWgs) k *= 2;
   return k;
 }
+// B images: the workspace is [z][B][pix][cout] and the finish kernel runs over the B * npix pixels of the batch (per element the same adds)
 template <int CIN, int TH>
 static hipError_t ep_conv_splitk(const ConvW& w, const _Float16* in, _Float16* out, const _Float16* res, int H, int W, bool relu, bool decim,
-                                 int ksplit, float* ws, hipStream_t s) {
+                                 int ksplit, float* ws, hipStream_t s, int B = 1) {
   IgemmArgs a{};
   a.in0 = in; a.in1 = in; a.cs0 = CIN; a.cs1 = CIN; a.cin0 = CIN;
-  a.wpack = w.w; a.bias = w.bias; a.B = 1; a.H = H; a.W = W; a.cout = w.cout; a.ostride = w.cout;
+  a.wpack = w.w; a.bias = w.bias; a.B = B; a.H = H; a.W = W; a.cout = w.cout; a.ostride = w.cout;
   a.out0 = ws;
   hipError_t e = decim ? launch_igemm_splitk<3, CIN, 64, TH, EpiPartial<true>>(a, w.cout_pad, ksplit, s)
                        : launch_igemm_splitk<3, CIN, 64, TH, EpiPartial<false>>(a, w.cout_pad, ksplit, s);
   if (e != hipSuccess) return e;
-  const int npix = decim ? ((H + 1) / 2) * ((W + 1) / 2) : H * W;
+  const int npix = B * (decim ? ((H + 1) / 2) * ((W + 1) / 2) : H * W);
   const int n = npix * (w.cout / 4);
   if (res) hipLaunchKernelGGL((k_ep_splitk_finish<true, true>), dim3((n + 255) / 256), dim3(256), 0, s, ws, ksplit, npix, w.cout, w.bias, res, out);
   else if (relu) hipLaunchKernelGGL((k_ep_splitk_finish<true, false>), dim3((n + 255) / 256), dim3(256), 0, s, ws, ksplit, npix, w.cout, w.bias, res, out);
@@ -165,6 +166,111 @@ hipError_t ep_conv(const ConvW& w, const _Float16* in, _Float16* out, const _Flo
   return hipErrorInvalidValue;
 }
 
+// ---- a batch of images (sship_ep_infer_u8_batch*) ----
+// The rule: image b of a batch gets the bits the single-image path gives it.  A deep layer therefore keeps the split k of ep_conv (workspace
+// guard of the SINGLE-image workspace included): k fixes the fp32 summation order.  What varies with the batch is only where the k group sums
+// are added: batched split-K (partials through the workspace, k_ep_splitk_finish) while the batch still leaves CUs idle, the grouped kernel
+// (igemm.h: GROUPED; one launch, nothing through HBM) once batch x unsplit workgroups reaches the target.  A function of (layer shape, batch).
+EpBatchPlan ep_batch_plan(int ks, int cin, int cout, int cout_pad, int H, int W, bool decim, int batch, size_t ws1_bytes) {
+  EpBatchPlan pl{kEpDirect, 1, 8};
+  if (ks != 3 || cin < 128 || cout % 64) return pl;
+  const bool th4 = H * W <= 64 * 64;
+  const int th = th4 ? 4 : 8;
+  ConvW w{};
+  w.ks = ks; w.cin = cin; w.cout = cout; w.cout_pad = cout_pad;
+  int k = ep_ksplit(w, H, W, th);
+  const size_t npix_out = decim ? (size_t)((H + 1) / 2) * ((W + 1) / 2) : (size_t)H * W;
+  while (k > 1 && (size_t)k * npix_out * cout * sizeof(float) > ws1_bytes) k >>= 1;
+  if (k == 1) return pl;
+  const long wgs_unsplit = (long)((W + 31) / 32) * ((H + th - 1) / th) * ((cout_pad + 63) / 64);
+  pl.k = k; pl.th = th;
+  pl.form = (long)batch * wgs_unsplit < kEpSplitTargetWgs ? kEpSplit : kEpGrouped;
+#if SSHIP_DEV_SWITCHES  // A/B of the threshold: every deep layer in one form; the bits are the same
+  if (const char* e = dev_env("SUPERSLAM_HIP_EP_BATCH")) {
+    if (std::string(e) == "split") pl.form = kEpSplit;
+    if (std::string(e) == "grouped") pl.form = kEpGrouped;
+  }
+#endif
+  return pl;
+}
+// the smallest workspace that holds k x batch x output pixels x cout floats of every layer the rule runs as batched split-K at this batch
+size_t ep_batch_workspace_bytes(int in_h, int in_w, int batch) {
+  const size_t ws1 = ep_splitk_workspace_bytes(in_h, in_w);
+  int h = (in_h - 1) / 2 + 1, w = (in_w - 1) / 2 + 1;
+  h = (h - 1) / 2 + 1; w = (w - 1) / 2 + 1;
+  size_t need = 0;
+  const int planes[3] = {128, 256, 512};
+  int cin = 64;
+  for (int L = 0; L < 3; ++L) {
+    const int ho = (h + 1) / 2, wo = (w + 1) / 2;
+    const size_t npix = (size_t)ho * wo;
+    auto one = [&](int ci, int H, int W, bool decim) {
+      const EpBatchPlan pl = ep_batch_plan(3, ci, planes[L], planes[L], H, W, decim, batch, ws1);
+      if (pl.form != kEpSplit) return;
+      const size_t n = (size_t)pl.k * batch * npix * planes[L];
+      need = need > n ? need : n;
+    };
+    one(cin, h, w, true);                 // block 0 conv1 (decimating)
+    one(planes[L], ho, wo, false);        // block 0 conv2, block 1 conv1 / conv2
+    cin = planes[L]; h = ho; w = wo;
+  }
+  return need * sizeof(float);
+}
+template <int CIN, int TH>
+static hipError_t ep_conv_grouped(const ConvW& w, const _Float16* in, _Float16* out, const _Float16* res, int H, int W, bool relu, bool decim,
+                                  int k, int B, hipStream_t s) {
+  IgemmArgs a{};
+  a.in0 = in; a.in1 = in; a.cs0 = CIN; a.cs1 = CIN; a.cin0 = CIN;
+  a.wpack = w.w; a.bias = w.bias; a.B = B; a.H = H; a.W = W; a.cout = w.cout; a.ostride = w.cout; a.flags = k;
+  a.out0 = out; a.out1 = const_cast<_Float16*>(res);
+  if (res) return launch_igemm_grouped<3, CIN, 64, TH, EpiEP<true, true, false>>(a, w.cout_pad, s);
+  if (decim) return relu ? launch_igemm_grouped<3, CIN, 64, TH, EpiEP<true, false, true>>(a, w.cout_pad, s) : hipErrorInvalidValue;
+  return relu ? launch_igemm_grouped<3, CIN, 64, TH, EpiEP<true, false, false>>(a, w.cout_pad, s) : hipErrorInvalidValue;  // the chain has no deep 3x3 without ReLU
+}
+template <int KS, int CIN, int TH>
+static hipError_t ep_gemm_batch(const ConvW& w, const _Float16* in, _Float16* out, const _Float16* res, int H, int W, bool relu, bool decim, int B,
+                                hipStream_t s) {
+  IgemmArgs a{};
+  a.in0 = in; a.in1 = in; a.cs0 = CIN; a.cs1 = CIN; a.cin0 = CIN;
+  a.wpack = w.w; a.bias = w.bias; a.B = B; a.H = H; a.W = W; a.cout = w.cout; a.ostride = w.cout;
+  a.out0 = out; a.out1 = const_cast<_Float16*>(res);
+  if (res) return launch_igemm<KS, CIN, 64, TH, EpiEP<true, true, false>>(a, w.cout_pad, s);
+  if (decim) return relu ? launch_igemm<KS, CIN, 64, TH, EpiEP<true, false, true>>(a, w.cout_pad, s)
+                         : launch_igemm<KS, CIN, 64, TH, EpiEP<false, false, true>>(a, w.cout_pad, s);
+  return relu ? launch_igemm<KS, CIN, 64, TH, EpiEP<true, false, false>>(a, w.cout_pad, s)
+              : launch_igemm<KS, CIN, 64, TH, EpiEP<false, false, false>>(a, w.cout_pad, s);
+}
+// ep_conv for B images, maps [B][H][W][c].  ws1_bytes: the single-image workspace of the engine (it guards k as ep_conv does); an undersized
+// batch workspace is an ERROR here, never a smaller split (that would change bits).  The direct layers run the kernels ep_conv runs.
+hipError_t ep_conv_batch(const ConvW& w, const _Float16* in, _Float16* out, const _Float16* res, int H, int W, bool relu, bool decim, int B,
+                         hipStream_t s, float* ws, size_t ws_bytes, size_t ws1_bytes) {
+  if (B < 1 || (long long)B * H * W > (1ll << 30)) return hipErrorInvalidValue;  // pixel indices stay below 2^31 in the kernels' int arithmetic
+  const EpBatchPlan pl = ws1_bytes ? ep_batch_plan(w.ks, w.cin, w.cout, w.cout_pad, H, W, decim, B, ws1_bytes) : EpBatchPlan{kEpDirect, 1, 8};
+  if (pl.form == kEpSplit) {
+    const size_t npix_out = decim ? (size_t)((H + 1) / 2) * ((W + 1) / 2) : (size_t)H * W;
+    if (!ws || (size_t)pl.k * B * npix_out * w.cout * sizeof(float) > ws_bytes) return hipErrorInvalidValue;
+    const bool th4 = pl.th == 4;
+    if (w.cin == 128) return th4 ? ep_conv_splitk<128, 4>(w, in, out, res, H, W, relu, decim, pl.k, ws, s, B) : ep_conv_splitk<128, 8>(w, in, out, res, H, W, relu, decim, pl.k, ws, s, B);
+    if (w.cin == 256) return th4 ? ep_conv_splitk<256, 4>(w, in, out, res, H, W, relu, decim, pl.k, ws, s, B) : ep_conv_splitk<256, 8>(w, in, out, res, H, W, relu, decim, pl.k, ws, s, B);
+    if (w.cin == 512) return th4 ? ep_conv_splitk<512, 4>(w, in, out, res, H, W, relu, decim, pl.k, ws, s, B) : ep_conv_splitk<512, 8>(w, in, out, res, H, W, relu, decim, pl.k, ws, s, B);
+    return hipErrorInvalidValue;
+  }
+  if (pl.form == kEpGrouped) {
+    const bool th4 = pl.th == 4;
+    if (w.cin == 128) return th4 ? ep_conv_grouped<128, 4>(w, in, out, res, H, W, relu, decim, pl.k, B, s) : ep_conv_grouped<128, 8>(w, in, out, res, H, W, relu, decim, pl.k, B, s);
+    if (w.cin == 256) return th4 ? ep_conv_grouped<256, 4>(w, in, out, res, H, W, relu, decim, pl.k, B, s) : ep_conv_grouped<256, 8>(w, in, out, res, H, W, relu, decim, pl.k, B, s);
+    if (w.cin == 512) return th4 ? ep_conv_grouped<512, 4>(w, in, out, res, H, W, relu, decim, pl.k, B, s) : ep_conv_grouped<512, 8>(w, in, out, res, H, W, relu, decim, pl.k, B, s);
+    return hipErrorInvalidValue;
+  }
+  if (w.ks == 3 && w.cin == 64 && !decim && H * W <= 160 * 160) return ep_gemm_batch<3, 64, 4>(w, in, out, res, H, W, relu, decim, B, s);
+#define EP_CASE(KS_, CIN_) \
+  if (w.ks == KS_ && w.cin == CIN_) return ep_gemm_batch<KS_, CIN_, 8>(w, in, out, res, H, W, relu, decim, B, s);
+  EP_CASE(3, 64) EP_CASE(3, 128) EP_CASE(3, 256) EP_CASE(3, 512)
+  EP_CASE(1, 64) EP_CASE(1, 128) EP_CASE(1, 256)
+#undef EP_CASE
+  return hipErrorInvalidValue;
+}
+
 // EigenPlaces::preprocess on the device (src/EigenPlaces.cc:123-145): GRAY2RGB / BGR2RGB, cv::resize INTER_LINEAR on 8-bit data, x 1/255,
 // ImageNet mean / std, HWC -> CHW.  OpenCV's 8-bit path is fixed-point and this kernel is its restatement integer for integer
 // (include/superslam_hip/place_recognizer.hpp::resize_bilinear_u8 is the host form the oracle pins): the tables hold, per output column /
@@ -177,11 +283,15 @@ hipError_t ep_conv(const ConvW& w, const _Float16* in, _Float16* out, const _Flo
 // mean; the stem's fp16 rounding hid that from every descriptor test - tests/test_gpu_ep_layers.py compares the tensor itself).
 // Output fp32 CHW, bit-identical to sship_ep_preprocess.
 // tab: [4][out_w] ints (sx, sx1, ax0, ax1) then [4][out_h] (sy, sy1, by0, by1)
-__global__ __launch_bounds__(256) void k_ep_resize_norm(const uint8_t* __restrict__ src, int stride, int ch, const int* __restrict__ tab,
-                                                        int out_w, int out_h, float* __restrict__ out) {
+// blockIdx.y = the image of a batch: its source starts image_stride BYTES after the previous one's (no alignment asked), its output is slice
+// blockIdx.y of [B][3][out_h][out_w].
+__global__ __launch_bounds__(256) void k_ep_resize_norm(const uint8_t* __restrict__ src, int stride, long long image_stride, int ch,
+                                                        const int* __restrict__ tab, int out_w, int out_h, float* __restrict__ out) {
 #pragma clang fp contract(off)
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= out_w * out_h) return;
+  src += (long long)blockIdx.y * image_stride;
+  out += (size_t)blockIdx.y * 3 * out_w * out_h;
   const int y = idx / out_w, x = idx - y * out_w;
   const int sx = tab[x], sx1 = tab[out_w + x], ax0 = tab[2 * out_w + x], ax1 = tab[3 * out_w + x];
   const int* ty = tab + 4 * out_w;
@@ -201,9 +311,10 @@ __global__ __launch_bounds__(256) void k_ep_resize_norm(const uint8_t* __restric
     out[c * hw + idx] = (f - kMean[c]) / kStd[c];
   }
 }
-void launch_ep_resize_norm(const uint8_t* src, int stride, int ch, const int* tab, int out_w, int out_h, float* out, hipStream_t s) {
+void launch_ep_resize_norm(const uint8_t* src, int stride, int ch, const int* tab, int out_w, int out_h, float* out, hipStream_t s, int B,
+                           long long image_stride) {
   const int n = out_w * out_h;
-  hipLaunchKernelGGL(k_ep_resize_norm, dim3((n + 255) / 256), dim3(256), 0, s, src, stride, ch, tab, out_w, out_h, out);
+  hipLaunchKernelGGL(k_ep_resize_norm, dim3((n + 255) / 256, B), dim3(256), 0, s, src, stride, image_stride, ch, tab, out_w, out_h, out);
 }
 
 // stem im2col: fp32 CHW [3][H][W] -> fp16 rows [Ho*Wo][192], k = c*49 + ky*7 + kx (PyTorch weight order), zero padded
@@ -285,6 +396,8 @@ __global__ __launch_bounds__(256) void k_ep_stem_pool(const float* __restrict__ 
   __shared__ __attribute__((aligned(16))) _Float16 s_in[3 * kStemIT * kStemIW];
   __shared__ __attribute__((aligned(16))) _Float16 s_st[320 * kStemLd];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = lane & 31, kg = lane >> 5;
+  x += (size_t)blockIdx.y * 3 * H * W;        // blockIdx.y = the image of a batch: [B][3][H][W] -> [B][Hp][Wp][64]
+  out += (size_t)blockIdx.y * Hp * Wp * 64;
   const int tiles_x = (Wp + kStemPT - 1) / kStemPT;
   const int py0 = (blockIdx.x / tiles_x) * kStemPT, px0 = (blockIdx.x % tiles_x) * kStemPT;
   const int sy0 = 2 * py0 - 1, sx0 = 2 * px0 - 1;     // first stem pixel of the tile (may be -1: pooling padding)
@@ -356,9 +469,9 @@ __global__ __launch_bounds__(256) void k_ep_stem_pool(const float* __restrict__ 
   }
 }
 void launch_ep_stem_pool(const float* x, int H, int W, int Ho, int Wo, int Hp, int Wp, const _Float16* wfrag, const float* bias, _Float16* out,
-                         hipStream_t s) {
+                         hipStream_t s, int B) {
   const int tiles = ((Hp + kStemPT - 1) / kStemPT) * ((Wp + kStemPT - 1) / kStemPT);
-  hipLaunchKernelGGL(k_ep_stem_pool, dim3(tiles), dim3(256), 0, s, x, H, W, Ho, Wo, Hp, Wp, wfrag, bias, out);
+  hipLaunchKernelGGL(k_ep_stem_pool, dim3(tiles, B), dim3(256), 0, s, x, H, W, Ho, Wo, Hp, Wp, wfrag, bias, out);
 }
 
 // aggregation tail: per-location L2 normalisation over the 512 channels, GeM(p, eps = 1e-6) over the npix locations, Linear(512 -> 512)
@@ -380,10 +493,15 @@ void launch_ep_stem_pool(const float* x, int H, int W, int Ho, int Wo, int Hp, i
 constexpr int kTailWg = 8;
 constexpr int kTailPoolWg = 32;
 int ep_tail_pool_wgs(int npix) { const int g = (npix + 7) / 8; return g < kTailPoolWg ? g : kTailPoolWg; }  // a function of the map size only
+// blockIdx.y = the image of a batch: map slice blockIdx.y of [B][npix][512] and tail slice blockIdx.y (slice floats apart: its partial sums,
+// its [512] pre-normalisation outputs and its own arrival counter).  Per image the workgroup count, the walk and the add order are unchanged.
 __global__ __launch_bounds__(512) void k_ep_tail_pool(const _Float16* __restrict__ feat, int npix, float p, float* __restrict__ g_part,
-                                                      int* __restrict__ counters) {
+                                                      int* __restrict__ counters, int slice) {
   __shared__ float s_part[8 * 512];
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63, g = blockIdx.x, G = gridDim.x;
+  feat += (size_t)blockIdx.y * npix * 512;
+  g_part += (size_t)blockIdx.y * slice;
+  counters += (size_t)blockIdx.y * slice;
   if (g == 0 && t == 0) counters[0] = 0;  // k_ep_tail_fc's ticket (stream-ordered after this kernel)
   float acc[8];
 #pragma unroll
@@ -411,10 +529,14 @@ __global__ __launch_bounds__(512) void k_ep_tail_pool(const _Float16* __restrict
 }
 __global__ __launch_bounds__(512) void k_ep_tail_fc(const float* __restrict__ g_part, int nparts, int npix, float p, const float* __restrict__ wt,
                                                     const float* __restrict__ bias, float* __restrict__ y_ws, int* __restrict__ counters,
-                                                    float* __restrict__ out) {
+                                                    float* __restrict__ out, int slice, int out_stride) {
   __shared__ float s_g[512], s_part[512], s_red[8];
   __shared__ int s_last;
   const int t = threadIdx.x, wave = t >> 6, lane = t & 63, g = blockIdx.x;
+  g_part += (size_t)blockIdx.y * slice;
+  y_ws += (size_t)blockIdx.y * slice;
+  counters += (size_t)blockIdx.y * slice;
+  out += (size_t)blockIdx.y * out_stride;
   // (3) Linear: outputs [64 g, 64 g + 64); thread (part, output) covers inputs [64 part, 64 part + 64): its weights first (independent of the
   // pooled values: the 64 loads overlap the partial-sum reads), then the GeM of channel t
   const int j = 64 * g + lane, part = wave;
@@ -460,12 +582,15 @@ __global__ __launch_bounds__(512) void k_ep_tail_fc(const float* __restrict__ g_
 }
 // ws: [kTailPoolWg * 512 partial sums | 512 pre-normalisation outputs] floats (sship_ep_tail_ws_floats), counters: [>= 1] int (any value: the first
 // kernel resets it).  Calls of one handle are stream-ordered (include/sship.h).
+// B images: image b uses ws + b * slice and counters + b * slice (slice in 4-byte words, >= ep_tail_ws_floats() + 1 when the counter follows
+// the floats) and writes row b of out, out_stride floats apart.
 size_t ep_tail_ws_floats() { return (size_t)kTailPoolWg * 512 + 512; }
 void launch_ep_tail(const _Float16* feat, int npix, float p, const float* wt, const float* bias, float* ws, int* counters, float* out,
-                    hipStream_t s) {
+                    hipStream_t s, int B, int slice, int out_stride) {
   const int G = ep_tail_pool_wgs(npix);
-  hipLaunchKernelGGL(k_ep_tail_pool, dim3(G), dim3(512), 0, s, feat, npix, p, ws, counters);
-  hipLaunchKernelGGL(k_ep_tail_fc, dim3(kTailWg), dim3(512), 0, s, ws, G, npix, p, wt, bias, ws + (size_t)kTailPoolWg * 512, counters, out);
+  hipLaunchKernelGGL(k_ep_tail_pool, dim3(G, B), dim3(512), 0, s, feat, npix, p, ws, counters, slice);
+  hipLaunchKernelGGL(k_ep_tail_fc, dim3(kTailWg, B), dim3(512), 0, s, ws, G, npix, p, wt, bias, ws + (size_t)kTailPoolWg * 512, counters, out, slice,
+                     out_stride);
 }
 
 }  // namespace sship

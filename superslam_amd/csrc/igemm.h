@@ -48,7 +48,11 @@ constexpr int kCP = 72;  // halfs per LDS pixel (64 channels + 8 pad)
 // SPLITK (EigenPlaces' deep, small-map layers): blockIdx.z owns the 64-channel chunks [z NCHUNK / gridDim.z, (z + 1) NCHUNK / gridDim.z) of
 // the reduction and the epilogue (EpiPartial) writes raw fp32 partial sums; a 16 x 16 x 512 layer is 16 workgroups walking 4.7 MB of
 // weights otherwise.  false: the code is exactly what it was.
-template <int KS, int CIN, int CT, int TH, class Epi, bool SPLITK = false>
+// GROUPED (EigenPlaces' deep layers in a batch that fills the chip with images): ONE workgroup walks the k = p.flags chunk groups of the
+// split-K form in ascending z.  Each group is summed into a fresh accumulator and then added to a running fp32 total in the order of
+// k_ep_splitk_finish (total = acc_0; total += acc_z), so the bits are those of the split-K pair while the partial sums never leave the
+// registers; the prefetch pipeline runs straight across the group boundaries.  false: the code is exactly what it was.
+template <int KS, int CIN, int CT, int TH, class Epi, bool SPLITK = false, bool GROUPED = false>
 __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs p) {
   constexpr int HALO = KS / 2, TW = 32, TWH = TW + KS - 1, THH = TH + KS - 1;
   constexpr int MT = CT / 32, NT = TH / 4, NCHUNK = CIN / 64;
@@ -57,6 +61,7 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs p) {
   constexpr int IN_UNITS = THH * TWH * 8, IN_IT = (IN_UNITS + 255) / 256;  // 16-byte units
   constexpr int W_UNITS = WSTAGE / 8, W_IT = (W_UNITS + 255) / 256;
   static_assert(TH % 4 == 0 && CT % 32 == 0 && CIN % 64 == 0, "tile shape");
+  static_assert(!(SPLITK && GROUPED), "one reduction form");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   _Float16* s_in = reinterpret_cast<_Float16*>(smem);
   _Float16* s_w = s_in + THH * TWH * kCP;
@@ -132,6 +137,10 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs p) {
     s_begin = (int)blockIdx.z * NCHUNK / (int)gridDim.z * KS;
     s_end = ((int)blockIdx.z + 1) * NCHUNK / (int)gridDim.z * KS;
   }
+  // GROUPED: the running total and the stage at which the current group ends (p.flags = k divides NCHUNK)
+  f16x_t tot[GROUPED ? MT : 1][GROUPED ? NT : 1];
+  const int g_len = GROUPED ? NCHUNK / p.flags * KS : 0;
+  int g_end = g_len;
   load_in(s_begin / KS);
   load_w(s_begin);
 #pragma unroll 1
@@ -162,8 +171,24 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs p) {
         }
       }
     }
+    if constexpr (GROUPED) {
+      if (s + 1 == g_end) {  // a group is complete: total = acc_0, then total += acc_z (plain fp32 adds, z ascending)
+        const bool first = g_end == g_len;
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+#pragma unroll
+          for (int n = 0; n < NT; ++n)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              tot[m][n][r] = first ? acc[m][n][r] : tot[m][n][r] + acc[m][n][r];
+              acc[m][n][r] = 0.f;
+            }
+        g_end += g_len;
+      }
+    }
   }
-  Epi::template run<MT, NT>(p, acc, b, y0 + wave * NT, x0 + j, cb * CT, hh);
+  if constexpr (GROUPED) Epi::template run<MT, NT>(p, tot, b, y0 + wave * NT, x0 + j, cb * CT, hh);
+  else Epi::template run<MT, NT>(p, acc, b, y0 + wave * NT, x0 + j, cb * CT, hh);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -240,14 +265,14 @@ struct EpiF32 {
   }
 };
 
-// split-K partial sums: raw fp32 accumulators -> ws[z][pixel][cout] (DECIM: only the even (y, x) pixels, at (y / 2, x / 2)); bias, residual
+// split-K partial sums: raw fp32 accumulators -> ws[z][image][pixel][cout] (DECIM: only the even (y, x) pixels, at (y / 2, x / 2)); bias, residual
 // and activation are applied by the kernel that adds the gridDim.z partials (ep_kernels.hip: k_ep_splitk_finish)
 template <bool DECIM>
 struct EpiPartial {
   template <int MT, int NT>
   static __device__ __forceinline__ void run(const IgemmArgs& p, f16x_t (&acc)[MT][NT], int b, int yb, int x, int cb0, int hh) {
     const int Ho = DECIM ? (p.H + 1) >> 1 : p.H, Wo = DECIM ? (p.W + 1) >> 1 : p.W;
-    float* out = static_cast<float*>(p.out0) + (size_t)blockIdx.z * Ho * Wo * p.ostride;
+    float* out = static_cast<float*>(p.out0) + ((size_t)blockIdx.z * p.B + b) * Ho * Wo * p.ostride;
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -287,7 +312,7 @@ inline hipError_t launch_igemm(const IgemmArgs& a, int cout_pad, hipStream_t str
   hipLaunchKernelGGL(kern, grid, dim3(256), smem, stream, a);
   return hipGetLastError();
 }
-// split-K launch: grid.z = ksplit (a divisor of CIN / 64); B = 1
+// split-K launch: grid.z = ksplit (a divisor of CIN / 64)
 template <int KS, int CIN, int CT, int TH, class Epi>
 inline hipError_t launch_igemm_splitk(const IgemmArgs& a, int cout_pad, int ksplit, hipStream_t stream) {
   constexpr size_t smem = igemm_smem_bytes<KS, CIN, CT, TH>();
@@ -300,6 +325,23 @@ inline hipError_t launch_igemm_splitk(const IgemmArgs& a, int cout_pad, int kspl
   }
   const int tiles_x = (a.W + 31) / 32, tiles_y = (a.H + TH - 1) / TH;
   dim3 grid(a.B * tiles_x * tiles_y, (cout_pad + CT - 1) / CT, ksplit);
+  hipLaunchKernelGGL(kern, grid, dim3(256), smem, stream, a);
+  return hipGetLastError();
+}
+// grouped launch: the grid of launch_igemm, a.flags = the number of chunk groups (a divisor of CIN / 64)
+template <int KS, int CIN, int CT, int TH, class Epi>
+inline hipError_t launch_igemm_grouped(const IgemmArgs& a, int cout_pad, hipStream_t stream) {
+  constexpr size_t smem = igemm_smem_bytes<KS, CIN, CT, TH>();
+  static bool attr_set = false;
+  auto kern = igemm_kernel<KS, CIN, CT, TH, Epi, false, true>;
+  if (a.flags < 1 || (CIN / 64) % a.flags) return hipErrorInvalidValue;
+  if (!attr_set) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    if (e != hipSuccess) return e;
+    attr_set = true;
+  }
+  const int tiles_x = (a.W + 31) / 32, tiles_y = (a.H + TH - 1) / TH;
+  dim3 grid(a.B * tiles_x * tiles_y, (cout_pad + CT - 1) / CT);
   hipLaunchKernelGGL(kern, grid, dim3(256), smem, stream, a);
   return hipGetLastError();
 }

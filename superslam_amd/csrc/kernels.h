@@ -137,16 +137,26 @@ hipError_t sp_conv1x1_f32(const ConvW& w, const _Float16* in, float* out, int os
 hipError_t ep_conv(const ConvW& w, const _Float16* in, _Float16* out, const _Float16* res, int H, int W, bool relu, bool decim,
                    hipStream_t s, float* ws = nullptr, size_t ws_bytes = 0);
 size_t ep_splitk_workspace_bytes(int in_h, int in_w);
-void launch_ep_resize_norm(const uint8_t* src, int stride, int ch, const int* tab, int out_w, int out_h, float* out, hipStream_t s);
+// a batch of B images (maps [B][H][W][c]): per deep layer the single-image split k, run as batched split-K or as the grouped kernel
+enum EpBatchForm { kEpDirect = 0, kEpSplit = 1, kEpGrouped = 2 };
+struct EpBatchPlan { int form, k, th; };
+EpBatchPlan ep_batch_plan(int ks, int cin, int cout, int cout_pad, int H, int W, bool decim, int batch, size_t ws1_bytes);
+size_t ep_batch_workspace_bytes(int in_h, int in_w, int batch);
+// ws_bytes: the batch workspace really held (too small for a split layer: hipErrorInvalidValue); ws1_bytes: ep_splitk_workspace_bytes of the engine
+hipError_t ep_conv_batch(const ConvW& w, const _Float16* in, _Float16* out, const _Float16* res, int H, int W, bool relu, bool decim, int B,
+                         hipStream_t s, float* ws, size_t ws_bytes, size_t ws1_bytes);
+// B images image_stride bytes apart -> [B][3][out_h][out_w]
+void launch_ep_resize_norm(const uint8_t* src, int stride, int ch, const int* tab, int out_w, int out_h, float* out, hipStream_t s, int B = 1,
+                           long long image_stride = 0);
 void launch_ep_im2col(const float* x, int H, int W, int Ho, int Wo, _Float16* out, hipStream_t s);
 void launch_ep_maxpool(const _Float16* in, int H, int W, int Ho, int Wo, _Float16* out, hipStream_t s);
 // fused stem + ReLU + max-pool (round 6): wfrag = [2][11][64][8] fp16 A fragments (k = (c, ky, kx padded to 8)), bias fp32 [64]
 void launch_ep_stem_pool(const float* x, int H, int W, int Ho, int Wo, int Hp, int Wp, const _Float16* wfrag, const float* bias, _Float16* out,
-                         hipStream_t s);
+                         hipStream_t s, int B = 1);
 int ep_tail_pool_wgs(int npix);   // workgroups of the tail's pooling kernel = rows of partial sums it writes
 size_t ep_tail_ws_floats();   // the tail's workspace: partial GeM sums of up to 32 workgroups + the [512] pre-normalisation outputs
 void launch_ep_tail(const _Float16* feat, int npix, float p, const float* wt, const float* bias, float* ws, int* counters, float* out,
-                    hipStream_t s);
+                    hipStream_t s, int B = 1, int slice = 0, int out_stride = 512);
 
 // ---- lg_kernels.hip ----
 struct LgDims {
