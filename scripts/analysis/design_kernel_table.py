@@ -35,10 +35,10 @@ for key, name, work, design in ROWS:
     per = "" if not key.startswith("lg_") else " per launch"
     joule = f", **{e['joules_per_launch']:.3f} J** at {e['avg_W']:.0f} W / {e['sclk_MHz']:.0f} MHz" if e.get("joules_per_launch") else ""
     print(f"| {name} | {bound} | {work} | {e['launch_ms'] * 1e3:.0f} µs{per}, {e['achieved']:.0f} TFLOP/s = **{e['frac']:.3f}**{extra}{joule} | {design} |")
-HB = [("k_convpb_stream", "`k_convpb_stream` convPb 1×1 256 → 65 (`sp_convs.hip`)", "streaming kernel, nothing staged through LDS: `v_mfma_f32_16x16x32_f16` with pixels as N, weights in registers, fp32 logits in 68-float rows"),
+HB = [("k_convpb_stream", "`k_convpb_stream` convPb 1×1 256 → 65 (`sp_convs.hip`)", "streaming kernel: `v_mfma_f32_16x16x32_f16` with pixels as N, weights in registers; the 16 × 68 fp32 logits of a tile go through a wave-private LDS patch and leave as lane-linear 16-byte stores (34 whole 128-B lines per tile), padding floats 65..67 written as zeros"),
       ("k_nms_tile", "`k_nms_tile` softmax + depth-to-space + 9×9 NMS + threshold + compaction (`sp_kernels.hip`)", "persistent over tiles, separable max in LDS, candidates compacted with one LDS atomic per wave; round 6: XCD-aware tile order - neighbouring tiles run on ONE XCD, the one-cell halo ring is an L2 hit (590 → 332 MB per launch, 258 → 153 µs isolated)"),
       ("k_topk", "`k_topk` (one workgroup per image)", "register-cached MSB radix select with early exit + barrier-free rank sort; writes keypoints and cells"),
-      ("k_desc_head_sparse", "`k_desc_head_sparse` convDa + convDb + normalise ×2 at the keypoints (`sp_convs.hip`)", "3×3×128 patches gathered as nine 256-B rows; same k order as the dense kernels → bit-identical rows")]
+      ("k_desc_head_sparse", "`k_desc_head_sparse_2wg` convDa + convDb + normalise ×2 at the keypoints (`sp_convs.hip`)", "3×3×128 patches gathered as nine 256-B rows, one 32-channel quarter at a time by LDS-DMA through a per-image buffer resource into two buffers; 78 KB of LDS and 126 VGPRs → two workgroups per CU; same k order as the dense kernels → bit-identical rows")]
 for key, name, design in HB:
     e = hb[key]
     joule = f", {e['joules_per_launch']:.3f} J at {e['avg_W']:.0f} W" if e.get("joules_per_launch") else ""

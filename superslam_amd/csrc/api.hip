@@ -1075,6 +1075,28 @@ extern "C" int sship_sp_debug_activation(sship_sp* sp, int layer, void* out_host
   SSHIP_HIP_CHECK(hipMemcpy(out_host, bufs[layer]->p, bytes, hipMemcpyDeviceToHost));
   return SSHIP_OK;
 }
+// Test-only hooks, exported but NOT part of include/sship.h (tests/_tail_ab.py binds them by name; the product never calls them): the two
+// kernels behind convPa alone, with this handle's weights on the caller's device buffers, device-synchronising.
+//   sship_sp_debug_convpb:    convPb on `pixels` rows of 256 fp16 -> `pixels` rows of 68 fp32 (65 logits, 3 zeros)
+//   sship_sp_debug_desc_head: the nearest-cell descriptor head on a conv4b map a4b [batch][Hc][Wc][128] fp16 at the cells cell_h / cell_w
+//                             [batch][max_kp] (counts n_dev [batch]) -> desc [batch][max_kp][256] fp16; rows past an image's count are left as they are
+extern "C" int sship_sp_debug_convpb(sship_sp* sp, const void* in_fp16_dev, int pixels, float* logits_dev) {
+  bind_thread();
+  if (!sp || !in_fp16_dev || !logits_dev || pixels <= 0) return fail(SSHIP_ERR_INVALID, "sp_debug_convpb: bad arguments");
+  SSHIP_HIP_CHECK(sp_conv1x1_f32(sp->cPb, static_cast<const _Float16*>(in_fp16_dev), logits_dev, kLogitStride, 1, 1, pixels, sp->stream));
+  SSHIP_HIP_CHECK(hipStreamSynchronize(sp->stream));
+  return SSHIP_OK;
+}
+extern "C" int sship_sp_debug_desc_head(sship_sp* sp, const void* a4b_fp16_dev, int batch, int Hc, int Wc, const int* cell_h_dev,
+                                        const int* cell_w_dev, const int* n_dev, int max_kp, void* desc_fp16_dev) {
+  bind_thread();
+  if (!sp || !a4b_fp16_dev || !cell_h_dev || !cell_w_dev || !n_dev || !desc_fp16_dev || batch <= 0 || Hc <= 0 || Wc <= 0 || max_kp <= 0)
+    return fail(SSHIP_ERR_INVALID, "sp_debug_desc_head: bad arguments");
+  SSHIP_HIP_CHECK(launch_desc_head_sparse(sp->cDa, sp->cDb32, static_cast<const _Float16*>(a4b_fp16_dev), Hc, Wc, cell_h_dev, cell_w_dev, n_dev,
+                                          max_kp, batch, static_cast<_Float16*>(desc_fp16_dev), (size_t)max_kp * 256, sp->stream));
+  SSHIP_HIP_CHECK(hipStreamSynchronize(sp->stream));
+  return SSHIP_OK;
+}
 extern "C" sship_pool* sship_sp_pool(sship_sp* sp) {
   bind_thread(); return sp ? sp->pool : nullptr; }
 extern "C" int sship_sp_max_keypoints(const sship_sp* sp) { return sp ? sp->cfg.max_keypoints : 0; }
