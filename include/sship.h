@@ -363,6 +363,41 @@ int sship_lg_prune_counts(sship_lg* lg, int pair, int32_t* prune0, int n0, int32
 enum { SSHIP_LG_DEBUG_X = 0, SSHIP_LG_DEBUG_SIM = 1, SSHIP_LG_DEBUG_KPTS = 2, SSHIP_LG_DEBUG_ROPE = 3, SSHIP_LG_DEBUG_IND = 4 };
 int sship_lg_debug_set_layers(sship_lg* lg, int n_layers);
 int sship_lg_debug_read(sship_lg* lg, int what, int index, int rows, int cols, float* out);
+/* Test-only: per-stage capture of the matcher (tests/test_gpu_lg_stages.py judges every launch from the inputs it read).  The residual
+ * stream is updated in place and q / k / v^T / ctx are overwritten by every block, so nothing but the last state can be read after a call
+ * unless it was copied aside while the call ran.
+ * sship_lg_debug_capture(lg, pairs, count): count in 0 .. 8 pair indices of later calls; count = 0 (the default) turns capture off, and off
+ *   costs one host branch per stage: no allocation, no launch, and no kernel knows about it.  On, every later match call of the handle (the
+ *   batch-device and the single-pair entries alike) enqueues, right after the launch that produces a stage and on the stream that ran it (on
+ *   the two-stream path each half copies its own pairs on its own stream), a device-to-device copy of that stage's slice of every listed pair
+ *   that the call holds.  matches0 / mscores0 keep their bits.  A call with adaptive depth or adaptive width on while capture is on returns
+ *   SSHIP_ERR_INVALID.  Negative or repeated pair indices -> SSHIP_ERR_INVALID.  Switching forgets what was captured.
+ * sship_lg_debug_stage(lg, slot, layer, stage, out, floats): stage `stage` of layer `layer` (0 .. 8) of the pair listed at position `slot`,
+ *   from the LAST call, as fp32 in natural order, device-synchronising: out[2][NP][256] (set 0, set 1 of the pair; NP = the handle's padded
+ *   sequence length, max_keypoints rounded up to 32), out[2][NP] for LOGSIG; `floats` must be exactly that size.  Rows past a sequence's
+ *   length are padding (whatever the buffers held).  SSHIP_ERR_INVALID for a stage, layer or slot that does not exist, for a slot whose pair
+ *   the last call did not hold, and while capture is off or no call has run since it was switched on.
+ * Stages (per layer, in launch order; `s` the softmax scale folded into the weights on the host, L = log2 e):
+ *    0 X_IN    residual stream entering the layer (layer 0: the fp16 descriptors, zero rows for padding)
+ *    1 Q_S     SelfBlock q [head h = c / 64][d = c % 64]: (Wq x + bq) * (L / 8), then rotary; the kernel stores it in MFMA B-fragment order
+ *              [seq][h][token / 32][d / 16][lane = ((d % 16) / 8) * 32 + token % 32][d % 8], un-permuted here
+ *    2 K_S     SelfBlock k, rotary, no scale; stored like Q_S
+ *    3 V_S     SelfBlock v (no rotary, no scale); the kernel stores V^T in the PV A-fragment order
+ *              [seq][h][token / 32][kk = (token % 32) / 16][d / 32][lane = hh * 32 + d % 32][e], r = token % 16, hh = (r % 8) / 4,
+ *              e = r % 4 + 4 (r / 8), un-permuted here
+ *    4 CTX_S   self-attention output softmax(q k^T) v per head, channels [h][d] (the output projection is folded into ffn.0)
+ *    5 X_MID   residual stream after the SelfBlock FFN
+ *    6 QK_C    CrossBlock to_qk(x) * (64^-1/4 * sqrt(L)) (shared by both directions, no rotary); stored like Q_S
+ *    7 V_C     CrossBlock to_v(x); stored like V_S
+ *    8 CTX_C   cross-attention output (sequence s attends to its partner s ^ 1)
+ *    9 X_OUT   residual stream after the CrossBlock FFN
+ *   10 MD      layer 8 only: final_proj(x) * 256^-1/4, fp16 [NP][256]
+ *   11 LOGSIG  layer 8 only: logsigmoid(matchability(x)), fp32 [NP] */
+enum { SSHIP_LG_STAGE_X_IN = 0, SSHIP_LG_STAGE_Q_S = 1, SSHIP_LG_STAGE_K_S = 2, SSHIP_LG_STAGE_V_S = 3, SSHIP_LG_STAGE_CTX_S = 4,
+       SSHIP_LG_STAGE_X_MID = 5, SSHIP_LG_STAGE_QK_C = 6, SSHIP_LG_STAGE_V_C = 7, SSHIP_LG_STAGE_CTX_C = 8, SSHIP_LG_STAGE_X_OUT = 9,
+       SSHIP_LG_STAGE_MD = 10, SSHIP_LG_STAGE_LOGSIG = 11 };
+int sship_lg_debug_capture(sship_lg* lg, const int* pairs, int count);
+int sship_lg_debug_stage(sship_lg* lg, int slot, int layer, int stage, float* out, unsigned long long floats);
 /* Test-only: copy one activation of the extractor's LAST call to the host, raw (channels-last [batch][h_l][w_l][c_l]), device-synchronising.
  * layer: 1 conv1b (+pool), 2 conv2a, 3 conv2b (+pool), 4 conv3a, 5 conv3b (+pool), 6 conv4a, 7 conv4b (the ids of sship_sp_bench_layer), all fp16;
  * and the heads: 8 convPa, fp16 [B,Hc,Wc,256]; 9 convDa, the same layout, filled only by sship_sp_dense called with a descriptor grid;

@@ -1757,6 +1757,13 @@ struct sship_lg {
   static constexpr int kAux = 3;
   hipStream_t aux[kAux] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[kAux] = {nullptr, nullptr, nullptr};
+  // test-only stage capture (include/sship.h: sship_lg_debug_capture): cap_n = 0 is off.  cap: fp16 [slot][layer][stage 0..9][2 NP][256],
+  // cap_md: fp16 [slot][2 NP][256], cap_ls: f32 [slot][2 NP]; allocated when capture is first switched on
+  static constexpr int kCapSlots = 8, kCapStages = 10;
+  int cap_n = 0, cap_pairs[kCapSlots] = {0, 0, 0, 0, 0, 0, 0, 0};
+  bool captured = false;
+  int cap_last_pairs = 0;
+  DevBuf cap, cap_md, cap_ls;
 };
 
 // Adaptive depth state layout in sship_lg::dep (ints): cnt [P][8] | layers_run [P] | lens_live [2P] | live [P + kAux + 1] | tickets [kAux + 1]
@@ -1898,6 +1905,87 @@ extern "C" int sship_lg_debug_read(sship_lg* lg, int what, int index, int rows, 
   }
 }
 
+// Test-only stage capture (include/sship.h).  A pair's slice of every token buffer is contiguous: sequences 2p, 2p + 1 = 2 NP rows of 256.
+extern "C" int sship_lg_debug_capture(sship_lg* lg, const int* pairs, int count) {
+  bind_thread();
+  if (!lg || count < 0 || count > sship_lg::kCapSlots || (count > 0 && !pairs))
+    return fail(SSHIP_ERR_INVALID, "lg_debug_capture: null handle, or count outside 0..8");
+  for (int i = 0; i < count; ++i) {
+    if (pairs[i] < 0) return fail(SSHIP_ERR_INVALID, "lg_debug_capture: negative pair index");
+    for (int k = 0; k < i; ++k)
+      if (pairs[k] == pairs[i]) return fail(SSHIP_ERR_INVALID, "lg_debug_capture: repeated pair index");
+  }
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // copies of an earlier call may still be in flight
+  if (count > 0) {
+    const size_t pair_halfs = (size_t)2 * lg->NP * 256;
+    SSHIP_HIP_CHECK(lg->cap.ensure((size_t)sship_lg::kCapSlots * kLgLayers * sship_lg::kCapStages * pair_halfs * 2));
+    SSHIP_HIP_CHECK(lg->cap_md.ensure((size_t)sship_lg::kCapSlots * pair_halfs * 2));
+    SSHIP_HIP_CHECK(lg->cap_ls.ensure((size_t)sship_lg::kCapSlots * 2 * lg->NP * 4));
+  }
+  for (int i = 0; i < count; ++i) lg->cap_pairs[i] = pairs[i];
+  lg->cap_n = count;
+  lg->captured = false;
+  return SSHIP_OK;
+}
+// The inverses of the fragment orders the projections store in, written from the consumer's side (what k_lg_attention's operand loads
+// expect of a 32-token tile of 2048 halfs), not from the epilogues that write them:
+//   Q / K  B fragment of K-step ks: lane (token j = lane % 32, half hh = lane / 32) holds channels d = 16 ks + 8 hh + e, e = 0 .. 7
+//   V^T    A fragment of PV K-step kk, M-tile mt: lane (channel d = 32 mt + lane % 32, hh = lane / 32) holds the 8 keys of the swapped QK^T
+//          C-layout, key = 16 kk + 4 hh + (e % 4) + 8 (e / 4)
+static void lg_unpermute_qk(const uint16_t* src, int NP, float* out) {  // src [4 heads][NP / 32 tiles][2048] -> out [NP][256]
+  const int nt32 = NP / 32;
+  for (int h = 0; h < 4; ++h)
+    for (int t = 0; t < nt32; ++t)
+      for (int o = 0; o < 2048; ++o) {
+        const int ks = o / 512, lane = (o % 512) / 8, e = o % 8;
+        const int token = t * 32 + lane % 32, d = 16 * ks + 8 * (lane / 32) + e;
+        out[(size_t)token * 256 + h * 64 + d] = half_bits_to_float(src[((size_t)h * nt32 + t) * 2048 + o]);
+      }
+}
+static void lg_unpermute_vt(const uint16_t* src, int NP, float* out) {
+  const int nt32 = NP / 32;
+  for (int h = 0; h < 4; ++h)
+    for (int t = 0; t < nt32; ++t)
+      for (int o = 0; o < 2048; ++o) {
+        const int kk = o / 1024, mt = (o / 512) % 2, lane = (o % 512) / 8, e = o % 8;
+        const int token = t * 32 + 16 * kk + 4 * (lane / 32) + (e % 4) + 8 * (e / 4), d = 32 * mt + lane % 32;
+        out[(size_t)token * 256 + h * 64 + d] = half_bits_to_float(src[((size_t)h * nt32 + t) * 2048 + o]);
+      }
+}
+extern "C" int sship_lg_debug_stage(sship_lg* lg, int slot, int layer, int stage, float* out, unsigned long long floats) {
+  bind_thread();
+  if (!lg || !out) return fail(SSHIP_ERR_INVALID, "lg_debug_stage: null argument");
+  if (lg->cap_n == 0 || !lg->captured) return fail(SSHIP_ERR_INVALID, "lg_debug_stage: capture is off or no call has run since it was switched on");
+  if (slot < 0 || slot >= lg->cap_n || lg->cap_pairs[slot] >= lg->cap_last_pairs)
+    return fail(SSHIP_ERR_INVALID, "lg_debug_stage: no such slot, or the last call did not hold its pair");
+  if (layer < 0 || layer >= kLgLayers || stage < 0 || stage > SSHIP_LG_STAGE_LOGSIG || (stage >= SSHIP_LG_STAGE_MD && layer != kLgLayers - 1))
+    return fail(SSHIP_ERR_INVALID, "lg_debug_stage: no such layer / stage");
+  const int NP = lg->NP;
+  const size_t pair_halfs = (size_t)2 * NP * 256;
+  if (floats != (stage == SSHIP_LG_STAGE_LOGSIG ? (size_t)2 * NP : pair_halfs)) return fail(SSHIP_ERR_INVALID, "lg_debug_stage: bad size");
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());
+  if (stage == SSHIP_LG_STAGE_LOGSIG) {
+    SSHIP_HIP_CHECK(hipMemcpy(out, lg->cap_ls.as<float>() + (size_t)slot * 2 * NP, (size_t)2 * NP * 4, hipMemcpyDeviceToHost));
+    return SSHIP_OK;
+  }
+  std::vector<uint16_t> tmp(pair_halfs);
+  const _Float16* src = stage == SSHIP_LG_STAGE_MD
+                            ? lg->cap_md.as<_Float16>() + (size_t)slot * pair_halfs
+                            : lg->cap.as<_Float16>() + (((size_t)slot * kLgLayers + layer) * sship_lg::kCapStages + stage) * pair_halfs;
+  SSHIP_HIP_CHECK(hipMemcpy(tmp.data(), src, pair_halfs * 2, hipMemcpyDeviceToHost));
+  const bool qk = stage == SSHIP_LG_STAGE_Q_S || stage == SSHIP_LG_STAGE_K_S || stage == SSHIP_LG_STAGE_QK_C;
+  const bool vt = stage == SSHIP_LG_STAGE_V_S || stage == SSHIP_LG_STAGE_V_C;
+  for (int seq = 0; seq < 2; ++seq) {
+    const uint16_t* s16 = tmp.data() + (size_t)seq * NP * 256;
+    float* o = out + (size_t)seq * NP * 256;
+    if (qk) lg_unpermute_qk(s16, NP, o);
+    else if (vt) lg_unpermute_vt(s16, NP, o);
+    else
+      for (size_t i = 0; i < (size_t)NP * 256; ++i) o[i] = half_bits_to_float(s16[i]);
+  }
+  return SSHIP_OK;
+}
+
 // the state of launch group `part` (pairs [p0, p0 + np))
 static LgDepth lg_depth_state(sship_lg* lg, int p0, int part) {
   const int P = lg->max_pairs;
@@ -2015,6 +2103,11 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
                 (dev_env("SUPERSLAM_HIP_ATTN") && std::string(dev_env("SUPERSLAM_HIP_ATTN")) == "res")))
     return fail(SSHIP_ERR_INVALID, "lightglue: adaptive width is not supported by the 16-wave FFN or the LDS-resident-key attention");
 #endif
+  if (lg->cap_n) {  // test-only stage capture (sship_lg_debug_capture)
+    if (adaptive || width) return fail(SSHIP_ERR_INVALID, "lightglue: stage capture is not supported with adaptive depth or adaptive width");
+    lg->captured = true;
+    lg->cap_last_pairs = pairs;
+  }
   lg->last_adaptive = adaptive || width;  // layers_run comes from the device in both modes
   lg->last_width = width;
   lg->last_layers = lg->debug_layers;
@@ -2032,6 +2125,24 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
     const int* ls = lens + 2 * p0;
     if (adaptive || width) launch_lg_depth_init(ls, np, dep, st);
     if (width) launch_lg_width_init(ls, lg->NP, np, wd, st);
+    // test-only stage capture: the slices of the listed pairs of this launch group, copied on this group's stream right after the launch
+    // that produced them (`buf` is the whole-call buffer; a pair's slice is contiguous)
+    const size_t pair_halfs = (size_t)2 * lg->NP * 256;
+    // (short names: SSHIP_HIP_CHECK spells its expression into the error text, and the shipped library holds no SSHIP_* name but the documented ones)
+    constexpr int kCap_X_IN = SSHIP_LG_STAGE_X_IN, kCap_Q_S = SSHIP_LG_STAGE_Q_S, kCap_K_S = SSHIP_LG_STAGE_K_S, kCap_V_S = SSHIP_LG_STAGE_V_S,
+                  kCap_CTX_S = SSHIP_LG_STAGE_CTX_S, kCap_X_MID = SSHIP_LG_STAGE_X_MID, kCap_QK_C = SSHIP_LG_STAGE_QK_C,
+                  kCap_V_C = SSHIP_LG_STAGE_V_C, kCap_CTX_C = SSHIP_LG_STAGE_CTX_C, kCap_X_OUT = SSHIP_LG_STAGE_X_OUT, kCap_MD = SSHIP_LG_STAGE_MD;
+    auto cap = [&](int layer, int stage, const _Float16* buf) -> hipError_t {
+      for (int c = 0; c < lg->cap_n; ++c) {
+        const int p = lg->cap_pairs[c];
+        if (p < p0 || p >= p0 + np) continue;
+        _Float16* dst = stage == SSHIP_LG_STAGE_MD
+                            ? lg->cap_md.as<_Float16>() + (size_t)c * pair_halfs
+                            : lg->cap.as<_Float16>() + (((size_t)c * kLgLayers + layer) * sship_lg::kCapStages + stage) * pair_halfs;
+        if (hipError_t e = hipMemcpyAsync(dst, buf + (size_t)p * pair_halfs, pair_halfs * 2, hipMemcpyDeviceToDevice, st)) return e;
+      }
+      return hipSuccess;
+    };
     const int tile_tokens = lg_ffn_tile_tokens(ds.S * ds.NP);
     // what each FFN launch streams (w0, w3, the fused projection): handed to the launch BEFORE it as a prefetch hint (latency mode)
     auto self_w = [&](int i, const ConvW** o) { o[0] = &w->ffn0_s[i]; o[1] = &w->ffn3_s[i]; o[2] = &w->cqkv_t[i]; };
@@ -2050,14 +2161,27 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
       const int* la = (adaptive || width) && i > 0 ? dep.lens_live : ls;
       const int* live = i > 0 ? (width ? wd.tiles : adaptive ? dep.live : nullptr) : nullptr;
       const int lm = width ? 2 : 1;
+      if (lg->cap_n) {  // what the previous launch (the first projection, or layer i - 1's CrossBlock FFN) left for this layer
+        SSHIP_HIP_CHECK(cap(i, kCap_X_IN, x));
+        SSHIP_HIP_CHECK(cap(i, kCap_Q_S, q));
+        SSHIP_HIP_CHECK(cap(i, kCap_K_S, k));
+        SSHIP_HIP_CHECK(cap(i, kCap_V_S, vt));
+      }
       // SelfBlock (both images of every pair in one launch); its FFN also emits CrossBlock's [to_qk | to_v]
       launch_lg_attention(qs, ks, vs, la, ds, false, cs, st, shared_gpu);
+      if (lg->cap_n) SSHIP_HIP_CHECK(cap(i, kCap_CTX_S, ctx));
       cross_w(i, pf);
       launch_lg_ffn(w->ffn0_s[i], w->ffn3_s[i], w->ln_g_s[i], w->ln_b_s[i], cs, xs, ds, &w->cqkv_t[i], true, /*rope_segs=*/0,
                     /*t_seg=*/1, rs, qs, ks, vs, nullptr, nullptr, 0.f, nullptr, st, pf, live, lm);
+      if (lg->cap_n) {
+        SSHIP_HIP_CHECK(cap(i, kCap_X_MID, x));
+        SSHIP_HIP_CHECK(cap(i, kCap_QK_C, q));
+        SSHIP_HIP_CHECK(cap(i, kCap_V_C, vt));
+      }
       // CrossBlock (qk shared by both directions; sequence s attends to s^1); its FFN emits the next layer's Wqkv,
       // or final_proj + matchability after the last layer
       launch_lg_attention(qs, qs, vs, la, ds, true, cs, st, shared_gpu);
+      if (lg->cap_n) SSHIP_HIP_CHECK(cap(i, kCap_CTX_C, ctx));
       if (i + 1 < kLgLayers) {
         self_w(i + 1, pf);
         launch_lg_ffn(w->ffn0_c[i], w->ffn3_c[i], w->ln_g_c[i], w->ln_b_c[i], cs, xs, ds, &w->qkv_t[i + 1], true, 2, 2, rs, qs, ks,
@@ -2076,6 +2200,18 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
       } else
         launch_lg_ffn(w->ffn0_c[i], w->ffn3_c[i], w->ln_g_c[i], w->ln_b_c[i], cs, xs, ds, &w->final_t, false, 0, 0, rs, qs, ks, vs,
                       lg->md.as<_Float16>() + tok * 256, w->match_w, w->match_b, lg->logsig.as<float>() + tok, st, nullptr, live, lm);
+      if (lg->cap_n) {
+        SSHIP_HIP_CHECK(cap(i, kCap_X_OUT, x));
+        if (i + 1 == kLgLayers) {
+          SSHIP_HIP_CHECK(cap(i, kCap_MD, lg->md.as<_Float16>()));
+          for (int c = 0; c < lg->cap_n; ++c) {
+            const int p = lg->cap_pairs[c];
+            if (p < p0 || p >= p0 + np) continue;
+            SSHIP_HIP_CHECK(hipMemcpyAsync(lg->cap_ls.as<float>() + (size_t)c * 2 * lg->NP, lg->logsig.as<float>() + (size_t)p * 2 * lg->NP,
+                                           (size_t)2 * lg->NP * 4, hipMemcpyDeviceToDevice, st));
+          }
+        }
+      }
     }
     SSHIP_HIP_CHECK(hipGetLastError());
     return SSHIP_OK;

@@ -578,8 +578,9 @@ void launch_lg_attention(const _Float16* q, const _Float16* k, const _Float16* v
 //   * a workgroup (8 waves) owns 64 tokens; cat[x, ctx] (64 x 512 fp16) is staged once in LDS and is the MFMA
 //     B operand of ffn.0; wave w owns output rows [64w, 64w+64) and streams its packed A fragments straight
 //     from L2 (no sharing between waves -> no point in staging weights through LDS);
-//   * LayerNorm statistics: lane-local over the accumulators, lane^32 exchange, then across the 8 waves via LDS
-//     (two rounds: mean, then centred variance); exact-erf GELU on the accumulators;
+//   * LayerNorm statistics: lane-local over the accumulators, lane^32 exchange, then across the 8 waves via LDS, in ONE pass
+//     (sum and sum of squares together, var = max(q / 512 - mean^2, 0): it cancels when mean^2 >> var - tests/test_gpu_lg_stages.py
+//     case G puts numbers on that); erf-form GELU (lg_ffn.h: gelu2, within 7e-6 of y Phi(y)) on the accumulators;
 //   * the activated hidden tile overwrites the LDS input tile and is the B operand of ffn.3 (wave w owns 32 output
 //     rows); the residual add reads x from global in fp32 and writes it back in place.
 // Removes per block: 2 kernel launches and the [T,512] hidden round trip (write + read + write + read).

@@ -175,6 +175,22 @@ class LightGlue:
         _lib.check(_lib.lib().sship_lg_debug_read(self._h, what, index, rows, cols, out.ctypes.data))
         return out
 
+    # per-stage capture (include/sship.h sship_lg_debug_capture / sship_lg_debug_stage): stage ids as in the header
+    STAGES = ("x_in", "q_s", "k_s", "v_s", "ctx_s", "x_mid", "qk_c", "v_c", "ctx_c", "x_out", "md", "logsig")
+
+    def debug_capture(self, pairs=()) -> None:
+        """Capture the stages of the listed pairs (at most 8) in every later call; an empty list turns capture off."""
+        a = np.ascontiguousarray(list(pairs), np.int32)
+        _lib.check(_lib.lib().sship_lg_debug_capture(self._h, a.ctypes.data if len(a) else None, len(a)))
+
+    def debug_stage(self, slot: int, layer: int, stage) -> np.ndarray:
+        """Stage `stage` (name or id) of layer `layer` of the pair captured in `slot`, last call: f32 [2, NP, 256] ([2, NP] for logsig)."""
+        st = self.STAGES.index(stage) if isinstance(stage, str) else int(stage)
+        npad = (self.max_keypoints + 31) // 32 * 32
+        out = np.zeros((2, npad) if st == 11 else (2, npad, 256), np.float32)
+        _lib.check(_lib.lib().sship_lg_debug_stage(self._h, int(slot), int(layer), st, out.ctypes.data, out.size))
+        return out
+
     def match_batch_device(self, kp, n, desc, matches0=None, mscores0=None, stream=None):
         """kp f32 [2P,K,3], n i32 [2P], desc f16 [2P,K,256] (torch CUDA) -> matches0 i32 [P,K], mscores0 f32 [P,K]."""
         import torch
