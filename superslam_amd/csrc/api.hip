@@ -913,7 +913,10 @@ static hipError_t sp_refine(sship_sp* sp, int B, int Hc, int Wc, float* kp, cons
   return hipGetLastError();
 }
 // heatmap softmax + NMS + threshold -> candidates -> top-k keypoints/cells (all on device).
-static int sp_select(sship_sp* sp, int B, int H, int W, float* scores_out, float* kp_out, int* n_out, hipStream_t s) {
+// The last three arguments are for sship_sp_debug_select alone (every product call leaves them null: its two launches get the arguments they
+// always got): other logits than sp->logits [B][Hc][Wc][kLogitStride], the pre-NMS softmax map [B][8Hc][8Wc], the candidate counts [B].
+static int sp_select(sship_sp* sp, int B, int H, int W, float* scores_out, float* kp_out, int* n_out, hipStream_t s,
+                     const float* logits = nullptr, float* raw_out = nullptr, int* n_cand_out = nullptr) {
   int H2, W2, H4, W4, Hc, Wc;
   sp_shapes(H, W, H2, W2, H4, W4, Hc, Wc);
   // The candidate counters are zeroed by k_topk once it has read them (a 5-us memset launch per call in latency mode otherwise);
@@ -924,10 +927,10 @@ static int sp_select(sship_sp* sp, int B, int H, int W, float* scores_out, float
     SSHIP_HIP_CHECK(hipMemsetAsync(sp->cand_count.p, 0, (size_t)B * 4, s));
   sp->cand_zero_ptr = sp->cand_count.p; sp->cand_zero_n = 0; sp->cand_zero_stream = s;
   NmsArgs a{};
-  a.logits = sp->logits.as<float>(); a.ls = kLogitStride; a.B = B; a.H = Hc * 8; a.W = Wc * 8;
+  a.logits = logits ? logits : sp->logits.as<float>(); a.ls = kLogitStride; a.B = B; a.H = Hc * 8; a.W = Wc * 8;
   a.radius = sp->cfg.nms_radius; a.thr_f = sp->thr_f; a.border = sp->cfg.remove_borders;
   a.cand = sp->cand.as<unsigned long long>(); a.cand_count = sp->cand_count.as<int>(); a.cap = sp->cap;
-  a.scores_out = scores_out;
+  a.scores_out = scores_out; a.scores_raw_out = raw_out;
   launch_nms_tile(0, a, s);
   g_timer.mark_fine("sp_extract_stereo:select/nms_tile", s);
   TopkArgs t{};
@@ -936,7 +939,7 @@ static int sp_select(sship_sp* sp, int B, int H, int W, float* scores_out, float
   t.scale_x = static_cast<float>(W) / (Wc * 8);
   t.scale_y = static_cast<float>(H) / (Hc * 8);
   t.desc_h = Hc; t.desc_w = Wc; t.kp_xys = kp_out; t.cell_h = sp->cell_h.as<int>(); t.cell_w = sp->cell_w.as<int>();
-  t.n_out = n_out; t.n_cand_out = nullptr; t.reset_count = a.cand_count;
+  t.n_out = n_out; t.n_cand_out = n_cand_out; t.reset_count = a.cand_count;
   t.pix = sp_wants_pix(sp) ? sp->pix.as<int>() : nullptr;
   launch_topk(t, B, s);
   SSHIP_HIP_CHECK(hipGetLastError());
@@ -1095,6 +1098,32 @@ extern "C" int sship_sp_debug_desc_head(sship_sp* sp, const void* a4b_fp16_dev, 
   SSHIP_HIP_CHECK(launch_desc_head_sparse(sp->cDa, sp->cDb32, static_cast<const _Float16*>(a4b_fp16_dev), Hc, Wc, cell_h_dev, cell_w_dev, n_dev,
                                           max_kp, batch, static_cast<_Float16*>(desc_fp16_dev), (size_t)max_kp * 256, sp->stream));
   SSHIP_HIP_CHECK(hipStreamSynchronize(sp->stream));
+  return SSHIP_OK;
+}
+//   sship_sp_debug_select:    the selection of an extraction - sp_select itself, with the handle's radius, threshold, border and max_keypoints - on
+//                             logits [batch][Hc][Wc][68] fp32 on the device, or (logits_dev NULL) on the ones the handle's last network call at
+//                             this batch and size left behind.  h, w: the image size (Hc = h / 8, Wc = w / 8).  kp [batch][max_kp][3], cells
+//                             [batch][max_kp] and counts [batch] as an extraction produces them (kp rows past an image's count are left as they are, cell
+//                             rows past it are the handle's buffers, copied whole), n_cand [batch] = candidates before the top-k.
+//                             raw / nms NULL: the NMS launch has exactly an extraction's arguments (candidates only, no map is written);
+//                             otherwise it also writes the softmax map before NMS and / or the map after it, [batch][8Hc][8Wc] fp32.
+extern "C" int sship_sp_debug_select(sship_sp* sp, const float* logits_dev, int batch, int h, int w, float* kp_dev, int* cell_h_dev,
+                                     int* cell_w_dev, int* n_dev, int* n_cand_dev, float* raw_dev, float* nms_dev) {
+  bind_thread();
+  if (!sp || !kp_dev || !n_dev || batch <= 0 || h < 8 || w < 8) return fail(SSHIP_ERR_INVALID, "sp_debug_select: bad arguments");
+  if (logits_dev) {
+    if (sp->kp_refinement == SSHIP_KP_SUBPIXEL) return fail(SSHIP_ERR_INVALID, "sp_debug_select: sub-pixel refinement reads the handle's own logits");
+    if (int rc = sp_ensure(sp, batch, h, w)) return rc;
+  } else if (!sp->logits.p || batch > sp->wsB || h != sp->wsH || w != sp->wsW) {
+    return fail(SSHIP_ERR_INVALID, "sp_debug_select: run the network at this shape first");
+  }
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the logits may come from any stream
+  hipStream_t s = sp->stream;
+  if (int rc = sp_select(sp, batch, h, w, nms_dev, kp_dev, n_dev, s, logits_dev, raw_dev, n_cand_dev)) return rc;
+  const size_t cells = (size_t)batch * sp->cfg.max_keypoints * sizeof(int);
+  if (cell_h_dev) SSHIP_HIP_CHECK(hipMemcpyAsync(cell_h_dev, sp->cell_h.p, cells, hipMemcpyDeviceToDevice, s));
+  if (cell_w_dev) SSHIP_HIP_CHECK(hipMemcpyAsync(cell_w_dev, sp->cell_w.p, cells, hipMemcpyDeviceToDevice, s));
+  SSHIP_HIP_CHECK(hipStreamSynchronize(s));
   return SSHIP_OK;
 }
 extern "C" sship_pool* sship_sp_pool(sship_sp* sp) {

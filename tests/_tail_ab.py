@@ -54,29 +54,50 @@ def desc_key(hc, wc, b, rot, mk):
     return "d_%dx%d_b%d_r%d_k%d" % (hc, wc, b, rot, mk)
 
 
+def desc_map(hc, wc, images=5):
+    """One conv4b-like map per size (ReLU output: non-negative, a third zeros), [images, hc, wc, 128] fp16."""
+    return np.maximum(np.random.default_rng(hc * wc).standard_normal((images, hc, wc, 128)).astype(np.float32) - 0.4, 0).astype(np.float16)
+
+
+def desc_cells(hc, wc, b, mk, counts, rot):
+    """(cell_h, cell_w) [b, mk] int32 of one case: cells_for per image, zeros past an image's count."""
+    rng = np.random.default_rng(1000 * hc + 10 * b + rot)
+    ch = np.zeros((b, mk), np.int32)
+    cw = np.zeros((b, mk), np.int32)
+    for i, n in enumerate(counts):
+        c = cells_for(hc, wc, n, rot + i, rng)
+        ch[i, :n] = [y for y, _ in c]
+        cw[i, :n] = [x for _, x in c]
+    return ch, cw
+
+
+def bind_desc_head(L):
+    L.sship_sp_debug_desc_head.restype = C.c_int
+    L.sship_sp_debug_desc_head.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+
+
+def run_desc_case(sp, L, dmap, hc, wc, b, mk, counts, ch, cw):
+    """One sship_sp_debug_desc_head call on a device map -> the descriptor rows as int16 [b, mk, 256] (DESC_FILL where nothing was written)."""
+    import torch
+
+    d = torch.full((b, mk, 256), DESC_FILL, dtype=torch.int16).cuda()
+    tch, tcw, tn = torch.from_numpy(ch).cuda(), torch.from_numpy(cw).cuda(), torch.tensor(counts, dtype=torch.int32).cuda()
+    torch.cuda.synchronize()
+    rc = L.sship_sp_debug_desc_head(sp._h, dmap.data_ptr(), b, hc, wc, tch.data_ptr(), tcw.data_ptr(), tn.data_ptr(), mk, d.data_ptr())
+    assert rc == 0, (rc, L.sship_last_error())
+    return d.cpu().numpy()
+
+
 def run_desc(sp, L, out):
     import torch
 
-    L.sship_sp_debug_desc_head.restype = C.c_int
-    L.sship_sp_debug_desc_head.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    bind_desc_head(L)
     maps = {}
     for hc, wc, b, mk, counts, rot in desc_cases():
-        rng = np.random.default_rng(1000 * hc + 10 * b + rot)
-        if (hc, wc) not in maps:  # one conv4b-like map per size (ReLU output: non-negative, a third zeros), 5 images
-            m = np.maximum(np.random.default_rng(hc * wc).standard_normal((5, hc, wc, 128)).astype(np.float32) - 0.4, 0).astype(np.float16)
-            maps[(hc, wc)] = torch.from_numpy(m).cuda()
-        ch = np.zeros((b, mk), np.int32)
-        cw = np.zeros((b, mk), np.int32)
-        for i, n in enumerate(counts):
-            c = cells_for(hc, wc, n, rot + i, rng)
-            ch[i, :n] = [y for y, _ in c]
-            cw[i, :n] = [x for _, x in c]
-        d = torch.full((b, mk, 256), DESC_FILL, dtype=torch.int16).cuda()
-        tch, tcw, tn = torch.from_numpy(ch).cuda(), torch.from_numpy(cw).cuda(), torch.tensor(counts, dtype=torch.int32).cuda()
-        torch.cuda.synchronize()
-        rc = L.sship_sp_debug_desc_head(sp._h, maps[(hc, wc)].data_ptr(), b, hc, wc, tch.data_ptr(), tcw.data_ptr(), tn.data_ptr(), mk, d.data_ptr())
-        assert rc == 0, (rc, L.sship_last_error())
-        out[desc_key(hc, wc, b, rot, mk)] = d.cpu().numpy()
+        if (hc, wc) not in maps:
+            maps[(hc, wc)] = torch.from_numpy(desc_map(hc, wc)).cuda()
+        ch, cw = desc_cells(hc, wc, b, mk, counts, rot)
+        out[desc_key(hc, wc, b, rot, mk)] = run_desc_case(sp, L, maps[(hc, wc)], hc, wc, b, mk, counts, ch, cw)
 
 
 def run_convpb(sp, L, out):
