@@ -1261,6 +1261,91 @@ int sship_stereo_search_host(const uint8_t* left, int left_stride, const uint8_t
                              uint8_t* has_depth_out, uint8_t* status, int64_t* cost);
 
 /* ------------------------------------------------------------------------------------------------
+ * Patch tracking - the keypoints of a keyframe (or of the previous frame) carried into a new image by a bounded 2-D patch search: the
+ * temporal twin of the stereo search.  With it a frame needs no network: track left to left, sship_stereo_search_batch_device at the
+ * tracked positions (unit_stride 1), sship_pose_obs_from_matches_batch_device, sship_ransac_* / sship_pose_*; the extractor and the
+ * matcher run on keyframes only.  No reference counterpart: StereoFrontEnd ties two frames by extracting both and matching them.  The rule
+ * is this library's own (the zero-mean SSD of the stereo stages over a 2-D box, a texture gate, a uniqueness gate and a forward-backward
+ * check in front of a parabola per axis) and is stated here in full; tests/_patch_track_ref.py restates this text.  All of it is integer
+ * arithmetic on u8 pixels up to two fp64 compares, two fp64 divisions, four fp64 additions and two roundings to fp32: the result does not
+ * depend on summation order, batch position or entry point.
+ *
+ * Image I0 of pair p is at imgs0_dev + p * image_stride0 (bytes) with rows of stride0 bytes, I1 at imgs1_dev + p * image_stride1 with
+ * rows of stride1 bytes; both are h x W u8.  An image stride of 2 * h * stride reads the left images of an L0, R0, L1, R1, ... batch, an
+ * image stride of 0 reads one image for every pair (a keyframe against many frames).  No alignment is required of any pointer or stride.
+ * kp_dev [units, max_keypoints, 3] f32 = (x, y, score) as an extractor writes it and n_dev [units] i32; pair p reads unit p * unit_stride
+ * (unit_stride 1 or 2).  The count n0 of pair p is n_dev[p * unit_stride] clamped to [0, max_keypoints] on the device.  pred_dev
+ * [pairs, max_keypoints, 3] f32 is optional: (px, py, .) of row i is where the search for keypoint i is centred in I1; NULL means
+ * (px, py) = (x, y).  pred_dev may be kp_out_dev: the output of one call seeds the next while the template stays the keyframe's.
+ * w = half_window, pw = 2w+1, N = pw^2, R = search_radius, u = uniqueness, mt = min_texture, fb = fb_check.  Keypoint i of pair p, in
+ * this order:
+ *   1. i >= n0: kp_out (0, 0, 0), matches0 -1, status NONE, cost -1; every entry of every output is written.
+ *   2. x, y, px or py not finite or outside [0, 16384): status BORDER.  Otherwise, in fp64 on the fp32 values, xa = floor(x + 0.5),
+ *      ya = floor(y + 0.5), xp = floor(px + 0.5), yp = floor(py + 0.5), and the status is BORDER unless the template lies inside I0:
+ *      xa-w >= 0, xa+w < W, ya-w >= 0 and ya+w < h.
+ *   3. The search box, clipped so that every candidate patch lies inside I1: lox = max(-R, w - xp), hix = min(R, W-1-w-xp),
+ *      loy = max(-R, w - yp), hiy = min(R, h-1-w-yp).  hix - lox + 1 < 3 or hiy - loy + 1 < 3: status RANGE.
+ *   4. Texture gate on the template A (the pixels I0[ya+j, xa+i], (j, i) in [-w, w]^2): T = N sum A^2 - (sum A)^2 in int64.  With mt > 0
+ *      and t = (double)mt (double)N:  (double)T < t t: status TEXTURE.
+ *   5. For dy = loy .. hiy, dx = lox .. hix over (j, i) in [-w, w]^2:  e = I0[ya+j, xa+i] - I1[yp+dy+j, xp+dx+i];  S1 = sum e,
+ *      S2 = sum e^2;  C(dx, dy) = N S2 - S1^2 in int64 - the stereo stages' cost.
+ *   6. The candidates are ordered by k = (dy - loy)(hix - lox + 1) + (dx - lox).  (dx*, dy*) = the candidate of the smallest k attaining
+ *      the minimum, cost = C(dx*, dy*).  dx* == lox, dx* == hix, dy* == loy or dy* == hiy: status EDGE.
+ *   7. With max_rms > 0 and t = (double)max_rms (double)N:  (double)cost > t t: status COST.
+ *   8. Uniqueness, with u > 0: C2 = min C(dx, dy) over the candidates with max(|dx - dx*|, |dy - dy*|) > 1.  If such a candidate exists
+ *      and 100 cost < (100 - u) C2 does NOT hold (int64): status AMBIGUOUS.
+ *   9. Forward-backward check, with fb >= 0: the template becomes the I1 patch at (xb, yb) = (xp + dx*, yp + dy*), and B(ex, ey) is the
+ *      same cost between it and the I0 patch at (xa + dx* - ex, ya + dy* - ey), for (ex, ey) in [-R, R]^2 clipped so that the patch lies
+ *      inside I0: elox = max(-R, xa + dx* - (W-1-w)), ehix = min(R, xa + dx* - w), and eloy, ehiy likewise with ya, dy* and h; the box
+ *      always contains e = d*.  Order and smallest-index minimiser (ex*, ey*) as in step 6, with k = (ey - eloy)(ehix - elox + 1) +
+ *      (ex - elox).  max(|ex* - dx*|, |ey* - dy*|) > fb: status FBCHECK.
+ *  10. Fit, per axis: Cm = C(dx*-1, dy*), Cp = C(dx*+1, dy*) for x, Cm = C(dx*, dy*-1), Cp = C(dx*, dy*+1) for y;
+ *      den = Cm + Cp - 2 cost (>= 1 on both axes: the left and the upper neighbour have a smaller k than the smallest minimiser),
+ *      delta = (double)(Cm - Cp) / (double)(2 den)  (|delta| <= 0.5),
+ *      x' = (float)(((double)x + (double)(xp - xa + dx*)) + delta_x), y' = (float)(((double)y + (double)(yp - ya + dy*)) + delta_y).
+ *      The template is centred on (xa, ya), not on (x, y), so a fractional keypoint keeps its fraction.
+ *      Status TRACKED: kp_out (x', y', the input's score bits), matches0 i.
+ *  11. Every status other than TRACKED and NONE writes kp_out (quiet NaN, quiet NaN, the input's score bits) and matches0 -1.  cost is
+ *      -1 for NONE, BORDER, RANGE and TEXTURE and C(dx*, dy*) otherwise.  A NaN row tracked again stays BORDER.
+ * kp_out_dev [pairs, max_keypoints, 3] f32 and matches0_dev [pairs, max_keypoints] i32 have the shape of an extractor's and a matcher's
+ * output for the new frame: sship_stereo_search_batch_device (unit_stride 1), sship_pose_obs_from_matches_batch_device and
+ * sship_ba_tracks_from_matches_batch_device take them unchanged.  n_out_dev [pairs] i32 receives n0; it is optional, as are status_dev
+ * [pairs, max_keypoints] u8 and cost_dev [pairs, max_keypoints] i64 (NULL = not wanted).  One launch, asynchronous on `stream`, no host
+ * synchronisation.  pairs >= 1, max_keypoints in [1, 4096], h, w in [1, 16384], stride0 and stride1 >= w, image strides >= 0,
+ * half_window in [1, 7], search_radius in [1, 16], uniqueness in [0, 99], fb_check in [-1, 16] (-1: no check), min_texture and max_rms
+ * not NaN (<= 0: off), unit_stride 1 or 2; anything else or a NULL required pointer is SSHIP_ERR_INVALID before any device is touched.
+ * ---------------------------------------------------------------------------------------------- */
+#define SSHIP_TRACK_STATUS_NONE 0
+#define SSHIP_TRACK_STATUS_TRACKED 1
+#define SSHIP_TRACK_STATUS_BORDER 2
+#define SSHIP_TRACK_STATUS_RANGE 3
+#define SSHIP_TRACK_STATUS_TEXTURE 4
+#define SSHIP_TRACK_STATUS_EDGE 5
+#define SSHIP_TRACK_STATUS_COST 6
+#define SSHIP_TRACK_STATUS_AMBIGUOUS 7
+#define SSHIP_TRACK_STATUS_FBCHECK 8
+typedef struct sship_patch_track_params {
+  int half_window;    /* w: the patch is (2w+1) x (2w+1) pixels; 1 .. 7, default 5 */
+  int search_radius;  /* R: displacements of up to R pixels per axis around the prediction are searched; 1 .. 16, default 8 */
+  int uniqueness;     /* u, percent: the best cost must be below (100 - u) % of the best one further than 1 px away; 0 .. 99, 0 is off; default 10 */
+  float min_texture;  /* texture gate on the standard deviation of the template in grey levels; <= 0 is off (default 0) */
+  float max_rms;      /* cost gate on the zero-mean RMS difference in grey levels; <= 0 is off (default 0) */
+  int fb_check;       /* largest accepted max(|ex* - dx*|, |ey* - dy*|) of the forward-backward check; -1 .. 16, -1 is off; default 1 */
+} sship_patch_track_params;
+int sship_patch_track_batch_device(const uint8_t* imgs0_dev, long long image_stride0, int stride0, const uint8_t* imgs1_dev,
+                                   long long image_stride1, int stride1, int pairs, int h, int w, const float* kp_dev, const int* n_dev,
+                                   int unit_stride, const float* pred_dev, int max_keypoints, const sship_patch_track_params* params,
+                                   float* kp_out_dev, int* n_out_dev, int32_t* matches0_dev, uint8_t* status_dev, int64_t* cost_dev,
+                                   void* stream);
+/* One pair from host arrays: img0 / img1 [h, stride* bytes] u8, keypoints[i * kp_stride + {0, 1}] = (x, y) with kp_stride >= 2 (where
+ * kp_stride >= 3 the third float is the score, else the score is 0), pred (optional) likewise with pred_stride >= 2, n in [0, 4096]
+ * (0: nothing is touched); kp_out [n, 3], matches0 [n]; status [n] and cost [n] are optional.  Staged through one device block, the same
+ * launch with pairs = 1: the same bits.  Synchronous. */
+int sship_patch_track_host(const uint8_t* img0, int stride0, const uint8_t* img1, int stride1, int h, int w, const float* keypoints,
+                           int kp_stride, const float* pred, int pred_stride, int n, const sship_patch_track_params* params, float* kp_out,
+                           int32_t* matches0, uint8_t* status, int64_t* cost);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused front-end step: what StereoFrontEnd::process asks of the two interfaces per frame
  * (src/StereoFrontEnd.cc:14,33): SuperPoint on L and R (one batch) + gather x2 + one LightGlue match,
  * for `pairs` stereo pairs at once, device-resident, no host synchronisation.  imgs_dev is

@@ -5,8 +5,8 @@ imports the CPU oracle; the HIP library is the only compute path.
 """
 from . import _lib  # noqa: F401
 from .eigenplaces import EigenPlaces  # noqa: F401
-from .frontend import (FrontEndBatch, process_stereo, rgbd_associate_batch, stereo_associate_batch, stereo_refine,  # noqa: F401
-                       stereo_refine_batch, stereo_search, stereo_search_batch)
+from .frontend import (FrontEndBatch, patch_track, patch_track_batch, patch_track_stereo_batch, process_stereo,  # noqa: F401
+                       rgbd_associate_batch, stereo_associate_batch, stereo_refine, stereo_refine_batch, stereo_search, stereo_search_batch)
 from .lightglue import LightGlue, LightGlueEngine, MatchResult  # noqa: F401
 from .nn_matcher import NNMatcher  # noqa: F401
 from .place_index import PlaceIndex  # noqa: F401
@@ -21,4 +21,5 @@ from .window_smoother import WindowSmoother, smooth_batch  # noqa: F401
 __all__ = ["SuperPoint", "LightGlue", "LightGlueEngine", "MatchResult", "Features", "DescriptorPool",
            "DeviceDescriptors", "FrontEndBatch", "process_stereo", "stereo_associate_batch", "EigenPlaces", "NNMatcher", "PlaceIndex", "PoseSolver",
            "track_batch", "RansacVerifier", "verify_batch", "WindowSmoother", "smooth_batch", "PoseGraph", "close_loops_batch", "Rectifier", "build_maps",
-           "rgbd_associate_batch", "stereo_refine_batch", "stereo_refine", "stereo_search_batch", "stereo_search"]
+           "rgbd_associate_batch", "stereo_refine_batch", "stereo_refine", "stereo_search_batch", "stereo_search",
+           "patch_track_batch", "patch_track", "patch_track_stereo_batch"]

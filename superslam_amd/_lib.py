@@ -82,6 +82,11 @@ class StereoSearchParams(C.Structure):
                 ("min_texture", C.c_float), ("max_rms", C.c_float), ("lr_check", C.c_int)]
 
 
+class PatchTrackParams(C.Structure):
+    _fields_ = [("half_window", C.c_int), ("search_radius", C.c_int), ("uniqueness", C.c_int), ("min_texture", C.c_float),
+                ("max_rms", C.c_float), ("fb_check", C.c_int)]
+
+
 _lib = None
 vp, ip, fp, dp = C.c_void_p, C.c_int, C.c_float, C.c_double
 _SIGS = {
@@ -242,6 +247,9 @@ _SIGS = {
     "sship_stereo_refine_host": (ip, [vp, ip, vp, ip, ip, ip, vp, vp, ip, C.POINTER(StereoRefineParams), vp, vp, vp, vp]),
     "sship_stereo_search_batch_device": (ip, [vp, ip, ip, ip, ip, vp, vp, ip, ip, C.POINTER(StereoSearchParams), vp, vp, vp, vp, vp]),
     "sship_stereo_search_host": (ip, [vp, ip, vp, ip, ip, ip, vp, ip, ip, C.POINTER(StereoSearchParams), vp, vp, vp, vp]),
+    "sship_patch_track_batch_device": (ip, [vp, C.c_longlong, ip, vp, C.c_longlong, ip, ip, ip, ip, vp, vp, ip, vp, ip,
+                                            C.POINTER(PatchTrackParams), vp, vp, vp, vp, vp, vp]),
+    "sship_patch_track_host": (ip, [vp, ip, vp, ip, ip, ip, vp, ip, vp, ip, ip, C.POINTER(PatchTrackParams), vp, vp, vp, vp]),
     "sship_desc_to_host": (ip, [vp, ip, ip, vp]),
     "sship_frontend_batch_device": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_bench_layer": (ip, [vp, ip, ip, ip, ip, ip, C.POINTER(fp), C.POINTER(C.c_double)]),

@@ -4160,6 +4160,85 @@ extern "C" int sship_stereo_search_host(const uint8_t* left, int left_stride, co
 }
 
 // ====================================================================================================
+// keypoint tracking by 2-D patch search (the rule is in include/sship.h)
+// ====================================================================================================
+// the checks both entries share; fills the kernel's constants
+static int track_check(int h, int w, int stride0, int stride1, const sship_patch_track_params* p, PatchTrackK* c, const char* who) {
+  if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, std::string(who) + ": h and w must be in [1, 16384]");
+  if (stride0 < w || stride1 < w) return fail(SSHIP_ERR_INVALID, std::string(who) + ": stride (bytes) must be >= w");
+  if (p->half_window < 1 || p->half_window > 7) return fail(SSHIP_ERR_INVALID, std::string(who) + ": half_window must be in [1, 7]");
+  if (p->search_radius < 1 || p->search_radius > 16) return fail(SSHIP_ERR_INVALID, std::string(who) + ": search_radius must be in [1, 16]");
+  if (p->uniqueness < 0 || p->uniqueness > 99) return fail(SSHIP_ERR_INVALID, std::string(who) + ": uniqueness must be in [0, 99]");
+  if (p->fb_check < -1 || p->fb_check > 16) return fail(SSHIP_ERR_INVALID, std::string(who) + ": fb_check must be in [-1, 16]");
+  if (std::isnan(p->min_texture) || std::isnan(p->max_rms)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": min_texture and max_rms must not be NaN");
+  const int pw = 2 * p->half_window + 1;
+  const double tt = (double)p->min_texture * (double)(pw * pw), tr = (double)p->max_rms * (double)(pw * pw);
+  c->tex = p->min_texture > 0.f ? 1 : 0;
+  c->tex2 = tt * tt;
+  c->gate = p->max_rms > 0.f ? 1 : 0;
+  c->gate2 = tr * tr;
+  c->half_window = p->half_window; c->radius = p->search_radius; c->uniqueness = p->uniqueness; c->fb = p->fb_check;
+  return SSHIP_OK;
+}
+extern "C" int sship_patch_track_batch_device(const uint8_t* imgs0, long long image_stride0, int stride0, const uint8_t* imgs1,
+                                              long long image_stride1, int stride1, int pairs, int h, int w, const float* kp, const int* n,
+                                              int unit_stride, const float* pred, int max_keypoints, const sship_patch_track_params* p,
+                                              float* kp_out, int* n_out, int32_t* matches0, uint8_t* status, int64_t* cost, void* stream) {
+  if (!imgs0 || !imgs1 || !kp || !n || !p || !kp_out || !matches0) return fail(SSHIP_ERR_INVALID, "patch_track_batch_device: null argument");
+  if (pairs <= 0 || max_keypoints <= 0 || max_keypoints > kMaxKp)
+    return fail(SSHIP_ERR_INVALID, "patch_track_batch_device: pairs must be positive and max_keypoints in [1, 4096]");
+  if (unit_stride != 1 && unit_stride != 2) return fail(SSHIP_ERR_INVALID, "patch_track_batch_device: unit_stride must be 1 or 2");
+  if (image_stride0 < 0 || image_stride1 < 0) return fail(SSHIP_ERR_INVALID, "patch_track_batch_device: image strides (bytes) must be >= 0");
+  PatchTrackK c;
+  if (int rc = track_check(h, w, stride0, stride1, p, &c, "patch_track_batch_device")) return rc;
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  launch_patch_track(imgs0, image_stride0, stride0, imgs1, image_stride1, stride1, pairs, h, w, kp, n, unit_stride, pred, max_keypoints, c, kp_out,
+                     n_out, matches0, status, reinterpret_cast<long long*>(cost), s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("patch_track", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_patch_track_host(const uint8_t* img0, int stride0, const uint8_t* img1, int stride1, int h, int w, const float* keypoints,
+                                      int kp_stride, const float* pred, int pred_stride, int n, const sship_patch_track_params* p, float* kp_out,
+                                      int32_t* matches0, uint8_t* status, int64_t* cost) {
+  if (!img0 || !img1 || !p) return fail(SSHIP_ERR_INVALID, "patch_track_host: null argument");
+  if (n < 0 || n > kMaxKp || kp_stride < 2 || (pred && pred_stride < 2))
+    return fail(SSHIP_ERR_INVALID, "patch_track_host: n must be in [0, 4096], kp_stride >= 2 and, with pred, pred_stride >= 2");
+  PatchTrackK c;
+  if (int rc = track_check(h, w, stride0, stride1, p, &c, "patch_track_host")) return rc;
+  if (n == 0) return SSHIP_OK;
+  if (!keypoints || !kp_out || !matches0) return fail(SSHIP_ERR_INVALID, "patch_track_host: null argument");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  // (x, y, score) rows: the score is the third float of a keypoint where kp_stride >= 3, else 0; its bits are handed on
+  std::vector<float> kp((size_t)n * 3, 0.f), pr(pred ? (size_t)n * 3 : 0, 0.f);
+  for (int i = 0; i < n; ++i) memcpy(&kp[3 * (size_t)i], keypoints + (size_t)i * kp_stride, (kp_stride >= 3 ? 3 : 2) * sizeof(float));
+  for (int i = 0; pred && i < n; ++i) memcpy(&pr[3 * (size_t)i], pred + (size_t)i * pred_stride, 2 * sizeof(float));
+  const size_t img = (size_t)h * w, kb = (size_t)n * 3 * sizeof(float);
+  StageLayout lay;   // one device block for the call: the two images packed to stride w, then the per-keypoint arrays
+  const size_t o_i0 = lay.add(2 * img), o_i1 = o_i0 + img, o_n = lay.add(sizeof(int)), o_kp = lay.add(kb), o_pr = lay.add(kb), o_out = lay.add(kb),
+               o_m = lay.add((size_t)n * sizeof(int32_t)), o_status = lay.add((size_t)n), o_cost = lay.add((size_t)n * sizeof(int64_t));
+  StageArena a;
+  SSHIP_HIP_CHECK(a.create(lay.end, 0, false));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_i0), (size_t)w, img0, (size_t)stride0, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_i1), (size_t)w, img1, (size_t)stride1, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<int>(o_n), &n, sizeof(int), hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<float>(o_kp), kp.data(), kb, hipMemcpyHostToDevice));
+  if (pred) { SSHIP_HIP_CHECK(hipMemcpy(a.dev<float>(o_pr), pr.data(), kb, hipMemcpyHostToDevice)); }
+  if (int rc = sship_patch_track_batch_device(a.dev<uint8_t>(o_i0), 0, w, a.dev<uint8_t>(o_i1), 0, w, 1, h, w, a.dev<float>(o_kp), a.dev<int>(o_n), 1,
+                                              pred ? a.dev<float>(o_pr) : nullptr, n, p, a.dev<float>(o_out), nullptr, a.dev<int32_t>(o_m),
+                                              a.dev<uint8_t>(o_status), a.dev<int64_t>(o_cost), nullptr)) return rc;
+  SSHIP_HIP_CHECK(hipMemcpy(kp_out, a.dev<float>(o_out), kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launch
+  SSHIP_HIP_CHECK(hipMemcpy(matches0, a.dev<int32_t>(o_m), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (status) { SSHIP_HIP_CHECK(hipMemcpy(status, a.dev<uint8_t>(o_status), (size_t)n, hipMemcpyDeviceToHost)); }
+  if (cost) { SSHIP_HIP_CHECK(hipMemcpy(cost, a.dev<int64_t>(o_cost), (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost)); }
+  return SSHIP_OK;
+}
+
+// ====================================================================================================
 // fused front-end step: SuperPoint(batch 2P) + select + gather + LightGlue(P)
 // ====================================================================================================
 extern "C" int sship_frontend_batch_device(sship_sp* sp, sship_lg* lg, const uint8_t* imgs, int pairs, int h, int w,

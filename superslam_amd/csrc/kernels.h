@@ -347,4 +347,13 @@ void launch_stereo_search(const uint8_t* imgs, int pairs, int h, int w, long lon
                           int max_kp, const StereoSearchK& c, float* stereo_out, uint8_t* has_depth_out, uint8_t* status, long long* cost,
                           hipStream_t s);
 
+// keypoint tracking by 2-D patch search (patch_track_kernels.hip).  tex2 = (min_texture * N)^2 and gate2 = (max_rms * N)^2, computed once on
+// the host; tex / gate = the gate is on; fb = fb_check.
+struct PatchTrackK { double tex2, gate2; int half_window, radius, uniqueness, fb, tex, gate; };
+// imgs0 / imgs1: image p at imgs + p * image_stride (bytes), rows of `stride` bytes; pair p reads kp / lens of unit p * unit_stride; pred
+// [pairs, max_kp, 3] may be null and may be kp_out; n_out / status / cost may be null
+void launch_patch_track(const uint8_t* imgs0, long long image_stride0, int stride0, const uint8_t* imgs1, long long image_stride1, int stride1,
+                        int pairs, int h, int w, const float* kp, const int* lens, int unit_stride, const float* pred, int max_kp,
+                        const PatchTrackK& c, float* kp_out, int* n_out, int* matches0, uint8_t* status, long long* cost, hipStream_t s);
+
 }  // namespace sship

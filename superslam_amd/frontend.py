@@ -336,6 +336,148 @@ def stereo_search(left: np.ndarray, right: np.ndarray, keypoints: np.ndarray, *,
     return (so, ho, status, cost) if return_status else (so, ho)
 
 
+# the status codes of sship_patch_track_*, by value
+TRACK_STATUS = ("none", "tracked", "border", "range", "texture", "edge", "cost", "ambiguous", "fbcheck")
+
+
+def patch_track_params(half_window: int = 5, search_radius: int = 8, uniqueness: int = 10, min_texture: float = 0.0, max_rms: float = 0.0,
+                       fb_check: int = 1):
+    """The library's sship_patch_track_params, checked as the library checks it."""
+    import math
+
+    ints = dict(half_window=half_window, search_radius=search_radius, uniqueness=uniqueness, fb_check=fb_check)
+    for name, v in ints.items():
+        if isinstance(v, bool) or int(v) != v:
+            raise ValueError(f"{name} must be an integer")
+    if not 1 <= int(half_window) <= 7:
+        raise ValueError("half_window must be in [1, 7]")
+    if not 1 <= int(search_radius) <= 16:
+        raise ValueError("search_radius must be in [1, 16]")
+    if not 0 <= int(uniqueness) <= 99:
+        raise ValueError("uniqueness must be in [0, 99]")
+    if not -1 <= int(fb_check) <= 16:
+        raise ValueError("fb_check must be in [-1, 16]")
+    if math.isnan(float(min_texture)) or math.isnan(float(max_rms)):
+        raise ValueError("min_texture and max_rms must not be NaN")
+    return _lib.PatchTrackParams(int(half_window), int(search_radius), int(uniqueness), float(min_texture), float(max_rms), int(fb_check))
+
+
+def _track_images(name, images, pairs):
+    """u8 [P, h, w] with unit stride along x, a row stride >= w and any image stride >= 0 (a view such as batch[0::2], or an expanded
+    [1, h, w] image): passed by its strides, never copied -> (h, w, row stride, image stride)"""
+    import torch
+
+    if images.dtype != torch.uint8 or images.dim() != 3 or int(images.shape[0]) != pairs:
+        raise ValueError(f"{name} must be uint8 [{pairs}, h, w]")
+    h, w = int(images.shape[1]), int(images.shape[2])
+    if not (1 <= h <= 16384 and 1 <= w <= 16384):
+        raise ValueError("h and w must be in [1, 16384]")
+    if (w > 1 and images.stride(2) != 1) or (h > 1 and images.stride(1) < w) or (pairs > 1 and images.stride(0) < 0):
+        raise ValueError(f"{name} must have unit stride along x, a row stride >= w and an image stride >= 0")
+    return h, w, int(images.stride(1)) if h > 1 else w, int(images.stride(0)) if pairs > 1 else 0
+
+
+def patch_track_batch(images0, images1, kp, n, pred=None, *, half_window: int = 5, search_radius: int = 8, uniqueness: int = 10,
+                      min_texture: float = 0.0, max_rms: float = 0.0, fb_check: int = 1, out=None, return_status: bool = False, stream=None):
+    """The keypoints of images0 carried into images1 by a bounded 2-D patch search (sship_patch_track_batch_device; the rule is in
+    include/sship.h): images0 / images1 u8 [P, h, w], strided views welcome (batch[0::2] reads the left images of an L0, R0, L1, R1, ...
+    batch; keyframe.expand(P, h, w) reads one image for every pair; rows may be strided, any alignment), kp f32 [U, K, 3] = (x, y, score)
+    and n i32 [U] as an extractor writes them, U = P or 2P (the units are then read at stride 2), pred f32 [P, K, 3] = where to centre each
+    search (None: at the keypoint; it may be out[0]) -> (kp1 f32 [P, K, 3] = (x', y', score) or (NaN, NaN, score), n1 i32 [P],
+    matches0 i32 [P, K] = the row itself or -1): an extractor's and a matcher's output for the new frame, taken unchanged by
+    stereo_search_batch, PoseSolver.obs_from_matches and the smoother's track gather.  out: a (kp1, n1, matches0) triple to write into.
+    return_status: also status u8 [P, K] (indices into TRACK_STATUS) and cost i64 [P, K] (C*, -1 where no search ran).  Asynchronous on
+    `stream` (default: torch's current), one launch."""
+    import torch
+
+    prm = patch_track_params(half_window, search_radius, uniqueness, min_texture, max_rms, fb_check)
+    if images0.dim() != 3 or images0.shape[0] < 1:
+        raise ValueError("images0 must be uint8 [pairs, h, w]")
+    pairs = int(images0.shape[0])
+    h, w, stride0, istride0 = _track_images("images0", images0, pairs)
+    h1, w1, stride1, istride1 = _track_images("images1", images1, pairs)
+    if (h1, w1) != (h, w):
+        raise ValueError("images0 and images1 must have the same shape")
+    if kp.dim() != 3 or kp.shape[2] != 3 or kp.dtype != torch.float32 or not kp.is_contiguous() or kp.shape[0] not in (pairs, 2 * pairs):
+        raise ValueError(f"kp must be a contiguous float32 tensor [{pairs} or {2 * pairs}, max_keypoints, 3]")
+    units, k = int(kp.shape[0]), int(kp.shape[1])
+    if not 1 <= k <= 4096:
+        raise ValueError("max_keypoints must be in [1, 4096]")
+    if n.dtype != torch.int32 or n.dim() != 1 or n.numel() != units or not n.is_contiguous():
+        raise ValueError(f"n must be a contiguous int32 tensor with {units} entries, one per unit of kp")
+    if pred is not None and (tuple(pred.shape) != (pairs, k, 3) or pred.dtype != torch.float32 or not pred.is_contiguous()):
+        raise ValueError(f"pred must be a contiguous float32 tensor [{pairs}, {k}, 3]")
+    if out is None:
+        out = (torch.empty((pairs, k, 3), dtype=torch.float32, device=kp.device), torch.empty((pairs,), dtype=torch.int32, device=kp.device),
+               torch.empty((pairs, k), dtype=torch.int32, device=kp.device))
+    ko, no, mo = out
+    for name, t, shape, dt in (("out[0]", ko, (pairs, k, 3), torch.float32), ("out[1]", no, (pairs,), torch.int32),
+                               ("out[2]", mo, (pairs, k), torch.int32)):
+        if tuple(t.shape) != shape or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor {list(shape)}")
+    if not all(t.is_cuda for t in (images0, images1, kp, n, ko, no, mo) + (() if pred is None else (pred,))):
+        raise ValueError("images0, images1, kp, n, pred and out must be device tensors")
+    status = torch.empty((pairs, k), dtype=torch.uint8, device=kp.device) if return_status else None
+    cost = torch.empty((pairs, k), dtype=torch.int64, device=kp.device) if return_status else None
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    _lib.check(_lib.lib().sship_patch_track_batch_device(images0.data_ptr(), istride0, stride0, images1.data_ptr(), istride1, stride1, pairs, h, w,
+                                                         kp.data_ptr(), n.data_ptr(), units // pairs,
+                                                         pred.data_ptr() if pred is not None else None, k, _lib.C.byref(prm), ko.data_ptr(),
+                                                         no.data_ptr(), mo.data_ptr(), status.data_ptr() if return_status else None,
+                                                         cost.data_ptr() if return_status else None, s))
+    return (ko, no, mo, status, cost) if return_status else (ko, no, mo)
+
+
+def patch_track(img0: np.ndarray, img1: np.ndarray, keypoints: np.ndarray, pred=None, *, half_window: int = 5, search_radius: int = 8,
+                uniqueness: int = 10, min_texture: float = 0.0, max_rms: float = 0.0, fb_check: int = 1, return_status: bool = False):
+    """One pair from host arrays (sship_patch_track_host): img0 / img1 u8 [h, w] (rows may be strided), keypoints f32 [n, >= 2] with
+    (x, y) in the first two columns and the score in the third where there is one, pred (optional) f32 [n, >= 2]
+    -> (kp1 f32 [n, 3], matches0 i32 [n]); return_status: also status u8 [n] and cost i64 [n].  Synchronous."""
+    prm = patch_track_params(half_window, search_radius, uniqueness, min_texture, max_rms, fb_check)
+    for name, im in (("img0", img0), ("img1", img1)):
+        if not isinstance(im, np.ndarray) or im.dtype != np.uint8 or im.ndim != 2:
+            raise ValueError(f"{name} must be a uint8 array [h, w]")
+    if img0.shape != img1.shape:
+        raise ValueError("img0 and img1 must have the same shape")
+    h, w = img0.shape
+    if not (1 <= h <= 16384 and 1 <= w <= 16384):
+        raise ValueError("h and w must be in [1, 16384]")
+    img0, img1 = (im if (im.strides[1] == 1 or w == 1) and (im.strides[0] >= w or h == 1) else np.ascontiguousarray(im) for im in (img0, img1))
+    kp = np.ascontiguousarray(keypoints, np.float32)
+    if kp.ndim != 2 or kp.shape[1] < 2:
+        raise ValueError("keypoints must be [n, >= 2]")
+    n = len(kp)
+    if n > 4096:
+        raise ValueError("n must be at most 4096")
+    pr = None
+    if pred is not None:
+        pr = np.ascontiguousarray(pred, np.float32)
+        if pr.ndim != 2 or pr.shape[1] < 2 or len(pr) != n:
+            raise ValueError("pred must be [n, >= 2]")
+    ko, mo = np.empty((n, 3), np.float32), np.empty(n, np.int32)
+    status, cost = np.zeros(n, np.uint8), np.full(n, -1, np.int64)
+    row = lambda im: int(im.strides[0]) if h > 1 else w   # noqa: E731
+    _lib.check(_lib.lib().sship_patch_track_host(img0.ctypes.data, row(img0), img1.ctypes.data, row(img1), h, w, kp.ctypes.data, int(kp.shape[1]),
+                                                 pr.ctypes.data if pr is not None else None, int(pr.shape[1]) if pr is not None else 0, n,
+                                                 _lib.C.byref(prm), ko.ctypes.data, mo.ctypes.data, status.ctypes.data, cost.ctypes.data))
+    return (ko, mo, status, cost) if return_status else (ko, mo)
+
+
+def patch_track_stereo_batch(images_prev, images_cur, kp, n, pred=None, track=None, search=None):
+    """A frame on which no network runs: images_prev / images_cur u8 [2P, h, w] ordered L0, R0, L1, R1, ..., kp / n the previous (or the
+    key) frame's left keypoints as patch_track_batch takes them.  Tracks left to left (patch_track_batch on the [0::2] views, keyword
+    arguments in `track`), then searches the current pair at the tracked keypoints (stereo_search_batch, keyword arguments in `search`)
+    -> (kp1 [P, K, 3], n1 [P], matches0 [P, K], stereo1 [P, K, 3], has_depth1 [P, K]): what PoseSolver.obs_from_matches and RansacVerifier
+    need next to the previous frame's stereo / has_depth.  An untracked row (NaN, NaN, score) is BORDER for the search: no depth.  Two
+    launches on torch's current stream, no host synchronisation."""
+    for name, im in (("images_prev", images_prev), ("images_cur", images_cur)):
+        if im.dim() != 3 or im.shape[0] < 2 or im.shape[0] % 2:
+            raise ValueError(f"{name} must be uint8 [2 * pairs, h, w]")
+    kp1, n1, m0 = patch_track_batch(images_prev[0::2], images_cur[0::2], kp, n, pred, **(track or {}))
+    stereo1, hd1 = stereo_search_batch(images_cur, kp1, n1, **(search or {}))
+    return kp1, n1, m0, stereo1, hd1
+
+
 class FrontEndBatch:
     """Device-resident throughput step: SuperPoint on 2P images + LightGlue on P pairs, no host sync."""
 
