@@ -21,7 +21,7 @@
 //             -Lsuperslam_amd/lib -lsuperslam_hip -Wl,-rpath,$PWD/superslam_amd/lib -Wl,-rpath,/opt/rocm/lib -lpthread -lz
 // run:    ./frontend_benchmark --sp sp.safetensors --lg lg.safetensors (--sequence DIR | --synthetic 200) [--keyframe-match]
 //                              [--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--subpixel] [--matcher lightglue|nn]
-//                              [--dump-keypoints FILE] [--stereo-gate MIN,MAX,ROW] [--track-window R]
+//                              [--dump-keypoints FILE] [--stereo-gate MIN,MAX,ROW] [--track-window R] [--dump DIR] [--strict-ahead]
 //
 // --matcher nn: the mutual nearest-neighbour matcher (superslam_hip::NNMatcher, hloc's NN-mutual) in LightGlue's place - same
 // IFeatureMatcher calls, no --lg needed.  Default: lightglue.
@@ -35,6 +35,24 @@
 // Cross-frame pipelining (default with the ring; --no-pipeline turns it off): as soon as frame t's extraction has returned, frame
 // t+1's extraction is ENQUEUED on the extractor's stream (sship_sp_ring_submit) - before frame t's LightGlue match - so the next
 // frame's SuperPoint kernels share the GPU with this frame's matcher, whose launches cover a fraction of the CUs at one pair.
+// --strict-ahead (ring + pipelining only): before deciding whether to submit frame t+1, the tracking thread waits until that frame
+// is decoded or the source is exhausted, so every frame but the last is submitted ahead whatever the decode speed.  It changes
+// when work is enqueued and nothing else.
+//
+// --dump DIR: what the consumer of every frame receives, written to DIR/frames.bin (DIR must exist and be writable) outside the
+// timed bracket; no printed statistic changes.  Little-endian, no padding; tests/_runner_dump.py is the reader.
+//   file header, 16 bytes : char[4] "SSRF" | u32 version = 1 | u32 descriptor dim (256) | u32 flags (bit 0: --keyframe-match)
+//   then one record per frame, in frame order:
+//     i32[8]              : frame index, n_left, n_right, n_stereo, n_temporal (-1: no temporal match was run for this frame - no
+//                           --keyframe-match, frame 0, or a previous left image without keypoints), submitted_ahead (1: this frame's
+//                           extraction had been enqueued by sship_sp_ring_submit before it was collected), 0, 0
+//     f32[n_left][3]      : left keypoints (x, y, response)
+//     f32[n_right][3]     : right keypoints
+//     f32[n_left][256]    : left descriptors, as sship_desc_to_host returns them
+//     f32[n_right][256]   : right descriptors
+//     n_stereo x 12 bytes : the stereo matches as IFeatureMatcher::match returned them, (i32 queryIdx, i32 trainIdx, f32 distance)
+//     u8[n_stereo]        : 1 where the runner's disparity gate (uL - uR >= 1, |vL - vR| <= 2) passed the match
+//     n_temporal x 12 bytes (if n_temporal > 0): the temporal matches, query = this frame's left, train = the previous frame's left
 #include <algorithm>
 #include <chrono>
 #include <condition_variable>
@@ -123,11 +141,11 @@ struct Source {
 }  // namespace
 
 int main(int argc, char** argv) {
-  std::string sp_path, lg_path, matcher_name = "lightglue", dump_path;
+  std::string sp_path, lg_path, matcher_name = "lightglue", dump_path, dump_dir;
   Source src;
   int max_kp = 600, border = 4;
   double thr = 0.005;
-  bool keyframe = false, use_ring = true, pipeline = true, bilinear = false, subpixel = false, stereo_gate = false;
+  bool keyframe = false, use_ring = true, pipeline = true, bilinear = false, subpixel = false, stereo_gate = false, strict_ahead = false, dump_frames = false;
   float gate_min = 0.f, gate_max = 0.f, gate_row = 0.f, track_window = -1.f;
   for (int i = 1; i < argc; ++i) {
     const std::string a = argv[i];
@@ -145,6 +163,8 @@ int main(int argc, char** argv) {
     else if (a == "--bilinear") bilinear = true;
     else if (a == "--subpixel") subpixel = true;
     else if (a == "--dump-keypoints") dump_path = next();
+    else if (a == "--dump") { dump_dir = next(); dump_frames = true; }
+    else if (a == "--strict-ahead") strict_ahead = true;
     else if (a == "--matcher") matcher_name = next();
     else if (a == "--stereo-gate") {
       stereo_gate = std::sscanf(next(), "%f,%f,%f", &gate_min, &gate_max, &gate_row) == 3;
@@ -155,11 +175,28 @@ int main(int argc, char** argv) {
   }
   const bool use_nn = matcher_name == "nn";
   const bool gated = stereo_gate || track_window >= 0.f;  // the gates belong to the nn matcher
-  if (sp_path.empty() || (!use_nn && (lg_path.empty() || matcher_name != "lightglue" || gated)) || (src.sequence.empty() && src.synthetic <= 0)) {
+  bool bad_usage = sp_path.empty() || (!use_nn && (lg_path.empty() || matcher_name != "lightglue" || gated)) ||
+                   (src.sequence.empty() && src.synthetic <= 0);
+  if (strict_ahead && (!use_ring || !pipeline)) {
+    std::fprintf(stderr, "--strict-ahead needs the ring and pipelining (not --no-ring / --no-pipeline)\n");
+    bad_usage = true;
+  }
+  std::FILE* dump_file = nullptr;  // --dump DIR: opened before anything else starts, so that an unwritable DIR is bad usage
+  if (!bad_usage && dump_frames) {
+    dump_file = dump_dir.empty() ? nullptr : std::fopen((dump_dir + "/frames.bin").c_str(), "wb");
+    if (!dump_file) { std::fprintf(stderr, "--dump: cannot write %s/frames.bin\n", dump_dir.c_str()); bad_usage = true; }
+  }
+  if (bad_usage) {
     std::fprintf(stderr, "usage: %s --sp W.safetensors --lg W.safetensors (--sequence DIR | --synthetic N) [--keyframe-match] "
                          "[--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--subpixel] [--matcher lightglue|nn] "
-                         "[--dump-keypoints FILE] [--stereo-gate MIN,MAX,ROW] [--track-window R] (the gates need --matcher nn)\n", argv[0]);
+                         "[--dump-keypoints FILE] [--stereo-gate MIN,MAX,ROW] [--track-window R] [--dump DIR] [--strict-ahead] "
+                         "(the gates need --matcher nn; --strict-ahead needs the ring and pipelining)\n", argv[0]);
     return 2;
+  }
+  if (dump_file) {
+    const uint32_t hdr[3] = {1u, (uint32_t)sh::SuperPoint::descriptor_dim, keyframe ? 1u : 0u};
+    std::fwrite("SSRF", 1, 4, dump_file);
+    std::fwrite(hdr, 4, 3, dump_file);
   }
 
   // ---- frame geometry from the first frame; timestamps as the reference reads them ----
@@ -228,6 +265,8 @@ int main(int argc, char** argv) {
   std::vector<float> ms;
   long stereo_points = 0, stereo_matches = 0, track_matches = 0, submitted_ahead = 0;
   sh::Features prev_left;
+  bool was_submitted = false;         // this frame's extraction was enqueued ahead, during the previous frame
+  std::vector<uint8_t> gate_passed;   // --dump: the gate's decision per stereo match
   const auto wall0 = std::chrono::steady_clock::now();
   for (int ni = 0;; ++ni) {
     {
@@ -236,14 +275,20 @@ int main(int argc, char** argv) {
       if (produced <= ni) break;
     }
     const int slot = ni % kDepth;
+    const bool submitted_this = was_submitted;
+    was_submitted = false;
     const auto t1 = std::chrono::steady_clock::now();
     std::pair<sh::Features, sh::Features> feats;
     if (use_ring) {
       feats = extractor.extract_stereo_ring(slot);   // a submitted slot: waits for its completion event only
       if (pipeline) {  // frame ni + 1 already decoded and uploading?  enqueue its extraction now, ahead of this frame's match
         bool have_next;
-        { std::lock_guard<std::mutex> lk(mu); have_next = produced > ni + 1; }
-        if (have_next && extractor.ring_submit((ni + 1) % kDepth)) ++submitted_ahead;
+        {
+          std::unique_lock<std::mutex> lk(mu);
+          if (strict_ahead) cv_ready.wait(lk, [&] { return produced > ni + 1 || done; });  // the decoder is at most kDepth - 1 frames ahead: no deadlock
+          have_next = produced > ni + 1;
+        }
+        if (have_next && extractor.ring_submit((ni + 1) % kDepth)) { ++submitted_ahead; was_submitted = true; }
       }
     } else feats = extractor.extract_stereo(sh::Image{plain[2 * slot].data(), rows, cols, 1, 0}, sh::Image{plain[2 * slot + 1].data(), rows, cols, 1, 0});
     if (ni == 0 && !dump_path.empty()) {
@@ -258,15 +303,45 @@ int main(int argc, char** argv) {
       }
     }
     sh::MatchResult lr = matcher.match(feats.first.keypoints, feats.first.descriptors, feats.second.keypoints, feats.second.descriptors);
-    for (const sh::DMatch& m : lr.matches) {  // StereoFrontEnd's gate
+    if (dump_file) gate_passed.assign(lr.matches.size(), 0);
+    for (size_t i = 0; i < lr.matches.size(); ++i) {  // StereoFrontEnd's gate
+      const sh::DMatch& m = lr.matches[i];
       const sh::KeyPoint &kl = feats.first.keypoints[m.queryIdx], &kr = feats.second.keypoints[m.trainIdx];
-      if (kl.x - kr.x >= 1.0f && std::abs(kl.y - kr.y) <= 2.0f) ++stereo_points;
+      if (kl.x - kr.x >= 1.0f && std::abs(kl.y - kr.y) <= 2.0f) {
+        ++stereo_points;
+        if (dump_file) gate_passed[i] = 1;
+      }
     }
     stereo_matches += (long)lr.matches.size();
-    if (keyframe && !prev_left.descriptors.empty())
-      track_matches += (long)track_matcher.match(feats.first.keypoints, feats.first.descriptors, prev_left.keypoints, prev_left.descriptors).matches.size();
+    sh::MatchResult tr;
+    const bool tracked = keyframe && !prev_left.descriptors.empty();
+    if (tracked) {
+      tr = track_matcher.match(feats.first.keypoints, feats.first.descriptors, prev_left.keypoints, prev_left.descriptors);
+      track_matches += (long)tr.matches.size();
+    }
     const auto t2 = std::chrono::steady_clock::now();
     ms.push_back((float)std::chrono::duration_cast<std::chrono::microseconds>(t2 - t1).count() / 1000.0f);
+    if (dump_file) {  // outside the timed bracket; layout in the header comment
+      const int32_t rec[8] = {ni, (int32_t)feats.first.keypoints.size(), (int32_t)feats.second.keypoints.size(), (int32_t)lr.matches.size(),
+                              tracked ? (int32_t)tr.matches.size() : -1, submitted_this ? 1 : 0, 0, 0};
+      std::fwrite(rec, 4, 8, dump_file);
+      for (const sh::Features* ft : {&feats.first, &feats.second})
+        for (const sh::KeyPoint& k : ft->keypoints) { const float v[3] = {k.x, k.y, k.response}; std::fwrite(v, 4, 3, dump_file); }
+      for (const sh::Features* ft : {&feats.first, &feats.second}) {
+        const sh::HostDescriptors hd = matcher.descriptors_to_host(ft->descriptors);
+        std::fwrite(hd.data.data(), 4, hd.data.size(), dump_file);
+      }
+      auto write_matches = [&](const sh::MatchResult& r) {
+        for (const sh::DMatch& m : r.matches) {
+          const int32_t qt[2] = {m.queryIdx, m.trainIdx};
+          std::fwrite(qt, 4, 2, dump_file);
+          std::fwrite(&m.distance, 4, 1, dump_file);
+        }
+      };
+      write_matches(lr);
+      std::fwrite(gate_passed.data(), 1, gate_passed.size(), dump_file);
+      write_matches(tr);
+    }
     if (keyframe) prev_left = std::move(feats.first);  // holds its pool slot until the next frame replaces it
     {
       std::lock_guard<std::mutex> lk(mu);
@@ -276,6 +351,10 @@ int main(int argc, char** argv) {
   }
   const double wall = std::chrono::duration_cast<std::chrono::milliseconds>(std::chrono::steady_clock::now() - wall0).count() / 1000.0;
   producer.join();
+  if (dump_file) {
+    const bool failed = std::ferror(dump_file) != 0;
+    if (std::fclose(dump_file) != 0 || failed) { std::fprintf(stderr, "--dump: writing %s/frames.bin failed\n", dump_dir.c_str()); return 1; }
+  }
   if (ms.empty()) { std::fprintf(stderr, "no frames\n"); return 1; }
 
   const double mean = std::accumulate(ms.begin(), ms.end(), 0.0) / ms.size();

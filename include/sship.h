@@ -247,6 +247,10 @@ int sship_sp_extract_stereo_ring(sship_sp* sp, int slot, sship_features* out_lef
  * that work's completion event and hands the results out.  Called right after frame t's extraction has returned - before frame
  * t's LightGlue match - it lets frame t+1's SuperPoint kernels share the GPU with frame t's matcher (the matcher's launches
  * cover a fraction of the CUs at one pair).  Same thread as every other call on this handle; at most one submission per slot.
+ * Pool budget: a submission acquires its two pool slots when it is ENQUEUED, not when it is collected.  The per-frame schedule of
+ * examples/frontend_benchmark.cc (submit t+1 right after collecting t, keep the previous frame's left features for the temporal
+ * match) therefore holds 2 slots in flight + 2 being matched + 1 held = 5 of the default 8 (cfg.pool_slots); a consumer that keeps
+ * more than 3 further handles alive exhausts the pool at the next submission (tests/test_gpu_runner_frames.py asserts the 5).
  * Constraints while a submission is pending (submitted, not yet collected):
  *   - sship_sp_ring_upload(slot) on that slot returns SSHIP_ERR_INVALID: the queued network still reads the slot's device
  *     frame (collect first, then refill);

@@ -54,6 +54,14 @@ def check(c, mscore_bar=None):
     assert c["mscores_maxd"] <= bar, c
 
 
+def keypoint_iou(kp, kp_ref):
+    """Intersection over union of two keypoint sets on their integer pixels (x, y) - the end-to-end keypoint measure of SURVEY 8(c),
+    bar 0.98 (test_superpoint_extract_vs_oracle_end_to_end)."""
+    a = {(int(k[0]), int(k[1])) for k in kp}
+    b = {(int(k[0]), int(k[1])) for k in kp_ref}
+    return len(a & b) / max(1, len(a | b))
+
+
 def margins(report):
     """{entry.key: (measured, bar, bar / measured)} for every mscores0 figure of a parity report."""
     out = {}

@@ -21,12 +21,28 @@ def _build():
                       extra=["-lpthread", "-lz"], opt="-O2", outdir=LIBDIR)
 
 
-def test_benchmark_runner_builds_and_rejects_bad_usage():
+def test_benchmark_runner_builds_and_rejects_bad_usage(tmp_path):
     from superslam_amd import _lib
 
     _lib.lib()   # the .so must exist (built by __graft_entry__.build / superslam_amd.build)
     out = subprocess.run([_build()], capture_output=True, text=True, timeout=60)
     assert out.returncode == 2 and "usage:" in out.stderr
+    assert "[--dump DIR]" in out.stderr and "[--strict-ahead]" in out.stderr
+    # --strict-ahead belongs to the ring's pipelined mode, --dump needs a directory it can write into: exit status 2 with the usage
+    # line, before any weight file is opened or the device is touched (the weight paths here do not exist)
+    base = [_build(), "--sp", str(tmp_path / "sp.safetensors"), "--lg", str(tmp_path / "lg.safetensors"), "--synthetic", "2"]
+    not_a_dir = tmp_path / "file"
+    not_a_dir.write_bytes(b"")
+    for extra in (["--strict-ahead", "--no-ring"], ["--strict-ahead", "--no-pipeline"], ["--no-pipeline", "--strict-ahead", "--keyframe-match"],
+                  ["--dump", str(tmp_path / "missing")], ["--dump", str(not_a_dir)], ["--dump", ""], ["--dump"]):
+        out = subprocess.run(base + extra, capture_output=True, text=True, timeout=60)
+        assert out.returncode == 2 and "usage:" in out.stderr, (extra, out.returncode, out.stderr)
+    # the good forms get past the usage check (what fails next is the missing weight file), with the dump file created
+    dump = tmp_path / "dump"
+    dump.mkdir()
+    out = subprocess.run(base + ["--strict-ahead", "--dump", str(dump)], capture_output=True, text=True, timeout=60)
+    assert out.returncode not in (0, 2) and "usage:" not in out.stderr, (out.returncode, out.stderr)
+    assert (dump / "frames.bin").exists()
 
 
 def _field(text, label):

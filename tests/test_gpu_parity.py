@@ -246,9 +246,7 @@ def test_superpoint_extract_vs_oracle_end_to_end(sp, weights_dir):
         s, d = R.dense_forward(weights_dir["sp"], x, emulate_fp16=True)
     for b, f in enumerate((fl, fr)):
         ref = H.select_topk(s[b].numpy(), 376, 1376, 0.005, 4, 600, 47, 172)
-        a = {(int(k[0]), int(k[1])) for k in f.keypoints}
-        bset = {(int(k[0]), int(k[1])) for k in ref["kp"]}
-        iou = len(a & bset) / max(1, len(a | bset))
+        iou = _lgcmp.keypoint_iou(f.keypoints, ref["kp"])   # shared with tests/test_gpu_runner_frames.py
         print(f"e2e image {b}: n={len(f.keypoints)} ref n={len(ref['kp'])} keypoint IoU {iou:.4f}")
         assert len(f.keypoints) == 600 and iou >= 0.98   # SURVEY 8(c); measured 0.993-0.997 (profiles/parity_report.json)
         sc = f.keypoints[:, 2]
