@@ -374,8 +374,10 @@ int sship_lg_debug_read(sship_lg* lg, int what, int index, int rows, int cols, f
  *   costs one host branch per stage: no allocation, no launch, and no kernel knows about it.  On, every later match call of the handle (the
  *   batch-device and the single-pair entries alike) enqueues, right after the launch that produces a stage and on the stream that ran it (on
  *   the two-stream path each half copies its own pairs on its own stream), a device-to-device copy of that stage's slice of every listed pair
- *   that the call holds.  matches0 / mscores0 keep their bits.  A call with adaptive depth or adaptive width on while capture is on returns
- *   SSHIP_ERR_INVALID.  Negative or repeated pair indices -> SSHIP_ERR_INVALID.  Switching forgets what was captured.
+ *   that the call holds.  matches0 / mscores0 keep their bits.  With adaptive depth or adaptive width on the same stages are captured (X_OUT
+ *   before the layer's pruning step, the next layer's X_IN / Q_S / K_S / V_S after it and after the re-projection), the state of the two modes
+ *   in addition (sship_lg_debug_adaptive below), and layers_run / prune_counts keep their values too.  Negative or repeated pair indices ->
+ *   SSHIP_ERR_INVALID.  Switching forgets what was captured.
  * sship_lg_debug_stage(lg, slot, layer, stage, out, floats): stage `stage` of layer `layer` (0 .. 8) of the pair listed at position `slot`,
  *   from the LAST call, as fp32 in natural order, device-synchronising: out[2][NP][256] (set 0, set 1 of the pair; NP = the handle's padded
  *   sequence length, max_keypoints rounded up to 32), out[2][NP] for LOGSIG; `floats` must be exactly that size.  Rows past a sequence's
@@ -402,6 +404,27 @@ enum { SSHIP_LG_STAGE_X_IN = 0, SSHIP_LG_STAGE_Q_S = 1, SSHIP_LG_STAGE_K_S = 2, 
        SSHIP_LG_STAGE_MD = 10, SSHIP_LG_STAGE_LOGSIG = 11 };
 int sship_lg_debug_capture(sship_lg* lg, const int* pairs, int count);
 int sship_lg_debug_stage(sship_lg* lg, int slot, int layer, int stage, float* out, unsigned long long floats);
+/* Test-only: what the capture kept of the adaptive modes (tests/test_gpu_lg_adaptive_stages.py), for the pair listed at `slot`, from the LAST
+ * call, device-synchronising.  Every item is an array of 4-byte values, int32 or f32 as listed; `count` must be exactly its length.  A stopped
+ * pair's items of later layers are copied all the same (they show that nothing touched it).  SSHIP_ERR_INVALID as for sship_lg_debug_stage,
+ * and when the last call ran with both modes off, for an item of adaptive width when width was off, and for the last four items after a
+ * truncated run (sship_lg_debug_set_layers).  `layer` must be 0 for the items that have none.
+ *    0 LENS        int32 [2]           layer 0 .. 8: the two counts the attention launches of the layer read (0, 0 for a pair that is not running)
+ *    1 ROPE        f32 [2][NP][64]     layer 0 .. 8: the pair's rotary table as the layer read it
+ *    2 IND         int32 [2][NP]       layer 0 .. 7, width: original keypoint index of every live row after the pruning step of the layer
+ *    3 PRUNE       int32 [2][NP]       layer 0 .. 7, width: prune counts by original index after that step
+ *    4 WLEN        int32 [2]           layer 0 .. 7, width: live tokens after that step
+ *    5 CHG         int32 [2]           layer 0 .. 7, width: 1 where the sequence lost tokens at that step
+ *    6 CNT         int32 [8]           tokens counted below the threshold after layer 0 .. 7 (0 where the pair was not running, or depth is off)
+ *    7 LAYERS_RUN  int32 [1]           as sship_lg_layers_run
+ *    8 MD          f32 [2][NP][256]    the fp16 rows the assignment read: the exit head's for a pair that stopped early
+ *    9 LOGSIG      f32 [2][NP]         likewise
+ *   10 MATCHES_C   int32 [max_kp]      width: matches of the live rows before they are mapped back through IND
+ *   11 MSCORES_C   f32 [max_kp]        width: their scores */
+enum { SSHIP_LG_ADAPT_LENS = 0, SSHIP_LG_ADAPT_ROPE = 1, SSHIP_LG_ADAPT_IND = 2, SSHIP_LG_ADAPT_PRUNE = 3, SSHIP_LG_ADAPT_WLEN = 4,
+       SSHIP_LG_ADAPT_CHG = 5, SSHIP_LG_ADAPT_CNT = 6, SSHIP_LG_ADAPT_LAYERS_RUN = 7, SSHIP_LG_ADAPT_MD = 8, SSHIP_LG_ADAPT_LOGSIG = 9,
+       SSHIP_LG_ADAPT_MATCHES_C = 10, SSHIP_LG_ADAPT_MSCORES_C = 11 };
+int sship_lg_debug_adaptive(sship_lg* lg, int slot, int layer, int what, void* out, unsigned long long count);
 /* Test-only: copy one activation of the extractor's LAST call to the host, raw (channels-last [batch][h_l][w_l][c_l]), device-synchronising.
  * layer: 1 conv1b (+pool), 2 conv2a, 3 conv2b (+pool), 4 conv3a, 5 conv3b (+pool), 6 conv4a, 7 conv4b (the ids of sship_sp_bench_layer), all fp16;
  * and the heads: 8 convPa, fp16 [B,Hc,Wc,256]; 9 convDa, the same layout, filled only by sship_sp_dense called with a descriptor grid;

@@ -146,6 +146,7 @@ _SIGS = {
     "sship_lg_debug_read": (ip, [vp, ip, ip, ip, ip, vp]),
     "sship_lg_debug_capture": (ip, [vp, vp, ip]),
     "sship_lg_debug_stage": (ip, [vp, ip, ip, ip, vp, C.c_ulonglong]),
+    "sship_lg_debug_adaptive": (ip, [vp, ip, ip, ip, vp, C.c_ulonglong]),
     "sship_filter_matches": (ip, [vp, vp, ip, vp, vp, vp]),
     "sship_nn_create": (ip, [ip, ip, C.POINTER(vp)]),
     "sship_nn_destroy": (None, [vp]),

@@ -1759,6 +1759,26 @@ extern "C" void sship_lg_weights_release(sship_lg_weights* w) {
   if (last) lg_weights_free(w);
 }
 
+// Word offsets inside one slot of sship_lg::cap_ad: lens [9][2] | rope [9][2 NP][64] | ind [8][2 NP] | prune [8][2 NP] | wlen [8][2] | chg [8][2] |
+// cnt [8] | layers_run [1] | mc [max_kp] | msc [max_kp]
+struct LgCapAd {
+  size_t lens, rope, ind, prune, wlen, chg, cnt, lr, mc, msc, words;
+  LgCapAd() : LgCapAd(0, 0) {}
+  LgCapAd(int NP, int max_kp) {
+    const size_t np2 = (size_t)2 * NP;
+    lens = 0;
+    rope = lens + 9 * 2;
+    ind = rope + 9 * np2 * 64;
+    prune = ind + 8 * np2;
+    wlen = prune + 8 * np2;
+    chg = wlen + 8 * 2;
+    cnt = chg + 8 * 2;
+    lr = cnt + 8;
+    mc = lr + 1;
+    msc = mc + (size_t)max_kp;
+    words = msc + (size_t)max_kp;
+  }
+};
 struct sship_lg {
   sship_lg_weights* w = nullptr;
   int image_w = 0, image_h = 0, max_kp = 0, max_pairs = 0, NP = 0;
@@ -1793,6 +1813,11 @@ struct sship_lg {
   bool captured = false;
   int cap_last_pairs = 0;
   DevBuf cap, cap_md, cap_ls;
+  // the same capture with adaptive depth / width on (sship_lg_debug_adaptive): cap_ad holds, per slot, cap_lay.words 4-byte words
+  // (layout: LgCapAd, set when capture is switched on), cap_amd / cap_als the md (fp16 [2 NP][256]) / logsig (f32 [2 NP]) the assignment read
+  bool cap_last_adaptive = false, cap_last_width = false, cap_last_assigned = false;
+  LgCapAd cap_lay;
+  DevBuf cap_ad, cap_amd, cap_als;
 };
 
 // Adaptive depth state layout in sship_lg::dep (ints): cnt [P][8] | layers_run [P] | lens_live [2P] | live [P + kAux + 1] | tickets [kAux + 1]
@@ -1950,6 +1975,10 @@ extern "C" int sship_lg_debug_capture(sship_lg* lg, const int* pairs, int count)
     SSHIP_HIP_CHECK(lg->cap.ensure((size_t)sship_lg::kCapSlots * kLgLayers * sship_lg::kCapStages * pair_halfs * 2));
     SSHIP_HIP_CHECK(lg->cap_md.ensure((size_t)sship_lg::kCapSlots * pair_halfs * 2));
     SSHIP_HIP_CHECK(lg->cap_ls.ensure((size_t)sship_lg::kCapSlots * 2 * lg->NP * 4));
+    lg->cap_lay = LgCapAd(lg->NP, lg->max_kp);
+    SSHIP_HIP_CHECK(lg->cap_ad.ensure((size_t)sship_lg::kCapSlots * lg->cap_lay.words * 4));
+    SSHIP_HIP_CHECK(lg->cap_amd.ensure((size_t)sship_lg::kCapSlots * pair_halfs * 2));
+    SSHIP_HIP_CHECK(lg->cap_als.ensure((size_t)sship_lg::kCapSlots * 2 * lg->NP * 4));
   }
   for (int i = 0; i < count; ++i) lg->cap_pairs[i] = pairs[i];
   lg->cap_n = count;
@@ -2012,6 +2041,52 @@ extern "C" int sship_lg_debug_stage(sship_lg* lg, int slot, int layer, int stage
     else
       for (size_t i = 0; i < (size_t)NP * 256; ++i) o[i] = half_bits_to_float(s16[i]);
   }
+  return SSHIP_OK;
+}
+
+// Test-only (include/sship.h): what the capture kept of the adaptive modes' state, as 4-byte values (int32 or f32 by item)
+extern "C" int sship_lg_debug_adaptive(sship_lg* lg, int slot, int layer, int what, void* out, unsigned long long count) {
+  bind_thread();
+  if (!lg || !out) return fail(SSHIP_ERR_INVALID, "lg_debug_adaptive: null argument");
+  if (lg->cap_n == 0 || !lg->captured || !lg->cap_last_adaptive)
+    return fail(SSHIP_ERR_INVALID, "lg_debug_adaptive: capture is off, no call has run since it was switched on, or the last call ran with both adaptive modes off");
+  if (slot < 0 || slot >= lg->cap_n || lg->cap_pairs[slot] >= lg->cap_last_pairs)
+    return fail(SSHIP_ERR_INVALID, "lg_debug_adaptive: no such slot, or the last call did not hold its pair");
+  const size_t NP = lg->NP, K = lg->max_kp;
+  const LgCapAd& lay = lg->cap_lay;
+  size_t off = 0, n = 0;
+  int layers = 1;      // valid layers: [0, layers)
+  bool need_width = false, need_assign = false;
+  switch (what) {
+    case SSHIP_LG_ADAPT_LENS: off = lay.lens + (size_t)layer * 2; n = 2; layers = kLgLayers; break;
+    case SSHIP_LG_ADAPT_ROPE: off = lay.rope + (size_t)layer * 2 * NP * 64; n = 2 * NP * 64; layers = kLgLayers; break;
+    case SSHIP_LG_ADAPT_IND: off = lay.ind + (size_t)layer * 2 * NP; n = 2 * NP; layers = kLgLayers - 1; need_width = true; break;
+    case SSHIP_LG_ADAPT_PRUNE: off = lay.prune + (size_t)layer * 2 * NP; n = 2 * NP; layers = kLgLayers - 1; need_width = true; break;
+    case SSHIP_LG_ADAPT_WLEN: off = lay.wlen + (size_t)layer * 2; n = 2; layers = kLgLayers - 1; need_width = true; break;
+    case SSHIP_LG_ADAPT_CHG: off = lay.chg + (size_t)layer * 2; n = 2; layers = kLgLayers - 1; need_width = true; break;
+    case SSHIP_LG_ADAPT_CNT: off = lay.cnt; n = 8; break;
+    case SSHIP_LG_ADAPT_LAYERS_RUN: off = lay.lr; n = 1; break;
+    case SSHIP_LG_ADAPT_MD: n = 2 * NP * 256; need_assign = true; break;
+    case SSHIP_LG_ADAPT_LOGSIG: n = 2 * NP; need_assign = true; break;
+    case SSHIP_LG_ADAPT_MATCHES_C: off = lay.mc; n = K; need_width = need_assign = true; break;
+    case SSHIP_LG_ADAPT_MSCORES_C: off = lay.msc; n = K; need_width = need_assign = true; break;
+    default: return fail(SSHIP_ERR_INVALID, "lg_debug_adaptive: unknown item");
+  }
+  if (layer < 0 || layer >= layers) return fail(SSHIP_ERR_INVALID, "lg_debug_adaptive: no such layer for this item");
+  if ((need_width && !lg->cap_last_width) || (need_assign && !lg->cap_last_assigned))
+    return fail(SSHIP_ERR_INVALID, "lg_debug_adaptive: the last call did not produce this item (adaptive width off, or a truncated run)");
+  if (count != n) return fail(SSHIP_ERR_INVALID, "lg_debug_adaptive: bad size");
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());
+  if (what == SSHIP_LG_ADAPT_MD) {
+    std::vector<uint16_t> tmp(n);
+    SSHIP_HIP_CHECK(hipMemcpy(tmp.data(), lg->cap_amd.as<_Float16>() + (size_t)slot * n, n * 2, hipMemcpyDeviceToHost));
+    float* o = static_cast<float*>(out);
+    for (size_t i = 0; i < n; ++i) o[i] = half_bits_to_float(tmp[i]);
+    return SSHIP_OK;
+  }
+  const void* src = what == SSHIP_LG_ADAPT_LOGSIG ? static_cast<const void*>(lg->cap_als.as<float>() + (size_t)slot * n)
+                                                  : static_cast<const void*>(lg->cap_ad.as<int>() + (size_t)slot * lay.words + off);
+  SSHIP_HIP_CHECK(hipMemcpy(out, src, n * 4, hipMemcpyDeviceToHost));
   return SSHIP_OK;
 }
 
@@ -2133,9 +2208,11 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
     return fail(SSHIP_ERR_INVALID, "lightglue: adaptive width is not supported by the 16-wave FFN or the LDS-resident-key attention");
 #endif
   if (lg->cap_n) {  // test-only stage capture (sship_lg_debug_capture)
-    if (adaptive || width) return fail(SSHIP_ERR_INVALID, "lightglue: stage capture is not supported with adaptive depth or adaptive width");
     lg->captured = true;
     lg->cap_last_pairs = pairs;
+    lg->cap_last_adaptive = adaptive || width;
+    lg->cap_last_width = width;
+    lg->cap_last_assigned = false;
   }
   lg->last_adaptive = adaptive || width;  // layers_run comes from the device in both modes
   lg->last_width = width;
@@ -2172,6 +2249,18 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
       }
       return hipSuccess;
     };
+    // the same for the state of the adaptive modes (4-byte words; `src` is offset to this launch group, `per_pair` words per pair)
+    const LgCapAd& lay = lg->cap_lay;
+    auto cap_words = [&](size_t dst_word, const void* src, size_t per_pair) -> hipError_t {
+      for (int c = 0; c < lg->cap_n; ++c) {
+        const int p = lg->cap_pairs[c];
+        if (p < p0 || p >= p0 + np) continue;
+        if (hipError_t e = hipMemcpyAsync(lg->cap_ad.as<int>() + (size_t)c * lay.words + dst_word,
+                                          static_cast<const int*>(src) + (size_t)(p - p0) * per_pair, per_pair * 4, hipMemcpyDeviceToDevice, st))
+          return e;
+      }
+      return hipSuccess;
+    };
     const int tile_tokens = lg_ffn_tile_tokens(ds.S * ds.NP);
     // what each FFN launch streams (w0, w3, the fused projection): handed to the launch BEFORE it as a prefetch hint (latency mode)
     auto self_w = [&](int i, const ConvW** o) { o[0] = &w->ffn0_s[i]; o[1] = &w->ffn3_s[i]; o[2] = &w->cqkv_t[i]; };
@@ -2195,6 +2284,10 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
         SSHIP_HIP_CHECK(cap(i, kCap_Q_S, q));
         SSHIP_HIP_CHECK(cap(i, kCap_K_S, k));
         SSHIP_HIP_CHECK(cap(i, kCap_V_S, vt));
+        if (adaptive || width) {  // the counts and the rope table this layer's launches read
+          SSHIP_HIP_CHECK(cap_words(lay.lens + (size_t)i * 2, la, 2));
+          SSHIP_HIP_CHECK(cap_words(lay.rope + (size_t)i * 2 * lg->NP * 64, rs, (size_t)2 * lg->NP * 64));
+        }
       }
       // SelfBlock (both images of every pair in one launch); its FFN also emits CrossBlock's [to_qk | to_v]
       launch_lg_attention(qs, ks, vs, la, ds, false, cs, st, shared_gpu);
@@ -2215,6 +2308,7 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
         self_w(i + 1, pf);
         launch_lg_ffn(w->ffn0_c[i], w->ffn3_c[i], w->ln_g_c[i], w->ln_b_c[i], cs, xs, ds, &w->qkv_t[i + 1], true, 2, 2, rs, qs, ks,
                       vs, nullptr, nullptr, 0.f, nullptr, st, pf, live, lm);
+        if (lg->cap_n) SSHIP_HIP_CHECK(cap(i, kCap_X_OUT, x));  // before a pruning step compacts the rows
         if (adaptive)  // token confidence of layer i and the stop rule (reads x after layer i; with width on, of the live tokens)
           launch_lg_depth_conf(xs, width ? wd.wlen : ls, lg->NP, np, w->tc_w + i * 256, w->tc_b[i], lg_depth_threshold(i), lg->depth_conf, i, dep, st);
         if (width) {
@@ -2225,13 +2319,19 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
           launch_lg_width_publish(lg->NP, np, tile_tokens, i, dep, wd, st);
           if (i + 1 < n_layers)
             SSHIP_HIP_CHECK(launch_lg_proj_heads(w->qkv_t[i + 1], xs, ds, 2, 2, rs, qs, ks, vs, st, nullptr, wd.rtiles));
+          if (lg->cap_n) {  // the width state after the pruning step of layer i
+            SSHIP_HIP_CHECK(cap_words(lay.ind + (size_t)i * 2 * lg->NP, wd.ind, (size_t)2 * lg->NP));
+            SSHIP_HIP_CHECK(cap_words(lay.prune + (size_t)i * 2 * lg->NP, wd.prune, (size_t)2 * lg->NP));
+            SSHIP_HIP_CHECK(cap_words(lay.wlen + (size_t)i * 2, wd.wlen, 2));
+            SSHIP_HIP_CHECK(cap_words(lay.chg + (size_t)i * 2, wd.chg, 2));
+          }
         }
       } else
         launch_lg_ffn(w->ffn0_c[i], w->ffn3_c[i], w->ln_g_c[i], w->ln_b_c[i], cs, xs, ds, &w->final_t, false, 0, 0, rs, qs, ks, vs,
                       lg->md.as<_Float16>() + tok * 256, w->match_w, w->match_b, lg->logsig.as<float>() + tok, st, nullptr, live, lm);
       if (lg->cap_n) {
-        SSHIP_HIP_CHECK(cap(i, kCap_X_OUT, x));
         if (i + 1 == kLgLayers) {
+          SSHIP_HIP_CHECK(cap(i, kCap_X_OUT, x));
           SSHIP_HIP_CHECK(cap(i, kCap_MD, lg->md.as<_Float16>()));
           for (int c = 0; c < lg->cap_n; ++c) {
             const int p = lg->cap_pairs[c];
@@ -2241,6 +2341,10 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
           }
         }
       }
+    }
+    if (lg->cap_n && (adaptive || width)) {  // test-only capture: the counters and the verdicts of the stop rule, as the layer stack left them
+      SSHIP_HIP_CHECK(cap_words(lay.cnt, dep.cnt, 8));
+      SSHIP_HIP_CHECK(cap_words(lay.lr, dep.layers_run, 1));
     }
     SSHIP_HIP_CHECK(hipGetLastError());
     return SSHIP_OK;
@@ -2292,6 +2396,18 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
   if (adaptive)  // md / logsig of the pairs that stopped early, from the assignment head of the layer they stopped after
     launch_lg_exit_head(x, lg->NP, pairs, lg->dep.as<int>() + (size_t)lg->max_pairs * 8, w->head_wt, w->head_b, w->head_mw, w->head_mb,
                         lg->md.as<_Float16>(), lg->logsig.as<float>(), s);
+  if (lg->cap_n && (adaptive || width)) {  // test-only capture: md / logsig as the assignment reads them (after the exit head)
+    const size_t pair_halfs = (size_t)2 * lg->NP * 256;
+    for (int c = 0; c < lg->cap_n; ++c) {
+      const int p = lg->cap_pairs[c];
+      if (p >= pairs) continue;
+      SSHIP_HIP_CHECK(hipMemcpyAsync(lg->cap_amd.as<_Float16>() + (size_t)c * pair_halfs, lg->md.as<_Float16>() + (size_t)p * pair_halfs,
+                                     pair_halfs * 2, hipMemcpyDeviceToDevice, s));
+      SSHIP_HIP_CHECK(hipMemcpyAsync(lg->cap_als.as<float>() + (size_t)c * 2 * lg->NP, lg->logsig.as<float>() + (size_t)p * 2 * lg->NP,
+                                     (size_t)2 * lg->NP * 4, hipMemcpyDeviceToDevice, s));
+    }
+    lg->cap_last_assigned = true;
+  }
   if (width) {
     // the assignment of the live sets (row a = the a-th surviving keypoint), then back to keypoint indices through ind
     const int* wlen = lg->wid.as<int>();
@@ -2299,6 +2415,16 @@ static int lg_forward(sship_lg* lg, const float* kp, int kp_stride, int kp_seq_s
                      lg->m0c.as<int32_t>(), lg->ms0c.as<float>(), 0.1f /* filter_threshold */, 0, s);
     SSHIP_HIP_CHECK(hipMemsetAsync(m0, 0xff, (size_t)pairs * lg->max_kp * 4, s));
     SSHIP_HIP_CHECK(hipMemsetAsync(ms0, 0, (size_t)pairs * lg->max_kp * 4, s));
+    if (lg->cap_n) {  // test-only capture: the matches of the live sets, as the scatter reads them
+      const LgCapAd& lay = lg->cap_lay;
+      for (int c = 0; c < lg->cap_n; ++c) {
+        const int p = lg->cap_pairs[c];
+        if (p >= pairs) continue;
+        int* dst = lg->cap_ad.as<int>() + (size_t)c * lay.words;
+        SSHIP_HIP_CHECK(hipMemcpyAsync(dst + lay.mc, lg->m0c.as<int32_t>() + (size_t)p * lg->max_kp, (size_t)lg->max_kp * 4, hipMemcpyDeviceToDevice, s));
+        SSHIP_HIP_CHECK(hipMemcpyAsync(dst + lay.msc, lg->ms0c.as<float>() + (size_t)p * lg->max_kp, (size_t)lg->max_kp * 4, hipMemcpyDeviceToDevice, s));
+      }
+    }
     launch_lg_width_scatter(wlen, wlen + 4 * (size_t)lg->max_pairs, lg->NP, pairs, lg->max_kp, lg->m0c.as<int32_t>(), lg->ms0c.as<float>(), m0, ms0, s);
     SSHIP_HIP_CHECK(hipGetLastError());
     g_timer.mark("fe_lg_stereo_match:assign_filter", s);

@@ -191,6 +191,18 @@ class LightGlue:
         _lib.check(_lib.lib().sship_lg_debug_stage(self._h, int(slot), int(layer), st, out.ctypes.data, out.size))
         return out
 
+    # the adaptive modes' state under capture (include/sship.h sship_lg_debug_adaptive): item ids as in the header
+    ADAPTIVE_ITEMS = ("lens", "rope", "ind", "prune", "wlen", "chg", "cnt", "layers_run", "md", "logsig", "matches_c", "mscores_c")
+
+    def debug_adaptive(self, slot: int, item, layer: int = 0) -> np.ndarray:
+        """Item `item` (name or id) of the pair captured in `slot`, last call, with adaptive depth and / or width on."""
+        it = self.ADAPTIVE_ITEMS.index(item) if isinstance(item, str) else int(item)
+        npad, k = (self.max_keypoints + 31) // 32 * 32, self.max_keypoints
+        shape = ((2,), (2, npad, 64), (2, npad), (2, npad), (2,), (2,), (8,), (1,), (2, npad, 256), (2, npad), (k,), (k,))[it]
+        out = np.zeros(shape, np.float32 if it in (1, 8, 9, 11) else np.int32)
+        _lib.check(_lib.lib().sship_lg_debug_adaptive(self._h, int(slot), int(layer), it, out.ctypes.data, out.size))
+        return out
+
     def match_batch_device(self, kp, n, desc, matches0=None, mscores0=None, stream=None):
         """kp f32 [2P,K,3], n i32 [2P], desc f16 [2P,K,256] (torch CUDA) -> matches0 i32 [P,K], mscores0 f32 [P,K]."""
         import torch

@@ -319,7 +319,11 @@ def test_capture_abi(hip, weights_dir):
     assert stage(0, 8, 11, ls) == _lib.OK and stage(0, 8, 11) == _lib.ERR_INVALID and stage(0, 8, 10) == _lib.OK   # sizes are exact
     m.set_width_confidence(0.9)
     r = m.match(R.to_pixels(prob[0]), prob[1], R.to_pixels(prob[2]), prob[3])
-    assert len(r.matches0) == 0 and "stage capture" in m.last_error            # capture + adaptive width: refused
+    assert len(r.matches0) == 7, m.last_error                                   # capture + adaptive width: the call succeeds,
+    assert stage(0, 0, 0) == _lib.OK and stage(0, 8, 11, ls) == _lib.OK         # the stages can be read back,
+    wl = np.zeros(2, np.int32)
+    assert L.sship_lg_debug_adaptive(m._h, 0, 0, 4, wl.ctypes.data, 2) == _lib.OK and 0 <= wl[0] <= 7 and 0 <= wl[1] <= 5   # and so the width state
+    assert np.array_equal(buf[0][:7], prob[1][:7])                              # layer 0 x_in of the captured pair: the descriptors
     m.set_width_confidence(-1.0)
     m.debug_capture([])
     assert stage(0, 0, 0) == _lib.ERR_INVALID                                   # off again
