@@ -20,7 +20,7 @@
 // build:  g++ -std=c++17 -O2 -Iinclude examples/frontend_benchmark.cc -o frontend_benchmark
 //             -Lsuperslam_amd/lib -lsuperslam_hip -Wl,-rpath,$PWD/superslam_amd/lib -Wl,-rpath,/opt/rocm/lib -lpthread -lz
 // run:    ./frontend_benchmark --sp sp.safetensors --lg lg.safetensors (--sequence DIR | --synthetic 200) [--keyframe-match]
-//                              [--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--subpixel] [--matcher lightglue|nn]
+//                              [--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--subpixel] [--balanced PX] [--matcher lightglue|nn]
 //                              [--dump-keypoints FILE] [--stereo-gate MIN,MAX,ROW] [--track-window R] [--dump DIR] [--strict-ahead]
 //
 // --matcher nn: the mutual nearest-neighbour matcher (superslam_hip::NNMatcher, hloc's NN-mutual) in LightGlue's place - same
@@ -30,6 +30,7 @@
 // temporal match of --keyframe-match then uses a second NNMatcher without a gate, or with --track-window R one gated (-R, R, -R, R).
 // --bilinear: descriptors by upstream SuperPoint's bilinear sampling (SSHIP_DESC_BILINEAR) instead of the reference's nearest-cell gather.
 // --subpixel: keypoints refined by the log-parabola peak fit (SSHIP_KP_SUBPIXEL) instead of the reference's integer score-map pixels.
+// --balanced PX: keypoints spread over buckets of PX score-map pixels (SSHIP_SELECT_BALANCED) instead of the highest scores of the whole image.
 // --dump-keypoints FILE: the first frame's keypoints as int32 n_left, n_right | f32 [n_left][3] (x, y, score) | f32 [n_right][3].
 //
 // Cross-frame pipelining (default with the ring; --no-pipeline turns it off): as soon as frame t's extraction has returned, frame
@@ -143,7 +144,7 @@ struct Source {
 int main(int argc, char** argv) {
   std::string sp_path, lg_path, matcher_name = "lightglue", dump_path, dump_dir;
   Source src;
-  int max_kp = 600, border = 4;
+  int max_kp = 600, border = 4, balanced_px = 0;
   double thr = 0.005;
   bool keyframe = false, use_ring = true, pipeline = true, bilinear = false, subpixel = false, stereo_gate = false, strict_ahead = false, dump_frames = false;
   float gate_min = 0.f, gate_max = 0.f, gate_row = 0.f, track_window = -1.f;
@@ -162,6 +163,10 @@ int main(int argc, char** argv) {
     else if (a == "--no-pipeline") pipeline = false;
     else if (a == "--bilinear") bilinear = true;
     else if (a == "--subpixel") subpixel = true;
+    else if (a == "--balanced") {
+      balanced_px = std::atoi(next());
+      if (balanced_px < 8 || balanced_px > 65535) { std::fprintf(stderr, "--balanced needs a bucket size PX in [8, 65535]\n"); return 2; }
+    }
     else if (a == "--dump-keypoints") dump_path = next();
     else if (a == "--dump") { dump_dir = next(); dump_frames = true; }
     else if (a == "--strict-ahead") strict_ahead = true;
@@ -188,7 +193,7 @@ int main(int argc, char** argv) {
   }
   if (bad_usage) {
     std::fprintf(stderr, "usage: %s --sp W.safetensors --lg W.safetensors (--sequence DIR | --synthetic N) [--keyframe-match] "
-                         "[--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--subpixel] [--matcher lightglue|nn] "
+                         "[--max-kp 600] [--threshold 0.005] [--border 4] [--no-ring] [--no-pipeline] [--bilinear] [--subpixel] [--balanced PX] [--matcher lightglue|nn] "
                          "[--dump-keypoints FILE] [--stereo-gate MIN,MAX,ROW] [--track-window R] [--dump DIR] [--strict-ahead] "
                          "(the gates need --matcher nn; --strict-ahead needs the ring and pipelining)\n", argv[0]);
     return 2;
@@ -226,6 +231,7 @@ int main(int argc, char** argv) {
   }
   if (bilinear) extractor.set_descriptor_sampling(SSHIP_DESC_BILINEAR);  // kept, applied by initialize()
   if (subpixel) extractor.set_keypoint_refinement(SSHIP_KP_SUBPIXEL);
+  if (balanced_px) extractor.set_keypoint_selection(SSHIP_SELECT_BALANCED, balanced_px);
   if (!extractor.initialize() || !(use_nn ? nn.initialize() : lightglue.initialize()) || (gated && keyframe && !nn_track.initialize())) {
     std::fprintf(stderr, "initialisation failed: %s\n", sship_last_error());
     return 1;
@@ -366,6 +372,7 @@ int main(int argc, char** argv) {
   if (stereo_gate) std::printf("stereo gate      : %g <= uL - uR <= %g, |vL - vR| <= %g\n", gate_min, gate_max, gate_row);
   if (track_window >= 0.f) std::printf("track window     : +-%g px\n", track_window);
   if (subpixel) std::printf("keypoints        : sub-pixel (SSHIP_KP_SUBPIXEL)\n");
+  if (balanced_px) std::printf("selection        : balanced over %d px buckets (SSHIP_SELECT_BALANCED)\n", balanced_px);
   if (use_ring) std::printf("pipelined        : %s (%ld of %zu extractions enqueued one frame ahead)\n", pipeline ? "yes" : "no", submitted_ahead, ms.size());
   std::printf("per-frame ms      mean=%.2f p50=%.2f p95=%.2f max=%.2f\n", mean, percentile(ms, 0.50), percentile(ms, 0.95), percentile(ms, 1.0));
   std::printf("throughput        : %.2f fps over %.1fs wall\n", wall > 0 ? ms.size() / wall : 0.0, wall);

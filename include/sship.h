@@ -157,6 +157,11 @@ int sship_nms(const float* scores_dev, int batch, int h, int w, int radius, floa
 int sship_select_topk(const float* scores_dev, int score_h, int score_w, int input_h, int input_w,
                       double thr, int border, int max_kp, int desc_h, int desc_w, float* kp_xys_dev,
                       int* cell_h_dev, int* cell_w_dev, int* n_dev, int* n_candidates_dev, void* stream);
+/* The same stage with the spatially balanced rule stated at sship_sp_set_keypoint_selection below (SSHIP_SELECT_BALANCED, G = bucket_px in
+ * [8, 65535]): same candidates, same outputs and output order, n_candidates = M.  Bad arguments are refused before any device is touched. */
+int sship_select_topk_balanced(const float* scores_dev, int score_h, int score_w, int input_h, int input_w,
+                               double thr, int border, int max_kp, int bucket_px, int desc_h, int desc_w, float* kp_xys_dev,
+                               int* cell_h_dev, int* cell_w_dev, int* n_dev, int* n_candidates_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * SuperPoint extractor - include/SuperPoint.h:36-54, src/SuperPoint.cc
@@ -220,6 +225,35 @@ int sship_sp_descriptor_sampling(const sship_sp* sp);
 enum { SSHIP_KP_INTEGER = 0, SSHIP_KP_SUBPIXEL = 1 };
 int sship_sp_set_keypoint_refinement(sship_sp* sp, int mode);
 int sship_sp_keypoint_refinement(const sship_sp* sp);   /* NULL -> SSHIP_KP_INTEGER */
+/* Which candidates become keypoints.  Per handle; it applies to every call made after it returns, through every entry point that yields
+ * keypoints: sship_sp_extract, _extract_stereo, _extract_stereo_ring, _ring_submit, _infer_host, _extract_batch_device and
+ * sship_frontend_batch_device.
+ *   SSHIP_SELECT_TOPK (default): the reference's rule, the max_keypoints highest scores of the whole image (src/SuperPoint.cc:696-719) -
+ *     today's path, bit for bit, with the launches it always made.  bucket_px is ignored.
+ *   SSHIP_SELECT_BALANCED: the keypoints are spread over square buckets of G = bucket_px score-map pixels.  One more launch
+ *     (k_select_balanced, between the candidate compaction and the top-k), in this mode only.  The reference has no counterpart.
+ * The rule.  The candidates of an image are exactly the default mode's: the pixels (h, w) of the H x W score map that survive NMS, lie
+ * inside the border and have score > thr, each with the 64-bit key k = (bits(score) << 32) | (h * W + w); M is their number.
+ *   Bucket:  the bucket of a candidate is (h / G, w / G) by integer division; the last row and column of buckets may be ragged.
+ *   Rank:    r(c) = the number of candidates in the same bucket with a key greater than k(c); the best of every occupied bucket has rank 0.
+ *   Selection order: c comes before c' if r(c) < r(c'), or if the ranks are equal and k(c) > k(c').  The selected set is the first
+ *            K = min(M, max_keypoints) candidates in this order.
+ *   Output order: the selected set is written in DESCENDING KEY ORDER, the default mode's order; keypoints, scores, cells and n have the
+ *            layout and meaning they always had, and n_candidates stays M.
+ * Everything is integer comparison of existing bits: there is no tolerance in this mode.  Three consequences:
+ *   - n does not depend on the mode.
+ *   - If M <= max_keypoints, the output is bit-identical to the default mode.
+ *   - If G >= max(H, W), there is one bucket, and the output is bit-identical to the default mode.
+ * The mode is independent of descriptor sampling and keypoint refinement: both act on the balanced set as they act on the default one.
+ * bucket_px must be in [8, 65535] for SSHIP_SELECT_BALANCED (8 = one descriptor cell; nothing finer is useful behind a 9 x 9 NMS).
+ * An unknown mode, a bucket_px out of range or a NULL handle -> SSHIP_ERR_INVALID, mode and bucket unchanged; also SSHIP_ERR_INVALID while
+ * a sship_sp_ring_submit is pending (collect it first).  The setter allocates nothing: the mode's buffers (the selected keys, and a
+ * workspace of 8 bytes per score-map pixel plus 12 per cell and image) are sized by the next call, where the handle's other selection
+ * buffers are.  Cost: the kernel keeps an image's keys in LDS when it has at most 8192 candidates and 1024 buckets; beyond that it works in
+ * the workspace, where a bucket of s candidates costs up to s^2 key comparisons. */
+enum { SSHIP_SELECT_TOPK = 0, SSHIP_SELECT_BALANCED = 1 };
+int sship_sp_set_keypoint_selection(sship_sp* sp, int mode, int bucket_px);
+int sship_sp_keypoint_selection(const sship_sp* sp, int* bucket_px_out);   /* NULL handle -> SSHIP_SELECT_TOPK; bucket_px_out may be NULL */
 
 /* SuperPoint::extract (src/SuperPoint.cc:895-899 -> infer_device :597-676): host u8 image, 1 or 3 (BGR)
  * channels, row stride in bytes.  Synchronous. */
@@ -1426,7 +1460,9 @@ int sship_sp_bench_layer(sship_sp* sp, int layer, int batch, int h, int w, int i
 /* (layer ids 12-14 are the memory-bound stages of the same handle: 12 = softmax + depth-to-space + NMS + threshold +
  * candidate compaction, 13 = top-k, 14 = descriptor head at the selected keypoints (nearest or bilinear, as the handle is set); *macs = 0 for them.
  * 15 = conv2a + conv2b + pool as the ONE launch throughput batches run instead of layers 2 and 3 (csrc/conv_fuse2.hip; *macs = both layers').
- * 16 = the sub-pixel refinement of the selected keypoints (k_kp_refine), timed whatever mode the handle is in; *macs = 0.)
+ * 16 = the sub-pixel refinement of the selected keypoints (k_kp_refine), timed whatever mode the handle is in; *macs = 0.
+ * 17 = the balanced selection alone (k_select_balanced) on the candidates of the handle's last selection, with the handle's bucket_px
+ * (32 until set), timed whatever mode the handle is in; *macs = 0.)
  *
  * Same for one stage of the matcher, over the state the last match call left on this handle, timed with hipEvents on the
  * handle's stream: 0 first Wqkv projection, 1 self attention, 2 cross attention (both directions), 3 SelfBlock FFN + the

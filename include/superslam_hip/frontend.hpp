@@ -158,8 +158,32 @@ public:
     if (keypoint_refinement_ != SSHIP_KP_INTEGER && sship_sp_set_keypoint_refinement(sp_, keypoint_refinement_) != SSHIP_OK) {
       last_error_ = sship_last_error(); sship_sp_destroy(sp_); sp_ = nullptr; return false;
     }
+    if (keypoint_selection_ != SSHIP_SELECT_TOPK && sship_sp_set_keypoint_selection(sp_, keypoint_selection_, bucket_px_) != SSHIP_OK) {
+      last_error_ = sship_last_error(); sship_sp_destroy(sp_); sp_ = nullptr; return false;
+    }
     pool_.reset(new DescriptorPool(sship_sp_pool(sp_), max_keypoints_, descriptor_dim));
     return true;
+  }
+  // Which candidates become keypoints (include/sship.h): SSHIP_SELECT_TOPK (default, the reference's highest scores of the whole image) or
+  // SSHIP_SELECT_BALANCED (spread over square buckets of bucket_px score-map pixels, 8 .. 65535; ignored for SSHIP_SELECT_TOPK).  The count n
+  // does not depend on the mode.  Before initialize() the arguments are validated, kept and applied by initialize(); afterwards they apply
+  // to the calls after this one.  false + last_error() for any other mode, a bucket out of range or while a ring submission is pending
+  // (mode and bucket are unchanged).
+  bool set_keypoint_selection(int mode, int bucket_px = 32) {
+    if (sp_ && sship_sp_set_keypoint_selection(sp_, mode, bucket_px) != SSHIP_OK) { last_error_ = sship_last_error(); return false; }
+    if (!sp_ && mode != SSHIP_SELECT_TOPK && mode != SSHIP_SELECT_BALANCED) {
+      last_error_ = "set_keypoint_selection: mode must be 0 (top-k) or 1 (balanced)"; return false;
+    }
+    if (!sp_ && mode == SSHIP_SELECT_BALANCED && (bucket_px < 8 || bucket_px > 65535)) {
+      last_error_ = "set_keypoint_selection: bucket_px must be in [8, 65535]"; return false;
+    }
+    keypoint_selection_ = mode;
+    if (mode == SSHIP_SELECT_BALANCED) bucket_px_ = bucket_px;
+    return true;
+  }
+  int keypoint_selection(int* bucket_px_out = nullptr) const {
+    if (bucket_px_out) *bucket_px_out = bucket_px_;
+    return keypoint_selection_;
   }
   // Where a keypoint is reported (include/sship.h): SSHIP_KP_INTEGER (default, the reference's integer score-map pixel) or
   // SSHIP_KP_SUBPIXEL (the log-parabola peak fit on the detector's log-scores).  x and y only: counts, order, scores and descriptors do
@@ -280,6 +304,7 @@ private:
   int remove_borders_;
   int descriptor_sampling_ = SSHIP_DESC_NEAREST;
   int keypoint_refinement_ = SSHIP_KP_INTEGER;
+  int keypoint_selection_ = SSHIP_SELECT_TOPK, bucket_px_ = 32;
   sship_sp* sp_ = nullptr;
   std::unique_ptr<DescriptorPool> pool_;
   std::string last_error_;

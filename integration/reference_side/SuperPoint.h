@@ -86,6 +86,15 @@ public:
     return ok;
   }
   int keypoint_refinement() const { return impl_.keypoint_refinement(); }
+  // Spatially balanced keypoint selection (include/sship.h: SSHIP_SELECT_BALANCED, buckets of bucket_px score-map pixels); no counterpart
+  // in the reference, which takes the highest scores of the whole image.  Off (SSHIP_SELECT_TOPK) unless called; kept before initialize()
+  // and applied by it.
+  bool set_keypoint_selection(int mode, int bucket_px = 32) {
+    const bool ok = impl_.set_keypoint_selection(mode, bucket_px);
+    if (!ok) SLOG_ERROR("SuperPoint(HIP): {}", impl_.last_error());
+    return ok;
+  }
+  int keypoint_selection(int* bucket_px_out = nullptr) const { return impl_.keypoint_selection(bucket_px_out); }
   bool infer(const cv::Mat& image, std::vector<cv::KeyPoint>& keypoints, cv::Mat& descriptors) {
     cv::Mat keep;
     std::vector<superslam_hip::KeyPoint> kp;

@@ -118,6 +118,9 @@ _SIGS = {
     "sship_sp_descriptor_sampling": (ip, [vp]),
     "sship_sp_set_keypoint_refinement": (ip, [vp, ip]),
     "sship_sp_keypoint_refinement": (ip, [vp]),
+    "sship_sp_set_keypoint_selection": (ip, [vp, ip, ip]),
+    "sship_sp_keypoint_selection": (ip, [vp, C.POINTER(ip)]),
+    "sship_select_topk_balanced": (ip, [vp, ip, ip, ip, ip, C.c_double, ip, ip, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_extract": (ip, [vp, vp, ip, ip, ip, ip, C.POINTER(Features)]),
     "sship_sp_extract_stereo": (ip, [vp, vp, vp, ip, ip, ip, ip, C.POINTER(Features), C.POINTER(Features)]),
     "sship_sp_infer_host": (ip, [vp, vp, ip, ip, ip, ip, vp, vp, C.POINTER(ip)]),

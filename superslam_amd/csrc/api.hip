@@ -739,6 +739,9 @@ struct sship_sp {
   DevBuf kp, cell_h, cell_w, n_dev, desc_stage, gray_in;
   int desc_sampling = SSHIP_DESC_NEAREST;  // sship_sp_set_descriptor_sampling
   int kp_refinement = SSHIP_KP_INTEGER;    // sship_sp_set_keypoint_refinement
+  int kp_selection = SSHIP_SELECT_TOPK;    // sship_sp_set_keypoint_selection
+  int bucket_px = 32;                      // G of the balanced mode (and of sship_sp_bench_layer 17 in either mode)
+  DevBuf sel, sel_count, sel_ws;           // balanced mode only: [B, max_kp] selected keys, [B] their counts, k_select_balanced's workspace
   DevBuf pix;                              // [B, max_kp] score-map pixels of the keypoints (h << 16 | w): written by k_topk in bilinear / sub-pixel mode only
   PinBuf h_kp, h_n, h_img;
   int cap = 0;
@@ -762,7 +765,45 @@ static void sp_shapes(int H, int W, int& H2, int& W2, int& H4, int& W4, int& Hc,
   H2 = H / 2; W2 = W / 2; H4 = H2 / 2; W4 = W2 / 2; Hc = H4 / 2; Wc = W4 / 2;  // MaxPool2d(2,2) floors
 }
 
+// Balanced selection: the second key list, its counters and the kernel's workspace, for B images of a map of Hc x Wc cells.  The workspace is
+// sized for the finest bucket (8 px: one bucket per cell), so a later change of bucket_px never allocates.  Grows only; the default mode never
+// calls it, and a handle that never leaves the default mode never holds these buffers.
+struct SelWs { unsigned long long* seg; unsigned long long* bnd; int* tab; };
+static size_t sel_ws_layout(const DevBuf& ws, int B, int cap, int nb_max, SelWs* out) {
+  const size_t seg = (size_t)B * cap * 8, bnd = (size_t)B * nb_max * 8, tab = (size_t)B * nb_max * 4;
+  if (out) {
+    char* p = static_cast<char*>(ws.p);
+    out->seg = reinterpret_cast<unsigned long long*>(p);
+    out->bnd = reinterpret_cast<unsigned long long*>(p + seg);
+    out->tab = reinterpret_cast<int*>(p + seg + bnd);
+  }
+  return seg + bnd + tab;
+}
+static int sp_ensure_balanced(sship_sp* sp, int B, int Hc, int Wc) {
+  const int mk = sp->cfg.max_keypoints;
+  SSHIP_HIP_CHECK(sp->sel.ensure((size_t)B * mk * 8));
+  SSHIP_HIP_CHECK(sp->sel_count.ensure((size_t)B * 4));
+  SSHIP_HIP_CHECK(sp->sel_ws.ensure(sel_ws_layout(sp->sel_ws, B, Hc * 8 * Wc * 8, Hc * Wc, nullptr)));
+  return SSHIP_OK;
+}
+static SelectBalancedArgs select_balanced_args(const unsigned long long* cand, const int* cand_count, int cap, int max_kp, int score_h, int score_w,
+                                               int bucket_px, unsigned long long* sel, int* sel_count, const SelWs& ws) {
+  SelectBalancedArgs q{};
+  q.cand = cand; q.cand_count = cand_count; q.cap = cap; q.max_kp = max_kp; q.score_w = score_w; q.bucket_px = bucket_px;
+  q.nbx = (score_w + bucket_px - 1) / bucket_px;
+  q.nb = q.nbx * ((score_h + bucket_px - 1) / bucket_px);
+  q.sel = sel; q.sel_count = sel_count; q.n_cand_out = nullptr;
+  q.ws_seg = ws.seg; q.ws_bnd = ws.bnd; q.ws_tab = ws.tab;
+  return q;
+}
+
 static int sp_ensure(sship_sp* sp, int B, int H, int W) {
+  if (sp->kp_selection == SSHIP_SELECT_BALANCED) {
+    int H2, W2, H4, W4, Hc, Wc;
+    sp_shapes(H, W, H2, W2, H4, W4, Hc, Wc);
+    if (Hc >= 1 && Wc >= 1)
+      if (int rc = sp_ensure_balanced(sp, B > sp->wsB ? B : sp->wsB, Hc, Wc)) return rc;
+  }
   if (B <= sp->wsB && H == sp->wsH && W == sp->wsW) return SSHIP_OK;
   int H2, W2, H4, W4, Hc, Wc;
   sp_shapes(H, W, H2, W2, H4, W4, Hc, Wc);
@@ -941,6 +982,19 @@ static int sp_select(sship_sp* sp, int B, int H, int W, float* scores_out, float
   t.desc_h = Hc; t.desc_w = Wc; t.kp_xys = kp_out; t.cell_h = sp->cell_h.as<int>(); t.cell_w = sp->cell_w.as<int>();
   t.n_out = n_out; t.n_cand_out = n_cand_out; t.reset_count = a.cand_count;
   t.pix = sp_wants_pix(sp) ? sp->pix.as<int>() : nullptr;
+  if (sp->kp_selection == SSHIP_SELECT_BALANCED) {
+    // one more launch, in this mode only: k_select_balanced leaves the K keys the rule selects in sp->sel, and k_topk sorts and emits THAT
+    // list.  It still clears the original counter (reset_count) for the next call; the candidate count M is reported by the new kernel.
+    SelWs ws;
+    if (sp->sel.bytes < (size_t)sp->wsB * t.max_kp * 8 || sp->sel_ws.bytes < sel_ws_layout(sp->sel_ws, sp->wsB, sp->cap, Hc * Wc, &ws))
+      return fail(SSHIP_ERR_INVALID, "balanced selection: the workspace has not been sized for this shape");  // sp_ensure does; never taken
+    SelectBalancedArgs q = select_balanced_args(a.cand, a.cand_count, sp->cap, t.max_kp, Hc * 8, Wc * 8, sp->bucket_px,
+                                                sp->sel.as<unsigned long long>(), sp->sel_count.as<int>(), ws);
+    q.n_cand_out = n_cand_out;
+    SSHIP_HIP_CHECK(launch_select_balanced(q, B, s));
+    g_timer.mark_fine("sp_extract_stereo:select/balanced", s);
+    t.cand = q.sel; t.cand_count = q.sel_count; t.cap = t.max_kp; t.n_cand_out = nullptr;
+  }
   launch_topk(t, B, s);
   SSHIP_HIP_CHECK(hipGetLastError());
   sp->cand_zero_n = B;
@@ -1116,6 +1170,8 @@ extern "C" int sship_sp_debug_select(sship_sp* sp, const float* logits_dev, int 
     if (int rc = sp_ensure(sp, batch, h, w)) return rc;
   } else if (!sp->logits.p || batch > sp->wsB || h != sp->wsH || w != sp->wsW) {
     return fail(SSHIP_ERR_INVALID, "sp_debug_select: run the network at this shape first");
+  } else if (sp->kp_selection == SSHIP_SELECT_BALANCED) {  // the mode may have been set after that network call
+    if (int rc = sp_ensure_balanced(sp, sp->wsB, h / 8, w / 8)) return rc;
   }
   SSHIP_HIP_CHECK(hipDeviceSynchronize());  // the logits may come from any stream
   hipStream_t s = sp->stream;
@@ -1155,6 +1211,60 @@ extern "C" int sship_sp_set_keypoint_refinement(sship_sp* sp, int mode) {
   return SSHIP_OK;
 }
 extern "C" int sship_sp_keypoint_refinement(const sship_sp* sp) { return sp ? sp->kp_refinement : SSHIP_KP_INTEGER; }
+extern "C" int sship_sp_set_keypoint_selection(sship_sp* sp, int mode, int bucket_px) {
+  if (!sp) return fail(SSHIP_ERR_INVALID, "sp_set_keypoint_selection: null handle");
+  if (mode != SSHIP_SELECT_TOPK && mode != SSHIP_SELECT_BALANCED)
+    return fail(SSHIP_ERR_INVALID, "sp_set_keypoint_selection: mode must be 0 (top-k) or 1 (balanced)");
+  if (mode == SSHIP_SELECT_BALANCED && (bucket_px < 8 || bucket_px > 65535))
+    return fail(SSHIP_ERR_INVALID, "sp_set_keypoint_selection: bucket_px must be in [8, 65535]");
+  for (const auto& pd : sp->ring.pending)
+    if (pd.active) return fail(SSHIP_ERR_INVALID, "sp_set_keypoint_selection: a ring submission is pending (collect it with sship_sp_extract_stereo_ring first)");
+  // no allocation here: the next call's sp_ensure sizes the mode's buffers where it sizes the other selection buffers
+  sp->kp_selection = mode;
+  if (mode == SSHIP_SELECT_BALANCED) sp->bucket_px = bucket_px;
+  return SSHIP_OK;
+}
+extern "C" int sship_sp_keypoint_selection(const sship_sp* sp, int* bucket_px_out) {
+  if (bucket_px_out) *bucket_px_out = sp ? sp->bucket_px : 0;
+  return sp ? sp->kp_selection : SSHIP_SELECT_TOPK;
+}
+// stage twin of sship_select_topk: threshold scan -> k_select_balanced -> k_topk on the selected list
+extern "C" int sship_select_topk_balanced(const float* scores, int score_h, int score_w, int input_h, int input_w, double thr, int border,
+                                          int max_kp, int bucket_px, int desc_h, int desc_w, float* kp_xys, int* cell_h, int* cell_w,
+                                          int* n_dev, int* n_cand_dev, void* stream) {
+  bind_thread();
+  if (!scores || !kp_xys || !cell_h || !cell_w || !n_dev || score_h <= 0 || score_w <= 0)
+    return fail(SSHIP_ERR_INVALID, "select_topk_balanced: bad arguments");
+  if (max_kp <= 0 || max_kp > kMaxKp) return fail(SSHIP_ERR_INVALID, "select_topk_balanced: max_kp must be in [1, 4096]");
+  if (bucket_px < 8 || bucket_px > 65535) return fail(SSHIP_ERR_INVALID, "select_topk_balanced: bucket_px must be in [8, 65535]");
+  if (int rc = require_device()) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int cap = score_h * score_w;
+  DevBuf cand, cnt, sel, ws_buf;  // cnt: the candidate counter, then the selected count
+  SSHIP_HIP_CHECK(cand.ensure((size_t)cap * 8));
+  SSHIP_HIP_CHECK(cnt.ensure(8));
+  SSHIP_HIP_CHECK(sel.ensure((size_t)max_kp * 8));
+  const int nb_max = ((score_h + 7) / 8) * ((score_w + 7) / 8);
+  SSHIP_HIP_CHECK(ws_buf.ensure(sel_ws_layout(ws_buf, 1, cap, nb_max, nullptr)));
+  SelWs ws;
+  sel_ws_layout(ws_buf, 1, cap, nb_max, &ws);
+  SSHIP_HIP_CHECK(hipMemsetAsync(cnt.p, 0, 8, s));
+  launch_threshold_scan(scores, score_h, score_w, threshold_as_float(thr), border, cand.as<unsigned long long>(), cnt.as<int>(), cap, s);
+  SelectBalancedArgs q = select_balanced_args(cand.as<unsigned long long>(), cnt.as<int>(), cap, max_kp, score_h, score_w, bucket_px,
+                                              sel.as<unsigned long long>(), cnt.as<int>() + 1, ws);
+  q.n_cand_out = n_cand_dev;
+  SSHIP_HIP_CHECK(launch_select_balanced(q, 1, s));
+  TopkArgs t{};
+  t.cand = q.sel; t.cand_count = q.sel_count; t.cap = max_kp; t.max_kp = max_kp;
+  t.score_w = score_w;
+  t.scale_x = static_cast<float>(input_w) / score_w;
+  t.scale_y = static_cast<float>(input_h) / score_h;
+  t.desc_h = desc_h; t.desc_w = desc_w; t.kp_xys = kp_xys; t.cell_h = cell_h; t.cell_w = cell_w; t.n_out = n_dev;
+  launch_topk(t, 1, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  SSHIP_HIP_CHECK(hipStreamSynchronize(s));  // scratch buffers die with this scope
+  return SSHIP_OK;
+}
 
 extern "C" int sship_sp_extract_batch_device(sship_sp* sp, const uint8_t* imgs, int batch, int h, int w, void* desc_out,
                                              float* kp_out, int* n_out, void* stream) {
@@ -1214,7 +1324,7 @@ extern "C" int sship_mfma_probe(int random_operands, float* tflops) {
 extern "C" int sship_sp_bench_layer(sship_sp* sp, int layer, int batch, int h, int w, int iters, float* avg_ms,
                                     double* macs) {
   bind_thread();
-  if (!sp || !avg_ms || iters <= 0 || layer < 0 || layer > 16) return fail(SSHIP_ERR_INVALID, "sp_bench_layer: bad arguments");
+  if (!sp || !avg_ms || iters <= 0 || layer < 0 || layer > 17) return fail(SSHIP_ERR_INVALID, "sp_bench_layer: bad arguments");
   if (batch > sp->wsB || h != sp->wsH || w != sp->wsW) return fail(SSHIP_ERR_INVALID, "sp_bench_layer: run the network at this shape first");
   if (layer <= 1 && !sp->img_valid)
     return fail(SSHIP_ERR_INVALID, "sp_bench_layer: the handle holds no copy of the last input - make one call with sship_set_profiling(1) first "
@@ -1265,6 +1375,13 @@ extern "C" int sship_sp_bench_layer(sship_sp* sp, int layer, int batch, int h, i
         launch_topk(t, batch, s);
         return hipGetLastError();
       }
+      case 17: {  // balanced selection over the candidates left by the last selection (k_select_balanced alone), whatever mode the handle is in
+        SelWs ws;
+        sel_ws_layout(sp->sel_ws, sp->wsB, sp->cap, Hc * Wc, &ws);
+        const SelectBalancedArgs q = select_balanced_args(sp->cand.as<unsigned long long>(), sp->cand_count.as<int>(), sp->cap, sp->cfg.max_keypoints,
+                                                          Hc * 8, Wc * 8, sp->bucket_px, sp->sel.as<unsigned long long>(), sp->sel_count.as<int>(), ws);
+        return launch_select_balanced(q, batch, s);
+      }
       case 16:  // sub-pixel refinement of the selected keypoints (k_kp_refine), whatever mode the handle is in
         return sp_refine(sp, batch, Hc, Wc, sp->kp.as<float>(), sp->n_dev.as<int>(), static_cast<float>(w) / (Wc * 8), static_cast<float>(h) / (Hc * 8), s);
       default:  // 14: descriptor head at the selected keypoints (k_desc_head_sparse) into the staging rows
@@ -1273,6 +1390,11 @@ extern "C" int sship_sp_bench_layer(sship_sp* sp, int layer, int batch, int h, i
                          (size_t)sp->cfg.max_keypoints * 256, s);
     }
   };
+  if (layer == 17) {  // reads the candidates (layer 12 leaves them and their counts behind); its buffers exist only once the mode has been used
+    if (int rc = sp_ensure_balanced(sp, sp->wsB, Hc, Wc)) return rc;
+    layer = 12; SSHIP_HIP_CHECK(run());
+    layer = 17;
+  }
   if (layer == 13 || layer == 14 || layer == 16) {  // these read the selection's outputs: produce them once on this handle's own buffers
     const int keep = layer;
     layer = 12; SSHIP_HIP_CHECK(run());

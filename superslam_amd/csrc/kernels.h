@@ -44,6 +44,22 @@ struct TopkArgs {
   int* pix;                        // [B, max_kp] or null: the keypoint's score-map pixel (h << 16 | w), what the bilinear descriptor head samples at and k_kp_refine refines
 };
 void launch_topk(const TopkArgs& a, int B, hipStream_t s);
+// Spatially balanced selection (include/sship.h, SSHIP_SELECT_BALANCED): from the M candidate keys of an image to the K = min(M, max_kp)
+// keys the rule selects, in any order, as a second candidate list that k_topk then sorts and emits (k_select_balanced).
+struct SelectBalancedArgs {
+  const unsigned long long* cand;  // [B, cap]
+  const int* cand_count;           // [B]; read, never written: k_topk's reset_count still clears it
+  int cap, max_kp;
+  int score_w;                     // W of the score map (key idx = h*W + w)
+  int bucket_px, nbx, nb;          // G; buckets per row = ceil(W / G); buckets = nbx * ceil(H / G)
+  unsigned long long* sel;         // [B, max_kp] the selected keys ...
+  int* sel_count;                  // [B] ... and their number K (written, not accumulated: needs no clearing)
+  int* n_cand_out;                 // [B] or null: M before the cap, what k_topk reports in the default mode
+  unsigned long long* ws_seg;      // [B, cap] workspace: per-bucket segments, when the image does not fit the LDS path
+  unsigned long long* ws_bnd;      // [B, nb]  boundary list
+  int* ws_tab;                     // [B, nb]  bucket table
+};
+hipError_t launch_select_balanced(const SelectBalancedArgs& a, int B, hipStream_t s);
 // Sub-pixel keypoint refinement (include/sship.h, sship_sp_set_keypoint_refinement): the three-point log-parabola fit per axis on the
 // pre-NMS log-scores of the keypoint's pixel and its four neighbours.  Logit c of cell (cy, cx) of image b is
 // logits[b * img_stride + (cy * Wc + cx) * cell_stride + c * chan_stride]; keypoint i of image b is pix[b * max_kp + i].

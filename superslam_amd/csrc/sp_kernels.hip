@@ -535,6 +535,241 @@ void launch_topk(const TopkArgs& a, int B, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Spatially balanced selection (include/sship.h: SSHIP_SELECT_BALANCED; the reference has no counterpart).  One 1024-thread workgroup
+// per image, between the candidate compaction and k_topk: it reads the image's M candidate keys and writes the K = min(M, max_kp) keys
+// the rule selects, in any order, to a list of its own; k_topk then sorts and emits that list (M' = K: no radix pass runs there).
+//   1. histogram of the candidates over the buckets (tab[nb])
+//   2. R* = the smallest R with sum_b min(count_b, R + 1) >= K, by bisection on the bucket counts alone (no rank has to exist yet);
+//      with it n_less = #{r < R*} = sum_b min(count_b, R*), E = #{r == R*} = #{b : count_b > R*} and need = K - n_less (1 .. E)
+//   3. exclusive scan of the histogram; the keys are scattered into per-bucket segments (seg[M]), tab[b] ends as the END of segment b
+//   4. one thread per candidate counts the greater keys of its own segment, r, and stops once r > R* (such a candidate is out whatever
+//      r is): r < R* is selected, r == R* goes to the boundary list (at most one per bucket) unless need == E takes them all
+//   5. need < E: the `need` largest boundary keys, by the 8-pass MSB radix select of k_topk on that list
+// Everything is integer comparison of the 64-bit keys, which are distinct (the pixel index is the low word): the selected SET does not
+// depend on the order the atomics of steps 1, 3 and 4 resolve in.
+// LDS = true: segments, bucket table and boundary list in LDS (M <= SELB_LDS_KEYS and nb <= SELB_LDS_BUCKETS: 64 + 4 + 8 KiB, two
+// workgroups per CU).  LDS = false: the same code on the image's slice of a global workspace; step 4 is O(sum of segment^2) in the worst
+// case (one huge bucket whose keys arrive in ascending order) and about (K + nb) * (largest segment) * log otherwise.
+// ---------------------------------------------------------------------------------------------------
+constexpr int SELB_LDS_KEYS = 8192, SELB_LDS_BUCKETS = 1024;
+constexpr size_t SELB_SMEM = (size_t)SELB_LDS_KEYS * 8 + (size_t)SELB_LDS_BUCKETS * 8 + (size_t)SELB_LDS_BUCKETS * 4;
+
+struct SelbShared {
+  unsigned long long red[2][16];
+  int hist[256];
+  unsigned long long prefix;
+  int remaining, done, n_sel, n_bnd;
+};
+
+// sum over the workgroup (1024 threads); consecutive calls alternate between the two rows of `red`, so one barrier per call is enough
+__device__ __forceinline__ unsigned long long selb_block_sum(unsigned long long v, SelbShared& sh, int& par) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  if ((threadIdx.x & 63) == 0) sh.red[par][threadIdx.x >> 6] = v;
+  __syncthreads();
+  unsigned long long t = 0;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) t += sh.red[par][j];
+  par ^= 1;
+  return t;
+}
+
+template <bool LDS>
+__device__ __forceinline__ void selb_body(const SelectBalancedArgs& a, const unsigned long long* cand, int M, int K, unsigned long long* seg,
+                                          int* tab, unsigned long long* bnd, unsigned long long* out, SelbShared& sh) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int nb = a.nb, G = a.bucket_px, W = a.score_w, nbx = a.nbx;
+  auto bucket_of = [&](unsigned long long k) {
+    const unsigned idx = (unsigned)(k & 0xffffffffu);
+    const int h = (int)(idx / (unsigned)W), w = (int)(idx % (unsigned)W);
+    return min((h / G) * nbx + w / G, nb - 1);
+  };
+  int par = 0;
+  // 1. histogram
+  for (int i = tid; i < nb; i += 1024) tab[i] = 0;
+  if (tid == 0) { sh.n_sel = 0; sh.n_bnd = 0; }
+  __syncthreads();
+  for (int i = tid; i < M; i += 1024) atomicAdd(&tab[bucket_of(cand[i])], 1);
+  __syncthreads();
+  // every thread owns `chunk` consecutive buckets (one on the LDS path)
+  const int chunk = (nb + 1023) / 1024;
+  const int b0 = min(tid * chunk, nb), b1 = min(b0 + chunk, nb);
+  // 2. bisection for R*: f(R) = sum_b min(count_b, R + 1) is non-decreasing, f(hi) = M > K for hi = min(M, G * G) - 1 (no bucket holds more)
+  const long long gg = (long long)G * G;
+  int lo = 0, hi = (int)min((long long)M, gg) - 1;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    unsigned long long part = 0;
+    for (int i = b0; i < b1; ++i) part += (unsigned)min(tab[i], mid + 1);
+    if (selb_block_sum(part, sh, par) >= (unsigned long long)K) hi = mid; else lo = mid + 1;
+  }
+  const int Rs = lo;
+  int need, E;
+  {
+    unsigned long long part = 0;  // n_less in the high word, E in the low one (both < 2^31)
+    for (int i = b0; i < b1; ++i) { const int c = tab[i]; part += ((unsigned long long)(unsigned)min(c, Rs) << 32) | (unsigned)(c > Rs); }
+    const unsigned long long tot = selb_block_sum(part, sh, par);
+    need = K - (int)(tot >> 32); E = (int)(tot & 0xffffffffu);
+  }
+  const bool all_boundary = need >= E;
+  // 3. exclusive scan (thread sums: wave scan + the 16 wave totals), then the scatter
+  {
+    int loc = 0;
+    for (int i = b0; i < b1; ++i) loc += tab[i];
+    int incl = loc;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int up = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += up;
+    }
+    if (lane == 63) sh.red[par][tid >> 6] = (unsigned long long)incl;
+    __syncthreads();
+    int base = incl - loc;
+    for (int j = 0; j < (tid >> 6); ++j) base += (int)sh.red[par][j];
+    par ^= 1;
+    for (int i = b0; i < b1; ++i) { const int c = tab[i]; tab[i] = base; base += c; }
+  }
+  __syncthreads();
+  for (int i = tid; i < M; i += 1024) {
+    const unsigned long long k = cand[i];
+    const int pos = atomicAdd(&tab[bucket_of(k)], 1);
+    if (pos < M) seg[pos] = k;
+  }
+  __syncthreads();
+  // 4. rank within the segment; one atomic per wave and list (the pattern of k_topk's emit)
+  auto append = [&](bool take, unsigned long long k, int* counter, unsigned long long* dst, int limit) {
+    const unsigned long long act = __ballot(take);
+    if (!act) return;
+    int base = 0;
+    const int leader = __ffsll((long long)act) - 1;
+    if (lane == leader) base = atomicAdd(counter, __popcll(act));
+    base = __shfl(base, leader, 64);
+    const int pos = base + __popcll(act & ((1ull << lane) - 1ull));
+    if (take && pos < limit) dst[pos] = k;
+  };
+  for (int i0 = 0; i0 < M; i0 += 1024) {
+    const int i = i0 + tid;
+    const bool valid = i < M;
+    unsigned long long mine = 0;
+    int r = 0;
+    if (valid) {
+      mine = seg[i];
+      const int bk = bucket_of(mine);
+      const int s0 = bk ? tab[bk - 1] : 0, s1 = min(tab[bk], M);
+      for (int j = s0; j < s1; ++j) {
+        r += seg[j] > mine;
+        if (r > Rs) break;
+      }
+    }
+    append(valid && (r < Rs || (r == Rs && all_boundary)), mine, &sh.n_sel, out, a.max_kp);
+    if (!all_boundary) append(valid && r == Rs, mine, &sh.n_bnd, bnd, nb);
+  }
+  if (all_boundary) return;
+  __syncthreads();
+  // 5. the `need` largest of the E boundary keys (k_topk's radix select: 8 bits a pass from the top, the boundary bin taken whole when it fits)
+  auto count = [&](bool valid, int digit) {
+    const unsigned long long act = __ballot(valid);
+    if (!act) return;
+    const int d0 = __shfl(digit, __ffsll((long long)act) - 1, 64);
+    const unsigned long long same = __ballot(valid && digit == d0);
+    if (same == act) {
+      if (lane == __ffsll((long long)act) - 1) atomicAdd(&sh.hist[d0], __popcll(act));
+    } else if (valid) {
+      atomicAdd(&sh.hist[digit], 1);
+    }
+  };
+  const int En = min(min(sh.n_bnd, E), nb);
+  if (tid == 0) { sh.prefix = 0; sh.remaining = need; sh.done = 0; }
+  for (int pass = 0; pass < 8; ++pass) {
+    if (tid < 256) sh.hist[tid] = 0;
+    __syncthreads();
+    const unsigned long long prefix = sh.prefix;
+    const int shift = 56 - 8 * pass;
+    for (int i0 = 0; i0 < En; i0 += 1024) {
+      const int i = i0 + tid;
+      const unsigned long long k = i < En ? bnd[i] : 0ull;
+      count(i < En && (pass == 0 || (k >> (shift + 8)) == prefix), (int)((k >> shift) & 255));
+    }
+    __syncthreads();
+    if (tid < 64) {
+      int h[4], loc = 0;  // descending-digit scan by one wave: lane l owns digits 255-4l .. 252-4l
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { h[j] = sh.hist[255 - (4 * lane + j)]; loc += h[j]; }
+      int incl = loc;
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) {
+        const int up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+      }
+      const int rem = sh.remaining;
+      int c = incl - loc;
+      if (c < rem && rem <= incl) {
+        int d = 255 - 4 * lane;
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+          if (c + h[j] < rem && d == 255 - (4 * lane + j)) { c += h[j]; --d; }
+        sh.remaining = rem - c;
+        sh.prefix = (prefix << 8) | (unsigned)d;
+        if (rem - c == h[255 - d - 4 * lane]) sh.done = pass + 1;
+      }
+    }
+    __syncthreads();
+    if (sh.done) break;
+  }
+  const unsigned long long thresh = sh.done ? sh.prefix << (64 - 8 * sh.done) : sh.prefix;
+  for (int i0 = 0; i0 < En; i0 += 1024) {
+    const int i = i0 + tid;
+    const unsigned long long k = i < En ? bnd[i] : 0ull;
+    append(i < En && k >= thresh, k, &sh.n_sel, out, a.max_kp);
+  }
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(1024) void k_select_balanced(SelectBalancedArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char selb_smem[];
+  __shared__ SelbShared sh;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int n_cand = a.cand_count[b];
+  const int M = min(n_cand, a.cap);
+  const int K = min(M, a.max_kp);
+  if (tid == 0) {
+    a.sel_count[b] = K;
+    if (a.n_cand_out) a.n_cand_out[b] = n_cand;
+  }
+  if (K == 0) return;
+  const unsigned long long* cand = a.cand + (size_t)b * a.cap;
+  unsigned long long* out = a.sel + (size_t)b * a.max_kp;
+  if (M <= K) {  // every candidate is selected: the list is the candidate list, and the output is the default mode's
+    for (int i = tid; i < M; i += 1024) out[i] = cand[i];
+    return;
+  }
+  unsigned long long* g_seg = a.ws_seg + (size_t)b * a.cap;
+  unsigned long long* g_bnd = a.ws_bnd + (size_t)b * a.nb;
+  int* g_tab = a.ws_tab + (size_t)b * a.nb;
+  if (LDS && M <= SELB_LDS_KEYS) {
+    unsigned long long* seg = reinterpret_cast<unsigned long long*>(selb_smem);
+    unsigned long long* bnd = seg + SELB_LDS_KEYS;
+    int* tab = reinterpret_cast<int*>(bnd + SELB_LDS_BUCKETS);
+    selb_body<true>(a, cand, M, K, seg, tab, bnd, out, sh);
+  } else {
+    selb_body<false>(a, cand, M, K, g_seg, g_tab, g_bnd, out, sh);
+  }
+}
+
+hipError_t launch_select_balanced(const SelectBalancedArgs& a, int B, hipStream_t s) {
+  if (a.nb <= SELB_LDS_BUCKETS) {
+    // thread-safe one-time opt-in to > 64 KiB of dynamic LDS
+    static const hipError_t attr_rc = hipFuncSetAttribute(reinterpret_cast<const void*>(k_select_balanced<true>),
+                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)SELB_SMEM);
+    if (attr_rc != hipSuccess) return attr_rc;
+    hipLaunchKernelGGL(k_select_balanced<true>, dim3(B), dim3(1024), SELB_SMEM, s, a);
+  } else {
+    hipLaunchKernelGGL(k_select_balanced<false>, dim3(B), dim3(1024), 0, s, a);
+  }
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Sub-pixel keypoint refinement (include/sship.h: SSHIP_KP_SUBPIXEL, sship_refine_keypoints*; the reference has no counterpart).
 // Per axis, the three-point log-parabola fit on L = logit - logsumexp(the 65 logits of the pixel's cell), the log of the softmax score
 // k_nms_tile compared.  A 16-lane group owns a keypoint (four per wave): lanes 0-3 hold the centre cell, 4-7 the cell of the x neighbour

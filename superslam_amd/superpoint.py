@@ -94,12 +94,53 @@ def refine_keypoints(logits, pix, layout: str = "chw", stream=None):
     return out
 
 
+KEYPOINT_SELECTION = {"topk": 0, "balanced": 1}   # SSHIP_SELECT_TOPK / SSHIP_SELECT_BALANCED (include/sship.h)
+
+
+def _selection_mode(name, bucket_px) -> tuple:
+    if name not in KEYPOINT_SELECTION:
+        raise ValueError(f"keypoint_selection must be one of {sorted(KEYPOINT_SELECTION)}, not {name!r}")
+    if isinstance(bucket_px, bool) or not isinstance(bucket_px, (int, np.integer)):
+        raise ValueError(f"bucket_px must be an integer, not {bucket_px!r}")
+    if name == "balanced" and not 8 <= int(bucket_px) <= 65535:
+        raise ValueError(f"bucket_px must be in [8, 65535], not {bucket_px!r}")
+    return KEYPOINT_SELECTION[name], int(bucket_px)
+
+
+def select_topk_balanced(scores, input_h: int, input_w: int, thr: float, border: int, max_kp: int, bucket_px: int, desc_h: int, desc_w: int,
+                         stream=None):
+    """The selection stage with the spatially balanced rule (include/sship.h: sship_select_topk_balanced, SSHIP_SELECT_BALANCED).
+    scores: torch fp32 CUDA tensor [H,W], a score map after NMS.  Returns (kp f32 [max_kp,3], cell_h i32 [max_kp], cell_w i32 [max_kp],
+    n i32 [1], n_candidates i32 [1]) on the device; rows past n are left as allocated."""
+    import torch
+
+    if scores.dtype != torch.float32 or scores.dim() != 2 or not scores.is_contiguous():
+        raise ValueError("scores must be a contiguous fp32 tensor [H, W]")
+    if not 1 <= int(max_kp) <= 4096:
+        raise ValueError("max_kp must be in [1, 4096]")
+    _selection_mode("balanced", bucket_px)
+    dev = scores.device
+    kp = torch.empty((max_kp, 3), dtype=torch.float32, device=dev)
+    ch = torch.empty((max_kp,), dtype=torch.int32, device=dev)
+    cw = torch.empty((max_kp,), dtype=torch.int32, device=dev)
+    n = torch.zeros((1,), dtype=torch.int32, device=dev)
+    nc = torch.zeros((1,), dtype=torch.int32, device=dev)
+    s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+    _lib.check(_lib.lib().sship_select_topk_balanced(scores.data_ptr(), scores.shape[0], scores.shape[1], int(input_h), int(input_w), float(thr),
+                                                     int(border), int(max_kp), int(bucket_px), int(desc_h), int(desc_w), kp.data_ptr(),
+                                                     ch.data_ptr(), cw.data_ptr(), n.data_ptr(), nc.data_ptr(), s))
+    return kp, ch, cw, n, nc
+
+
 class SuperPoint:
     descriptor_dim = 256
 
     def __init__(self, engine_file: str, max_keypoints: int, keypoint_threshold: float, remove_borders: int,
                  nms_radius: int = 4, pool_slots: int = 8, max_batch: int = 2, descriptor_sampling: str = "nearest",
-                 keypoint_refinement: str = "integer"):
+                 keypoint_refinement: str = "integer", keypoint_selection: str = "topk", bucket_px: int = 32):
+        # "topk": the reference's highest scores of the whole image (default); "balanced": spread over buckets of bucket_px score-map pixels
+        _, bucket_px = _selection_mode(keypoint_selection, bucket_px)
+        self._keypoint_selection = (keypoint_selection, bucket_px)
         # "integer": the reference's integer score-map pixels (default); "subpixel": the log-parabola peak fit of include/sship.h
         _refinement_mode(keypoint_refinement)
         self._keypoint_refinement = keypoint_refinement
@@ -133,6 +174,12 @@ class SuperPoint:
                     return False
             if self._keypoint_refinement != "integer":
                 rc = _lib.lib().sship_sp_set_keypoint_refinement(h, _refinement_mode(self._keypoint_refinement))
+                if rc != _lib.OK:
+                    self.last_error = (_lib.lib().sship_last_error() or b"").decode()
+                    _lib.lib().sship_sp_destroy(h)
+                    return False
+            if self._keypoint_selection[0] != "topk":
+                rc = _lib.lib().sship_sp_set_keypoint_selection(h, *_selection_mode(*self._keypoint_selection))
                 if rc != _lib.OK:
                     self.last_error = (_lib.lib().sship_last_error() or b"").decode()
                     _lib.lib().sship_sp_destroy(h)
@@ -179,6 +226,20 @@ class SuperPoint:
         if self._h is not None:
             _lib.check(_lib.lib().sship_sp_set_keypoint_refinement(self._h, m))
         self._keypoint_refinement = mode
+
+    def keypoint_selection(self) -> tuple:
+        """(mode, bucket_px): ("topk" | "balanced", the bucket size the balanced mode uses or would use)."""
+        return self._keypoint_selection
+
+    def set_keypoint_selection(self, mode: str, bucket_px: int = 32) -> None:
+        """"topk" | "balanced" for the calls after this one (which candidates become keypoints: include/sship.h; the count n does not change).
+        bucket_px in [8, 65535] is the bucket size in score-map pixels; "topk" ignores it.  Before initialize() the mode is kept and applied
+        by it.  Raises ValueError for a bad name or bucket and SshipError if the library refuses (a ring submission is pending); the mode is
+        then unchanged."""
+        m, g = _selection_mode(mode, bucket_px)
+        if self._h is not None:
+            _lib.check(_lib.lib().sship_sp_set_keypoint_selection(self._h, m, g))
+        self._keypoint_selection = (mode, g if mode == "balanced" else self._keypoint_selection[1])
 
     @property
     def pool_handle(self):
