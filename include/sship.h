@@ -1407,6 +1407,88 @@ int sship_patch_track_host(const uint8_t* img0, int stride0, const uint8_t* img1
                            int32_t* matches0, uint8_t* status, int64_t* cost);
 
 /* ------------------------------------------------------------------------------------------------
+ * Image pyramid - a batch of u8 images reduced level by level on the device: the primitive under the coarse-to-fine tracker below, and a
+ * source of half-, quarter-, ... resolution images for the other image stages (sship_stereo_search_batch_device on level 1 is
+ * half-resolution depth at a quarter of the candidates).  The reduction rule is the one OpenCV documents for cv::pyrDown with its default
+ * border; equality with cv::pyrDown is the intent, not a measured fact (OpenCV is on none of this project's machines), exactly as for the
+ * rectification remap.  tests/_pyr_ref.py restates this text.  Integers only: the result does not depend on tiling, batch position or
+ * entry point.
+ *   Level l+1 of a level of h x w pixels S has h' = (h + 1) / 2 rows and w' = (w + 1) / 2 columns (integer division), and
+ *     D(y, x) = (sum over j, i in -2 .. 2 of k_j k_i S(r(2y + j, h), r(2x + i, w)) + 128) >> 8,   k = (1, 4, 6, 4, 1),
+ *   where r is reflect-101: r(i, 1) = 0; otherwise i < 0 becomes -i and i >= n becomes 2 (n - 1) - i, repeated until 0 <= i < n.
+ *   The weights sum to 256; the largest accumulator is 255 * 256 = 65 280.
+ * A handle is made for one image size, `levels` levels (1 .. 8, level 0 counted) and at most max_images (1 .. 65 535) images.  It owns the
+ * storage of levels 1 and above: level l holds max_images images of lh x lw pixels in rows of pitch_l = lw rounded up to 64 bytes, image
+ * i at i * pitch_l * lh bytes from the level's base, every level's base on 256 bytes; the bytes of a row past lw are zero.  Nothing is
+ * allocated after sship_pyr_create.  Level 0 is the caller's memory, borrowed, never copied: a byte pointer, a row stride >= w and an
+ * image stride >= 0, all in bytes, no alignment required (an image stride of 2 * h * stride picks the left images of an L0, R0, L1, R1,
+ * ... batch).  It must stay valid and unchanged until the next build or sship_pyr_destroy: sship_pyr_level(0) and the tracker read it.
+ * sship_pyr_build_batch_device reduces images [0, images) (images <= max_images; a later build may hold fewer) with one launch per level,
+ * asynchronous on `stream`, no host synchronisation.  sship_pyr_level describes a level of the last build (every output pointer is
+ * optional): with it sship_patch_track_batch_device, sship_stereo_search_batch_device (where the stride fits its int) and any other
+ * consumer of (pointer, strides) run on any level.  sship_pyr_read_level copies images [first, first + count) of a level to the host in rows
+ * of out_stride >= lw bytes, image after image (synchronous; it waits for the device).  sship_pyr_down_host is one image and one reduction
+ * from host arrays, staged through one device block - the drop-in for one cv::pyrDown; dst is ((h + 1) / 2) x ((w + 1) / 2) in rows of
+ * dst_stride bytes.  sship_pyr_bench re-runs the last build's launches `iters` times on the handle's stream (*avg_ms per build).
+ * A NULL required pointer, h or w outside [1, 16384], levels outside [1, 8], max_images outside [1, 65535], images outside
+ * [1, max_images], stride < w, a negative image stride, a level outside [0, levels), images outside the last build, or a level asked for
+ * before the first build is SSHIP_ERR_INVALID before any device is touched.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sship_pyr sship_pyr;
+int sship_pyr_create(int h, int w, int levels, int max_images, sship_pyr** out);
+void sship_pyr_destroy(sship_pyr* pyr);
+int sship_pyr_build_batch_device(sship_pyr* pyr, const uint8_t* imgs_dev, long long image_stride, int stride, int images, void* stream);
+int sship_pyr_level(const sship_pyr* pyr, int level, const uint8_t** ptr, int* h, int* w, int* stride, long long* image_stride, int* images);
+int sship_pyr_read_level(const sship_pyr* pyr, int level, int first, int count, uint8_t* out_host, int out_stride);
+int sship_pyr_down_host(const uint8_t* src, int src_stride, int h, int w, uint8_t* dst, int dst_stride);
+int sship_pyr_bench(sship_pyr* pyr, int iters, float* avg_ms);
+
+/* ------------------------------------------------------------------------------------------------
+ * Coarse-to-fine patch tracking - the patch-tracking rule above run on the levels of two image pyramids from the top down, each level's
+ * result centring the search of the next: the reach grows to roughly (coarse_radius - 1) * 2^(L-1) pixels per axis around the prediction
+ * (plus the fine radius) while every level searches a small box.  tests/_pyr_track_ref.py restates this text on top of
+ * tests/_patch_track_ref.py.
+ * Pair p reads image first0 + p * step0 of pyr0 as I0 and image first1 + p * step1 of pyr1 as I1 (a step of 0: one keyframe for every
+ * pair; pyr0 == pyr1 is allowed, e.g. P + 1 consecutive frames built once and first1 = first0 + 1).  The indices must lie inside the last
+ * build of each pyramid; both pyramids must have the same h and w and at least params.levels levels.  kp_dev, n_dev, unit_stride,
+ * pred_dev, max_keypoints and the outputs are those of sship_patch_track_batch_device; pred_dev may be kp_out_dev.
+ * L = levels, I0_l / I1_l = level l of the two images.  Keypoint i of pair p with (x, y) and the prediction (px, py) (= (x, y) without
+ * pred_dev):
+ *   1. i >= n0: the outputs of step 1 of the patch-tracking rule, levels_tracked 0.
+ *   2. The top level t = L - 1 starts from p_t = ((float)((double)px 2^-t), (float)((double)py 2^-t)).
+ *   3. Each level l = t, t - 1, ..., 1 applies steps 2 to 10 of the patch-tracking rule to I0_l and I1_l, the keypoint
+ *      ((float)((double)x 2^-l), (float)((double)y 2^-l)) - the product formed in fp64, rounded once - and the prediction p_l, with
+ *      half_window and uniqueness of `fine`, search_radius = coarse_radius, and the texture gate, the cost gate and the forward-backward
+ *      check off.
+ *   4. Status TRACKED with the fp32 output (x', y'): p_(l-1) = (2 x', 2 y').  Any other status: p_(l-1) = 2 p_l.  Both doublings are exact.
+ *      A coarse failure (a template that does not fit the small level, a minimiser on the box's edge, a periodic texture, a box that
+ *      leaves the image) is therefore not fatal: the prediction is carried down unchanged and the finer levels search around it.
+ *   5. Level 0 is the patch-tracking rule with the original (x, y), the prediction p_0 and all of `fine`; its outputs are the call's
+ *      kp_out, matches0, status and cost.
+ *   6. levels_tracked_dev [pairs, max_keypoints] u8 (optional): bit l is set when level l ended TRACKED.
+ *   7. levels == 1 gives exactly the bits of sship_patch_track_batch_device.
+ * One launch, asynchronous on `stream`, no host synchronisation.  levels in [1, 8], coarse_radius in [1, 16], `fine` as
+ * sship_patch_track_params, first and step >= 0, pairs >= 1, max_keypoints in [1, 4096], unit_stride 1 or 2; anything else, a NULL
+ * required pointer, unequal pyramids, too few levels, a pyramid that was never built or an image index outside the last build is
+ * SSHIP_ERR_INVALID before any device is touched.  sship_patch_track_pyramid_host is one pair from host arrays (arguments as
+ * sship_patch_track_host, levels_tracked [n] optional): both images are staged in one device block, a two-image pyramid is built for the
+ * call, and the same launch runs with pairs = 1 - the same bits.  Synchronous.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sship_pyr_track_params {
+  sship_patch_track_params fine;  /* level 0: every field as in sship_patch_track_batch_device */
+  int levels;                     /* L: levels walked, level 0 counted; 1 .. 8, default 3 */
+  int coarse_radius;              /* search radius of the levels above 0; 1 .. 16, default 8 */
+} sship_pyr_track_params;
+int sship_patch_track_pyramid_batch_device(const sship_pyr* pyr0, int first0, int step0, const sship_pyr* pyr1, int first1, int step1,
+                                           int pairs, const float* kp_dev, const int* n_dev, int unit_stride, const float* pred_dev,
+                                           int max_keypoints, const sship_pyr_track_params* params, float* kp_out_dev, int* n_out_dev,
+                                           int32_t* matches0_dev, uint8_t* status_dev, int64_t* cost_dev, uint8_t* levels_tracked_dev,
+                                           void* stream);
+int sship_patch_track_pyramid_host(const uint8_t* img0, int stride0, const uint8_t* img1, int stride1, int h, int w, const float* keypoints,
+                                   int kp_stride, const float* pred, int pred_stride, int n, const sship_pyr_track_params* params,
+                                   float* kp_out, int32_t* matches0, uint8_t* status, int64_t* cost, uint8_t* levels_tracked);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused front-end step: what StereoFrontEnd::process asks of the two interfaces per frame
  * (src/StereoFrontEnd.cc:14,33): SuperPoint on L and R (one batch) + gather x2 + one LightGlue match,
  * for `pairs` stereo pairs at once, device-resident, no host synchronisation.  imgs_dev is

@@ -10,6 +10,7 @@ from .frontend import (FrontEndBatch, patch_track, patch_track_batch, patch_trac
 from .lightglue import LightGlue, LightGlueEngine, MatchResult  # noqa: F401
 from .nn_matcher import NNMatcher  # noqa: F401
 from .place_index import PlaceIndex  # noqa: F401
+from .pyramid import ImagePyramid, patch_track_pyramid, patch_track_pyramid_batch, pyr_down, pyr_track_params  # noqa: F401
 from .pose_graph import PoseGraph, close_loops_batch  # noqa: F401
 from .rectifier import Rectifier, build_maps  # noqa: F401
 from .pose_solver import PoseSolver, track_batch  # noqa: F401
@@ -22,4 +23,5 @@ __all__ = ["SuperPoint", "LightGlue", "LightGlueEngine", "MatchResult", "Feature
            "DeviceDescriptors", "FrontEndBatch", "process_stereo", "stereo_associate_batch", "EigenPlaces", "NNMatcher", "PlaceIndex", "PoseSolver",
            "track_batch", "RansacVerifier", "verify_batch", "WindowSmoother", "smooth_batch", "PoseGraph", "close_loops_batch", "Rectifier", "build_maps",
            "rgbd_associate_batch", "stereo_refine_batch", "stereo_refine", "stereo_search_batch", "stereo_search",
-           "patch_track_batch", "patch_track", "patch_track_stereo_batch"]
+           "patch_track_batch", "patch_track", "patch_track_stereo_batch", "ImagePyramid", "pyr_down", "patch_track_pyramid_batch",
+           "patch_track_pyramid", "pyr_track_params"]

@@ -87,6 +87,10 @@ class PatchTrackParams(C.Structure):
                 ("max_rms", C.c_float), ("fb_check", C.c_int)]
 
 
+class PyrTrackParams(C.Structure):
+    _fields_ = [("fine", PatchTrackParams), ("levels", C.c_int), ("coarse_radius", C.c_int)]
+
+
 _lib = None
 vp, ip, fp, dp = C.c_void_p, C.c_int, C.c_float, C.c_double
 _SIGS = {
@@ -254,6 +258,16 @@ _SIGS = {
     "sship_patch_track_batch_device": (ip, [vp, C.c_longlong, ip, vp, C.c_longlong, ip, ip, ip, ip, vp, vp, ip, vp, ip,
                                             C.POINTER(PatchTrackParams), vp, vp, vp, vp, vp, vp]),
     "sship_patch_track_host": (ip, [vp, ip, vp, ip, ip, ip, vp, ip, vp, ip, ip, C.POINTER(PatchTrackParams), vp, vp, vp, vp]),
+    "sship_pyr_create": (ip, [ip, ip, ip, ip, C.POINTER(vp)]),
+    "sship_pyr_destroy": (None, [vp]),
+    "sship_pyr_build_batch_device": (ip, [vp, vp, C.c_longlong, ip, ip, vp]),
+    "sship_pyr_level": (ip, [vp, ip, C.POINTER(vp), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(C.c_longlong), C.POINTER(ip)]),
+    "sship_pyr_read_level": (ip, [vp, ip, ip, ip, vp, ip]),
+    "sship_pyr_down_host": (ip, [vp, ip, ip, ip, vp, ip]),
+    "sship_pyr_bench": (ip, [vp, ip, C.POINTER(fp)]),
+    "sship_patch_track_pyramid_batch_device": (ip, [vp, ip, ip, vp, ip, ip, ip, vp, vp, ip, vp, ip, C.POINTER(PyrTrackParams), vp, vp, vp, vp,
+                                                    vp, vp, vp]),
+    "sship_patch_track_pyramid_host": (ip, [vp, ip, vp, ip, ip, ip, vp, ip, vp, ip, ip, C.POINTER(PyrTrackParams), vp, vp, vp, vp, vp]),
     "sship_desc_to_host": (ip, [vp, ip, ip, vp]),
     "sship_frontend_batch_device": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_bench_layer": (ip, [vp, ip, ip, ip, ip, ip, C.POINTER(fp), C.POINTER(C.c_double)]),

@@ -4487,6 +4487,221 @@ extern "C" int sship_patch_track_host(const uint8_t* img0, int stride0, const ui
 }
 
 // ====================================================================================================
+// image pyramid (sship_pyr_*) and coarse-to-fine patch tracking (the rules are in include/sship.h)
+// ====================================================================================================
+struct sship_pyr {
+  int h = 0, w = 0, levels = 0, max_images = 0;
+  int lh[kPyrMaxLevels] = {}, lw[kPyrMaxLevels] = {}, pitch[kPyrMaxLevels] = {};
+  size_t off[kPyrMaxLevels] = {};   // of level l >= 1 in `store`: max_images images of pitch[l] * lh[l] bytes each
+  hipStream_t stream = nullptr;
+  DevBuf store;
+  // the last build; level 0 is the caller's memory
+  const uint8_t* l0 = nullptr;
+  long long l0_image_stride = 0;
+  int l0_stride = 0, images = 0;
+  size_t image_bytes(int l) const { return (size_t)pitch[l] * lh[l]; }
+  uint8_t* level_ptr(int l) const { return store.as<uint8_t>() + off[l]; }
+};
+static int pyr_pitch(int w) { return (w + kPyrRowAlign - 1) / kPyrRowAlign * kPyrRowAlign; }
+extern "C" int sship_pyr_create(int h, int w, int levels, int max_images, sship_pyr** out) {
+  if (!out) return fail(SSHIP_ERR_INVALID, "pyr_create: null argument");
+  *out = nullptr;
+  if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, "pyr_create: h and w must be in [1, 16384]");
+  if (levels < 1 || levels > kPyrMaxLevels) return fail(SSHIP_ERR_INVALID, "pyr_create: levels must be in [1, 8]");
+  if (max_images < 1 || max_images > 65535) return fail(SSHIP_ERR_INVALID, "pyr_create: max_images must be in [1, 65535]");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  std::unique_ptr<sship_pyr, void (*)(sship_pyr*)> p(new sship_pyr(), sship_pyr_destroy);
+  p->h = h; p->w = w; p->levels = levels; p->max_images = max_images;
+  p->lh[0] = h; p->lw[0] = w;
+  StageLayout lay;
+  for (int l = 1; l < levels; ++l) {
+    p->lh[l] = (p->lh[l - 1] + 1) / 2; p->lw[l] = (p->lw[l - 1] + 1) / 2; p->pitch[l] = pyr_pitch(p->lw[l]);
+    p->off[l] = lay.add(p->image_bytes(l) * max_images);
+  }
+  SSHIP_HIP_CHECK(p->store.ensure(lay.end));
+  if (lay.end) { SSHIP_HIP_CHECK(hipMemset(p->store.p, 0, lay.end)); }
+  SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&p->stream, hipStreamDefault));
+  *out = p.release();
+  return SSHIP_OK;
+}
+extern "C" void sship_pyr_destroy(sship_pyr* pyr) { destroy_handle(pyr); }
+// dword loads need every row of every image on a multiple of 4 bytes: always so in the handle's own levels, in the caller's level 0 where
+// its pointer and strides happen to be
+static bool pyr_dword_rows(const uint8_t* p, long long image_stride, long long stride) {
+  return (reinterpret_cast<uintptr_t>(p) | (uintptr_t)image_stride | (uintptr_t)stride) % 4 == 0;
+}
+static void pyr_launch_levels(const sship_pyr* pyr, hipStream_t s) {
+  for (int l = 1; l < pyr->levels; ++l) {
+    const bool own = l > 1;
+    const uint8_t* src = own ? pyr->level_ptr(l - 1) : pyr->l0;
+    const long long is = own ? (long long)pyr->image_bytes(l - 1) : pyr->l0_image_stride, st = own ? pyr->pitch[l - 1] : pyr->l0_stride;
+    launch_pyr_down(src, is, st, pyr->lh[l - 1], pyr->lw[l - 1], pyr_dword_rows(src, is, st) ? 1 : 0, pyr->level_ptr(l), (long long)pyr->image_bytes(l),
+                    pyr->pitch[l], pyr->images, s);
+  }
+}
+extern "C" int sship_pyr_build_batch_device(sship_pyr* pyr, const uint8_t* imgs, long long image_stride, int stride, int images, void* stream) {
+  if (!pyr || !imgs) return fail(SSHIP_ERR_INVALID, "pyr_build_batch_device: null argument");
+  if (images < 1 || images > pyr->max_images) return fail(SSHIP_ERR_INVALID, "pyr_build_batch_device: images must be in [1, max_images]");
+  if (stride < pyr->w) return fail(SSHIP_ERR_INVALID, "pyr_build_batch_device: stride (bytes) must be >= w");
+  if (image_stride < 0) return fail(SSHIP_ERR_INVALID, "pyr_build_batch_device: image_stride (bytes) must be >= 0");
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  pyr->l0 = imgs; pyr->l0_image_stride = image_stride; pyr->l0_stride = stride; pyr->images = images;
+  pyr_launch_levels(pyr, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("pyr_build", s);
+  return SSHIP_OK;
+}
+static int pyr_check_level(const sship_pyr* pyr, int level, const char* who) {
+  if (!pyr) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  if (level < 0 || level >= pyr->levels) return fail(SSHIP_ERR_INVALID, std::string(who) + ": level must be in [0, levels)");
+  if (pyr->images <= 0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": build the pyramid first");
+  return SSHIP_OK;
+}
+extern "C" int sship_pyr_level(const sship_pyr* pyr, int level, const uint8_t** ptr, int* h, int* w, int* stride, long long* image_stride, int* images) {
+  if (int rc = pyr_check_level(pyr, level, "pyr_level")) return rc;
+  if (ptr) *ptr = level ? pyr->level_ptr(level) : pyr->l0;
+  if (h) *h = pyr->lh[level];
+  if (w) *w = pyr->lw[level];
+  if (stride) *stride = level ? pyr->pitch[level] : pyr->l0_stride;
+  if (image_stride) *image_stride = level ? (long long)pyr->image_bytes(level) : pyr->l0_image_stride;
+  if (images) *images = pyr->images;
+  return SSHIP_OK;
+}
+extern "C" int sship_pyr_read_level(const sship_pyr* pyr, int level, int first, int count, uint8_t* out, int out_stride) {
+  if (int rc = pyr_check_level(pyr, level, "pyr_read_level")) return rc;
+  if (!out) return fail(SSHIP_ERR_INVALID, "pyr_read_level: null argument");
+  if (first < 0 || count < 1 || (long long)first + count > pyr->images)
+    return fail(SSHIP_ERR_INVALID, "pyr_read_level: first and count must name images of the last build");
+  if (out_stride < pyr->lw[level]) return fail(SSHIP_ERR_INVALID, "pyr_read_level: out_stride (bytes) must be >= the level's width");
+  bind_thread();
+  const uint8_t* ptr; int h, w, stride; long long is;
+  (void)sship_pyr_level(pyr, level, &ptr, &h, &w, &stride, &is, nullptr);
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());   // the build may have run on the caller's stream
+  for (int i = 0; i < count; ++i)
+    SSHIP_HIP_CHECK(hipMemcpy2D(out + (size_t)i * h * out_stride, (size_t)out_stride, ptr + (size_t)(first + i) * is, (size_t)stride, (size_t)w, (size_t)h,
+                                hipMemcpyDeviceToHost));
+  return SSHIP_OK;
+}
+extern "C" int sship_pyr_down_host(const uint8_t* src, int src_stride, int h, int w, uint8_t* dst, int dst_stride) {
+  if (!src || !dst) return fail(SSHIP_ERR_INVALID, "pyr_down_host: null argument");
+  if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, "pyr_down_host: h and w must be in [1, 16384]");
+  const int h2 = (h + 1) / 2, w2 = (w + 1) / 2, pitch = pyr_pitch(w2);
+  if (src_stride < w || dst_stride < w2) return fail(SSHIP_ERR_INVALID, "pyr_down_host: src_stride must be >= w and dst_stride >= (w + 1) / 2");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  StageLayout lay;   // one device block for the call: the image packed to stride w, then the reduced image in padded rows
+  const size_t o_src = lay.add((size_t)h * w), o_dst = lay.add((size_t)h2 * pitch);
+  StageArena a;
+  SSHIP_HIP_CHECK(a.create(lay.end, 0, false));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_src), (size_t)w, src, (size_t)src_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  launch_pyr_down(a.dev<uint8_t>(o_src), 0, w, h, w, pyr_dword_rows(a.dev<uint8_t>(o_src), 0, w) ? 1 : 0, a.dev<uint8_t>(o_dst), 0, pitch, 1, nullptr);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  SSHIP_HIP_CHECK(hipMemcpy2D(dst, (size_t)dst_stride, a.dev<uint8_t>(o_dst), (size_t)pitch, (size_t)w2, (size_t)h2, hipMemcpyDeviceToHost));   // blocking, on the NULL stream: after the launch
+  return SSHIP_OK;
+}
+// Measurement hook (include/sship.h): the last build's launches re-run `iters` times on the handle's stream.
+extern "C" int sship_pyr_bench(sship_pyr* pyr, int iters, float* avg_ms) {
+  if (!pyr || !avg_ms || iters <= 0) return fail(SSHIP_ERR_INVALID, "pyr_bench: bad arguments");
+  if (pyr->images <= 0) return fail(SSHIP_ERR_INVALID, "pyr_bench: build the pyramid first");
+  bind_thread();
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());   // the last build may have run on the caller's stream
+  return bench_loop(pyr->stream, iters, [&]() { pyr_launch_levels(pyr, pyr->stream); return hipGetLastError(); }, avg_ms);
+}
+
+// the checks both pyramid-tracker entries share; fills the kernel's constants
+static int pyr_track_check(int h, int w, const sship_pyr_track_params* p, PyrTrackK* c, const char* who) {
+  if (p->levels < 1 || p->levels > kPyrMaxLevels) return fail(SSHIP_ERR_INVALID, std::string(who) + ": levels must be in [1, 8]");
+  if (p->coarse_radius < 1 || p->coarse_radius > 16) return fail(SSHIP_ERR_INVALID, std::string(who) + ": coarse_radius must be in [1, 16]");
+  if (int rc = track_check(h, w, w, w, &p->fine, &c->fine, who)) return rc;
+  c->levels = p->levels; c->coarse_radius = p->coarse_radius;
+  c->slot_bytes = (int)pyr_track_slot_bytes(p->fine.half_window, p->levels > 1 ? std::max(p->fine.search_radius, p->coarse_radius) : p->fine.search_radius);
+  return SSHIP_OK;
+}
+extern "C" int sship_patch_track_pyramid_batch_device(const sship_pyr* pyr0, int first0, int step0, const sship_pyr* pyr1, int first1, int step1,
+                                                      int pairs, const float* kp, const int* n, int unit_stride, const float* pred,
+                                                      int max_keypoints, const sship_pyr_track_params* p, float* kp_out, int* n_out,
+                                                      int32_t* matches0, uint8_t* status, int64_t* cost, uint8_t* levels_tracked, void* stream) {
+  const char* who = "patch_track_pyramid_batch_device";
+  if (!pyr0 || !pyr1 || !kp || !n || !p || !kp_out || !matches0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  if (pairs <= 0 || max_keypoints <= 0 || max_keypoints > kMaxKp)
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": pairs must be positive and max_keypoints in [1, 4096]");
+  if (unit_stride != 1 && unit_stride != 2) return fail(SSHIP_ERR_INVALID, std::string(who) + ": unit_stride must be 1 or 2");
+  if (pyr0->h != pyr1->h || pyr0->w != pyr1->w) return fail(SSHIP_ERR_INVALID, std::string(who) + ": the pyramids must have the same h and w");
+  PyrTrackK c;
+  if (int rc = pyr_track_check(pyr0->h, pyr0->w, p, &c, who)) return rc;
+  if (pyr0->levels < p->levels || pyr1->levels < p->levels) return fail(SSHIP_ERR_INVALID, std::string(who) + ": a pyramid has fewer levels than params.levels");
+  if (pyr0->images <= 0 || pyr1->images <= 0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": build the pyramids first");
+  if (first0 < 0 || step0 < 0 || first1 < 0 || step1 < 0 || (long long)first0 + (long long)(pairs - 1) * step0 >= pyr0->images ||
+      (long long)first1 + (long long)(pairs - 1) * step1 >= pyr1->images)
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": first + pair * step must name images of the last build, with first and step >= 0");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  PyrTrackLevels tab = {};
+  for (int l = 0; l < p->levels; ++l) {
+    PyrTrackLevel& L = tab.l[l];
+    const uint8_t *b0, *b1; int s0, s1; long long is0, is1;
+    (void)sship_pyr_level(pyr0, l, &b0, &L.h, &L.w, &s0, &is0, nullptr);
+    (void)sship_pyr_level(pyr1, l, &b1, nullptr, nullptr, &s1, &is1, nullptr);
+    L.img0 = b0 + (size_t)first0 * is0; L.img1 = b1 + (size_t)first1 * is1;
+    L.pair_stride0 = step0 * is0; L.pair_stride1 = step1 * is1; L.stride0 = s0; L.stride1 = s1;
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  launch_pyr_track(tab, pairs, kp, n, unit_stride, pred, max_keypoints, c, kp_out, n_out, matches0, status, reinterpret_cast<long long*>(cost),
+                   levels_tracked, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("patch_track_pyramid", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_patch_track_pyramid_host(const uint8_t* img0, int stride0, const uint8_t* img1, int stride1, int h, int w, const float* keypoints,
+                                              int kp_stride, const float* pred, int pred_stride, int n, const sship_pyr_track_params* p, float* kp_out,
+                                              int32_t* matches0, uint8_t* status, int64_t* cost, uint8_t* levels_tracked) {
+  const char* who = "patch_track_pyramid_host";
+  if (!img0 || !img1 || !p) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  if (n < 0 || n > kMaxKp || kp_stride < 2 || (pred && pred_stride < 2))
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": n must be in [0, 4096], kp_stride >= 2 and, with pred, pred_stride >= 2");
+  if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, std::string(who) + ": h and w must be in [1, 16384]");
+  if (stride0 < w || stride1 < w) return fail(SSHIP_ERR_INVALID, std::string(who) + ": stride (bytes) must be >= w");
+  PyrTrackK c;
+  if (int rc = pyr_track_check(h, w, p, &c, who)) return rc;
+  if (n == 0) return SSHIP_OK;
+  if (!keypoints || !kp_out || !matches0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  std::vector<float> kp((size_t)n * 3, 0.f), pr(pred ? (size_t)n * 3 : 0, 0.f);
+  for (int i = 0; i < n; ++i) memcpy(&kp[3 * (size_t)i], keypoints + (size_t)i * kp_stride, (kp_stride >= 3 ? 3 : 2) * sizeof(float));
+  for (int i = 0; pred && i < n; ++i) memcpy(&pr[3 * (size_t)i], pred + (size_t)i * pred_stride, 2 * sizeof(float));
+  const size_t img = (size_t)h * w, kb = (size_t)n * 3 * sizeof(float);
+  StageLayout lay;   // one device block for the call: the two images packed to stride w (a two-image pyramid reads them), then the per-keypoint arrays
+  const size_t o_i0 = lay.add(2 * img), o_n = lay.add(sizeof(int)), o_kp = lay.add(kb), o_pr = lay.add(kb), o_out = lay.add(kb),
+               o_m = lay.add((size_t)n * sizeof(int32_t)), o_status = lay.add((size_t)n), o_cost = lay.add((size_t)n * sizeof(int64_t)),
+               o_lv = lay.add((size_t)n);
+  StageArena a;
+  SSHIP_HIP_CHECK(a.create(lay.end, 0, false));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_i0), (size_t)w, img0, (size_t)stride0, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_i0) + img, (size_t)w, img1, (size_t)stride1, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<int>(o_n), &n, sizeof(int), hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<float>(o_kp), kp.data(), kb, hipMemcpyHostToDevice));
+  if (pred) { SSHIP_HIP_CHECK(hipMemcpy(a.dev<float>(o_pr), pr.data(), kb, hipMemcpyHostToDevice)); }
+  sship_pyr* raw = nullptr;
+  if (int rc = sship_pyr_create(h, w, p->levels, 2, &raw)) return rc;
+  std::unique_ptr<sship_pyr, void (*)(sship_pyr*)> pyr(raw, sship_pyr_destroy);
+  if (int rc = sship_pyr_build_batch_device(raw, a.dev<uint8_t>(o_i0), (long long)img, w, 2, nullptr)) return rc;
+  if (int rc = sship_patch_track_pyramid_batch_device(raw, 0, 1, raw, 1, 1, 1, a.dev<float>(o_kp), a.dev<int>(o_n), 1, pred ? a.dev<float>(o_pr) : nullptr, n,
+                                                      p, a.dev<float>(o_out), nullptr, a.dev<int32_t>(o_m), a.dev<uint8_t>(o_status),
+                                                      a.dev<int64_t>(o_cost), a.dev<uint8_t>(o_lv), nullptr)) return rc;
+  SSHIP_HIP_CHECK(hipMemcpy(kp_out, a.dev<float>(o_out), kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launches
+  SSHIP_HIP_CHECK(hipMemcpy(matches0, a.dev<int32_t>(o_m), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+  if (status) { SSHIP_HIP_CHECK(hipMemcpy(status, a.dev<uint8_t>(o_status), (size_t)n, hipMemcpyDeviceToHost)); }
+  if (cost) { SSHIP_HIP_CHECK(hipMemcpy(cost, a.dev<int64_t>(o_cost), (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost)); }
+  if (levels_tracked) { SSHIP_HIP_CHECK(hipMemcpy(levels_tracked, a.dev<uint8_t>(o_lv), (size_t)n, hipMemcpyDeviceToHost)); }
+  return SSHIP_OK;
+}
+
+// ====================================================================================================
 // fused front-end step: SuperPoint(batch 2P) + select + gather + LightGlue(P)
 // ====================================================================================================
 extern "C" int sship_frontend_batch_device(sship_sp* sp, sship_lg* lg, const uint8_t* imgs, int pairs, int h, int w,

@@ -372,4 +372,21 @@ void launch_patch_track(const uint8_t* imgs0, long long image_stride0, int strid
                         int pairs, int h, int w, const float* kp, const int* lens, int unit_stride, const float* pred, int max_kp,
                         const PatchTrackK& c, float* kp_out, int* n_out, int* matches0, uint8_t* status, long long* cost, hipStream_t s);
 
+// image pyramid and coarse-to-fine patch tracking (pyr_kernels.hip)
+constexpr int kPyrMaxLevels = 8, kPyrTileW = 64, kPyrTileH = 16, kPyrRowAlign = 64;
+// one reduction of `images` images: src image i at src + i * src_image_stride, rows of src_stride bytes, h x w; dst rows of dst_pitch bytes
+// (a multiple of 4, >= (w + 1) / 2 rounded up to 4; dst and every dst row dword aligned).  aligned: src, src_image_stride and src_stride are multiples of 4 (rows are then read by dwords, else by bytes).
+void launch_pyr_down(const uint8_t* src, long long src_image_stride, long long src_stride, int h, int w, int aligned, uint8_t* dst,
+                     long long dst_image_stride, int dst_pitch, int images, hipStream_t s);
+// one level of both pyramids as the tracker reads it: pair p reads the images at img + p * pair_stride (bytes)
+struct PyrTrackLevel { const uint8_t* img0; const uint8_t* img1; long long pair_stride0, pair_stride1, stride0, stride1; int h, w; };
+struct PyrTrackLevels { PyrTrackLevel l[kPyrMaxLevels]; };
+// fine: level 0's constants; the levels above use its half_window and uniqueness with coarse_radius and no gate.  slot_bytes =
+// pyr_track_slot_bytes(half_window, max(fine.radius, coarse_radius)): the LDS of one keypoint.
+struct PyrTrackK { PatchTrackK fine; int levels, coarse_radius, slot_bytes; };
+size_t pyr_track_slot_bytes(int half_window, int radius);
+void launch_pyr_track(const PyrTrackLevels& tab, int pairs, const float* kp, const int* lens, int unit_stride, const float* pred, int max_kp,
+                      const PyrTrackK& c, float* kp_out, int* n_out, int* matches0, uint8_t* status, long long* cost, uint8_t* levels_tracked,
+                      hipStream_t s);
+
 }  // namespace sship
