@@ -231,12 +231,23 @@ class Rule:
         return None
 
 
-def _lin(x, w, b):
-    """fp64 ref, S on absolute values, rel32 of a plain fp32 CPU evaluation.  x [T,K], w [O,K], b [O], all fp64 holding fp16 / fp32 values."""
+def _lin(x, w, b, x_is_fp64=False):
+    """fp64 ref, S on absolute values, rel32 of a plain fp32 CPU evaluation.  x [T,K], w [O,K], b [O], all fp64 holding fp16 / fp32 values.
+    x_is_fp64: x holds genuine fp64 values (the softmax weights of attn_rule, down to 2^-1000).  rel32 is the error of an fp32 SUMMATION, so it
+    is then measured against the fp64 sum of the operands the fp32 evaluation actually summed, x rounded to fp32: with a one-hot row whose
+    winning key has v = 0 in some channel, the exact sum is the runner-up's 1e-65 v, fp32 holds that weight as 0, and measured against the
+    exact sum the "summation error" would be 1.0 (found by the softmax_onehot family, test_gpu_weight_families.py).  Outputs whose S is
+    below 2^-100 are left out of the MEASUREMENT for the same reason - their products are fp32 subnormals or zero, which says nothing about
+    summation - and are judged like every other element.  ref and S stay exact."""
     ref = x @ w.T + b
     S = np.abs(x) @ np.abs(w).T + np.abs(b)
     y32 = (x.astype(f32) @ np.ascontiguousarray(w.T.astype(f32)) + b.astype(f32)).astype(f64)
-    rel32 = float((np.abs(y32 - ref) / np.maximum(S, 1e-300)).max()) if ref.size else 1e-7
+    if x_is_fp64:
+        xm = x.astype(f32).astype(f64)
+        Sm = np.abs(xm) @ np.abs(w).T + np.abs(b)
+        rel32 = float(np.where(Sm >= 2.0 ** -100, np.abs(y32 - (xm @ w.T + b)) / np.maximum(Sm, 1e-300), 0.0).max()) if ref.size else 1e-7
+    else:
+        rel32 = float((np.abs(y32 - ref) / np.maximum(S, 1e-300)).max()) if ref.size else 1e-7
     assert rel32 < REL32_SANE, rel32
     return ref, S, max(rel32, 2.0 ** -26)
 
@@ -288,7 +299,7 @@ def attn_rule(q, k, v, nk: int) -> Rule:
         mx = s.max(1, keepdims=True)
         p = np.exp2(s - mx)
         w = p / p.sum(1, keepdims=True)
-        o, Sv, r2 = _lin(w, v[:, sl].T, np.zeros(64))
+        o, Sv, r2 = _lin(w, v[:, sl].T, np.zeros(64), x_is_fp64=True)
         rel_s, rel_pv = max(rel_s, r1), max(rel_pv, r2)
         ref[:, sl], A[:, sl] = o, Sv
         dsmax[:, sl] = (Ss + np.abs(mx) + 8.5).max(1, keepdims=True)

@@ -53,11 +53,22 @@ def sp(hip, weights_dir):
 _REFS = {}   # (layer, digest of one image's input) -> reference object: computed once, shared by every batch that reads the same bits
 
 
-def _ref_of(key, x, make):
+def _ref_of_input(key, x, make):
     k = (key, x.shape, hashlib.blake2b(np.ascontiguousarray(x).tobytes(), digest_size=16).digest())
     if k not in _REFS:
         _REFS[k] = make(x)
     return _REFS[k]
+
+
+_WEIGHT_KEYS = {}   # id(state dict) -> (the dict, kept alive so that the id stays its own; its sha-256)
+
+
+def _weights_key(sd):
+    from superslam_amd.weights import state_dict_sha256
+
+    if id(sd) not in _WEIGHT_KEYS:
+        _WEIGHT_KEYS[id(sd)] = (sd, state_dict_sha256(sd))
+    return _WEIGHT_KEYS[id(sd)][1]
 
 
 def _read(hip, sp, layer, shape, dtype):
@@ -88,57 +99,16 @@ def _judge(tag, got, lo, hi, failures):
     return n
 
 
-@pytest.mark.parametrize("h,w,batch", CASES, ids=[f"{h}x{w}-B{b}" for h, w, b in CASES])
-def test_shipped_layers_against_fp64(hip, sp, weights_dir, parity_report, h, w, batch):
-    sd = weights_dir["sp"]
-    cus = torch.cuda.get_device_properties(0).multi_processor_count
-    bstar = _b_star(h, w, cus)
-    b = {"B*": bstar, "B*+1": bstar + 1}.get(batch, batch)
-    (h2, w2), (h4, w4), (hc, wc) = _shapes(h, w)
-    # ---- which kernels this case reaches: a change of the library's rule must fail here, not silently lose the coverage ----
-    if (h, w) in ((136, 264), (200, 376)):
-        on8 = {name: _few_tiles(b, lh, lw, cout, cus) for name, lh, lw, cout, _ in _layers16(h, w)}
-        pairs = {name: _pairs_shape(pool, b, lw) for name, lh, lw, cout, pool in _layers16(h, w)}
-        print(f"{h}x{w} B={b} (B* = {bstar}, {cus} CUs): 8-row kernel {on8}, shared edge tiles {pairs}")
-        if batch == 2:
-            assert all(on8.values()), on8
-        elif batch == "B*":
-            assert b % 2 == 0 and not any(on8.values()), on8
-            assert pairs == {"conv3b": False, "conv4a": True, "conv4b": True, "convPa": True}, pairs   # Wc = 33 / 47: edge strips of 1 / 15
-        else:
-            assert b % 2 == 1 and not any(on8.values()) and not any(pairs.values()), (on8, pairs)
-    assert _conv2_fused(h, w) == ((h, w) != (8, 8))
-
-    uniq = [make_frame(h, w, s) for s in R.IMAGE_SEEDS]
-    imgs = np.stack([uniq[i % 3] for i in range(b)])
-    nref = min(b, 3)
-    dimg = torch.from_numpy(imgs).cuda()
-    scores, grid, logits = sp.dense(dimg, want_logits=True)
-    torch.cuda.synchronize()
-    acts = _read_all(hip, sp, b, h, w, heads=True)
-    acts["grid"] = grid.cpu().numpy()
-    logits = logits.cpu().numpy()
-    assert all(np.isfinite(a.astype(np.float32)).all() for a in acts.values())
-    # the [B,65,Hc,Wc] export is the layer-11 buffer, transposed
-    np.testing.assert_array_equal(logits, acts[11].transpose(0, 3, 1, 2))
-
-    # ---- every copy of an image equals its first copy bit for bit, at every layer ----
-    for l, a in acts.items():
-        v = a.view(np.uint16) if a.dtype == np.float16 else a.view(np.uint32)
-        for i in range(3, b):
-            assert np.array_equal(v[i], v[i % 3]), f"layer {l}: image {i} differs from its first copy {i % 3} (batch {b}, {h}x{w})"
-
-    # ---- extraction at the same shape and batch runs the same network: layers 1, 3 .. 8 and the logits bit-identical ----
-    sp.extract_batch_device(dimg)
-    torch.cuda.synchronize()
-    ext = _read_all(hip, sp, b, h, w, heads=False)
-    for l, a in ext.items():
-        assert np.array_equal(a.view(np.uint16 if a.dtype == np.float16 else np.uint32),
-                              acts[l].view(np.uint16 if a.dtype == np.float16 else np.uint32)), f"layer {l}: extraction and dense differ"
-
-    # ---- each layer against the interval built from the GPU's own previous layer (the three distinct images) ----
+def judge_layers(sd, imgs, acts, h, w, b, nref):
+    """Every layer of one run against the interval built from the GPU's own previous layer, for the first `nref` (distinct) images: `acts` as
+    _read_all returns them plus "grid".  -> (rows: tag -> {rel32, needed_c, violations, differs_from_rn16_ref}, failures: first lines of the
+    reports; the full report of a failing layer is printed).  Shared with test_gpu_weight_families.py, which runs it on other state dicts."""
     failures = []
     rows = {}
+    wkey = _weights_key(sd)   # the reference cache is shared by every state dict that passes through here
+
+    def _ref_of(key, x, make):
+        return _ref_of_input((wkey, key), x, make)
 
     def single(tag, name, src, dst):
         n_bad, need, differ, rel = 0, 0.0, 0.0, 0.0
@@ -199,6 +169,59 @@ def test_shipped_layers_against_fp64(hip, sp, weights_dir, parity_report, h, w, 
     near = R.rn16(v / np.maximum(np.sqrt((v * v).sum(-1, keepdims=True)), 1e-12)).transpose(0, 3, 1, 2)
     rows["grid k_desc_dense_chw"] = {"rel32": None, "needed_c": None, "eps": R.NORMALIZE_EPS, "violations": n_bad,
                                      "differs_from_rn16_ref": float((g != near).mean())}
+    return rows, failures
+
+
+@pytest.mark.parametrize("h,w,batch", CASES, ids=[f"{h}x{w}-B{b}" for h, w, b in CASES])
+def test_shipped_layers_against_fp64(hip, sp, weights_dir, parity_report, h, w, batch):
+    sd = weights_dir["sp"]
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    bstar = _b_star(h, w, cus)
+    b = {"B*": bstar, "B*+1": bstar + 1}.get(batch, batch)
+    (h2, w2), (h4, w4), (hc, wc) = _shapes(h, w)
+    # ---- which kernels this case reaches: a change of the library's rule must fail here, not silently lose the coverage ----
+    if (h, w) in ((136, 264), (200, 376)):
+        on8 = {name: _few_tiles(b, lh, lw, cout, cus) for name, lh, lw, cout, _ in _layers16(h, w)}
+        pairs = {name: _pairs_shape(pool, b, lw) for name, lh, lw, cout, pool in _layers16(h, w)}
+        print(f"{h}x{w} B={b} (B* = {bstar}, {cus} CUs): 8-row kernel {on8}, shared edge tiles {pairs}")
+        if batch == 2:
+            assert all(on8.values()), on8
+        elif batch == "B*":
+            assert b % 2 == 0 and not any(on8.values()), on8
+            assert pairs == {"conv3b": False, "conv4a": True, "conv4b": True, "convPa": True}, pairs   # Wc = 33 / 47: edge strips of 1 / 15
+        else:
+            assert b % 2 == 1 and not any(on8.values()) and not any(pairs.values()), (on8, pairs)
+    assert _conv2_fused(h, w) == ((h, w) != (8, 8))
+
+    uniq = [make_frame(h, w, s) for s in R.IMAGE_SEEDS]
+    imgs = np.stack([uniq[i % 3] for i in range(b)])
+    nref = min(b, 3)
+    dimg = torch.from_numpy(imgs).cuda()
+    scores, grid, logits = sp.dense(dimg, want_logits=True)
+    torch.cuda.synchronize()
+    acts = _read_all(hip, sp, b, h, w, heads=True)
+    acts["grid"] = grid.cpu().numpy()
+    logits = logits.cpu().numpy()
+    assert all(np.isfinite(a.astype(np.float32)).all() for a in acts.values())
+    # the [B,65,Hc,Wc] export is the layer-11 buffer, transposed
+    np.testing.assert_array_equal(logits, acts[11].transpose(0, 3, 1, 2))
+
+    # ---- every copy of an image equals its first copy bit for bit, at every layer ----
+    for l, a in acts.items():
+        v = a.view(np.uint16) if a.dtype == np.float16 else a.view(np.uint32)
+        for i in range(3, b):
+            assert np.array_equal(v[i], v[i % 3]), f"layer {l}: image {i} differs from its first copy {i % 3} (batch {b}, {h}x{w})"
+
+    # ---- extraction at the same shape and batch runs the same network: layers 1, 3 .. 8 and the logits bit-identical ----
+    sp.extract_batch_device(dimg)
+    torch.cuda.synchronize()
+    ext = _read_all(hip, sp, b, h, w, heads=False)
+    for l, a in ext.items():
+        assert np.array_equal(a.view(np.uint16 if a.dtype == np.float16 else np.uint32),
+                              acts[l].view(np.uint16 if a.dtype == np.float16 else np.uint32)), f"layer {l}: extraction and dense differ"
+
+    # ---- each layer against the interval built from the GPU's own previous layer (the three distinct images) ----
+    rows, failures = judge_layers(sd, imgs, acts, h, w, b, nref)
     for tag, row in rows.items():
         print(f"{h}x{w} B={b} {tag}: {row}")
     # per layer: rel32, the margin actually needed, violations, the share of outputs that differ from RN16(ref) - saved with the suite's parity
