@@ -1489,6 +1489,66 @@ int sship_patch_track_pyramid_host(const uint8_t* img0, int stride0, const uint8
                                    float* kp_out, int32_t* matches0, uint8_t* status, int64_t* cost, uint8_t* levels_tracked);
 
 /* ------------------------------------------------------------------------------------------------
+ * CLAHE - contrast-limited adaptive histogram equalisation of a batch of u8 images on the device: the stage in front of the patch
+ * trackers and the stereo search above, whose zero-mean SSD cost forgives a brightness offset and nothing else (a gain between the two
+ * cameras, or between two frames of an auto-exposure camera, is paid in accuracy).  VINS-Mono / VINS-Fusion (`equalize: 1`) and OpenVINS
+ * (`histogram_method: CLAHE`) equalise in front of their trackers; here the image stays on the device.  The rule is modelled on OpenCV's
+ * 8-bit cv::CLAHE; equality with cv::CLAHE is the intent, not a measured fact (OpenCV is on none of this project's machines), exactly as
+ * for the rectification remap and cv::pyrDown.  tests/_clahe_ref.py restates this text.  Integers plus a handful of fp32 operations that
+ * are each rounded once (round to nearest even, no fused multiply-add): an image has the same bits alone, at any position of any batch,
+ * at any pointer alignment or stride, and on the host entry.
+ *   Parameters: tiles_x, tiles_y in 1 .. 16; clip_limit fp64, finite, >= 0 (0: no clipping).  S is the h x w source, h, w <= 16384.
+ *   Extension.  If w % tiles_x == 0 and h % tiles_y == 0: (ew, eh) = (w, h).  Otherwise ew = w + (tiles_x - w % tiles_x) and
+ *     eh = h + (tiles_y - h % tiles_y) - an axis that already divides grows by a whole `tiles` pixels when the other does not divide
+ *     (OpenCV's behaviour, kept).  E(y, x) = S(r(y, h), r(x, w)) with reflect-101: r(i, n) = i for i < n, else 2 (n - 1) - i.  The call is
+ *     refused unless ew - w <= w - 1 and eh - h <= h - 1 (one reflection lands inside).
+ *   Tiles.  tw = ew / tiles_x, th = eh / tiles_y, A = tw th; refused unless A <= 2^24, so that every partial sum is an exact fp32.
+ *   Limit.  clip_limit > 0: L = min(A, max(1, trunc((clip_limit * A) / 256))), product and quotient in fp64.  Otherwise no clipping.
+ *   Histogram of tile (j, i): the 256 counts hist[v] of E over rows [j th, (j + 1) th) and columns [i tw, (i + 1) tw).
+ *   Clip (with a limit only).  clipped = sum over v of max(hist[v] - L, 0); hist[v] = min(hist[v], L); batch = clipped / 256 and
+ *     residual = clipped % 256 (integers); every bin += batch; if residual > 0: step = max(256 / residual, 1) (integer) and the bins
+ *     0, step, 2 step, ... each += 1, stopping after `residual` bins or at bin 256, whichever comes first (always `residual` bins: the
+ *     histogram still sums to A).
+ *   Table.  s_v = hist[0] + ... + hist[v]; lut[v] = sat_u8(rint((float)s_v * scale)), scale = 255.f / (float)A (one fp32 division).
+ *   Output pixel (y, x), v = S(y, x):
+ *     txf = (float)x * inv_tw - 0.5f, inv_tw = 1.f / (float)tw;  t1 = floor(txf);  xa = txf - (float)t1;  xa1 = 1.f - xa;
+ *     tx2 = min(t1 + 1, tiles_x - 1);  tx1 = max(t1, 0);  the same in y with inv_th = 1.f / (float)th: ty1, ty2, ya, ya1;
+ *     res = (lut[ty1][tx1][v] xa1 + lut[ty1][tx2][v] xa) ya1 + (lut[ty2][tx1][v] xa1 + lut[ty2][tx2][v] xa) ya,
+ *     the table entries converted to fp32, every product and every sum rounded once to fp32 in exactly this association;
+ *     D(y, x) = sat_u8(rint(res)).  Exact halves are common (thousands per EuRoC-sized image): the rounding mode matters.
+ *   scale, inv_tw, inv_th and L are formed on the host and passed to the kernels by value: no device division enters the rule.
+ * A handle is made for one image size, one tile grid and at most max_images (1 .. 65 535) images; it owns the table workspace
+ * [max_images, tiles_y, tiles_x, 256] u8, and nothing is allocated after sship_clahe_create.  sship_clahe_set_clip_limit changes the
+ * limit for the calls that follow; sship_clahe_get_params reads the handle back (every output pointer is optional).
+ * sship_clahe_apply_batch_device equalises images [0, images): image i is read at src_dev + i * src_image_stride in rows of src_stride
+ * bytes and written at dst_dev + i * dst_image_stride in rows of dst_stride bytes, all strides in bytes, row strides >= w, image strides
+ * >= 0, no alignment asked of pointers or strides (src_image_stride = 2 * h * stride reads the left images of an L0, R0, L1, R1, ...
+ * batch).  dst_dev == src_dev with equal strides is allowed (in place); any other overlap of source and destination is undefined.  Two
+ * launches (tables, then pixels), asynchronous on `stream`, no host synchronisation; every destination pixel is written and nothing
+ * outside w bytes of a row.  sship_clahe_read_luts copies the tables of images [first, first + count) of the last call to the host,
+ * [count, tiles_y, tiles_x, 256] u8 (synchronous; it waits for the device).  sship_clahe_apply_host is one image from host arrays,
+ * staged through one device block - the drop-in for one cv::CLAHE::apply; the same two launches with images = 1, hence the same bits.
+ * sship_clahe_bench re-runs the last call's two launches `iters` times on the handle's stream (*avg_ms per call; an in-place call is
+ * re-run on its own output); sship_clahe_bench_kernels the chosen ones (1: the tables, 2: the pixels, 3: both).
+ * A NULL required pointer, h or w outside [1, 16384], tiles outside [1, 16], either extension condition, A > 2^24, a negative or
+ * non-finite clip limit, max_images outside [1, 65535], images outside [1, max_images], a row stride < w, a negative image stride, or
+ * tables asked for before the first call is SSHIP_ERR_INVALID before any device is touched; valid create arguments without a GPU are
+ * SSHIP_ERR_NO_DEVICE.  Not wired into sship_frontend_batch_device; 8-bit images only.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sship_clahe sship_clahe;
+int sship_clahe_create(int h, int w, int tiles_x, int tiles_y, double clip_limit, int max_images, sship_clahe** out);
+void sship_clahe_destroy(sship_clahe* clahe);
+int sship_clahe_set_clip_limit(sship_clahe* clahe, double clip_limit);
+int sship_clahe_get_params(const sship_clahe* clahe, int* h, int* w, int* tiles_x, int* tiles_y, double* clip_limit, int* max_images);
+int sship_clahe_apply_batch_device(sship_clahe* clahe, const uint8_t* src_dev, long long src_image_stride, int src_stride, uint8_t* dst_dev,
+                                   long long dst_image_stride, int dst_stride, int images, void* stream);
+int sship_clahe_read_luts(const sship_clahe* clahe, int first, int count, uint8_t* out_host);
+int sship_clahe_apply_host(const uint8_t* src, int src_stride, int h, int w, int tiles_x, int tiles_y, double clip_limit, uint8_t* dst,
+                           int dst_stride);
+int sship_clahe_bench(sship_clahe* clahe, int iters, float* avg_ms);
+int sship_clahe_bench_kernels(sship_clahe* clahe, int kernels, int iters, float* avg_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused front-end step: what StereoFrontEnd::process asks of the two interfaces per frame
  * (src/StereoFrontEnd.cc:14,33): SuperPoint on L and R (one batch) + gather x2 + one LightGlue match,
  * for `pairs` stereo pairs at once, device-resident, no host synchronisation.  imgs_dev is

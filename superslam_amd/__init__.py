@@ -7,6 +7,7 @@ from . import _lib  # noqa: F401
 from .eigenplaces import EigenPlaces  # noqa: F401
 from .frontend import (FrontEndBatch, patch_track, patch_track_batch, patch_track_stereo_batch, process_stereo,  # noqa: F401
                        rgbd_associate_batch, stereo_associate_batch, stereo_refine, stereo_refine_batch, stereo_search, stereo_search_batch)
+from .clahe import Clahe, clahe  # noqa: F401
 from .lightglue import LightGlue, LightGlueEngine, MatchResult  # noqa: F401
 from .nn_matcher import NNMatcher  # noqa: F401
 from .place_index import PlaceIndex  # noqa: F401
@@ -24,4 +25,4 @@ __all__ = ["SuperPoint", "LightGlue", "LightGlueEngine", "MatchResult", "Feature
            "track_batch", "RansacVerifier", "verify_batch", "WindowSmoother", "smooth_batch", "PoseGraph", "close_loops_batch", "Rectifier", "build_maps",
            "rgbd_associate_batch", "stereo_refine_batch", "stereo_refine", "stereo_search_batch", "stereo_search",
            "patch_track_batch", "patch_track", "patch_track_stereo_batch", "ImagePyramid", "pyr_down", "patch_track_pyramid_batch",
-           "patch_track_pyramid", "pyr_track_params"]
+           "patch_track_pyramid", "pyr_track_params", "Clahe", "clahe"]

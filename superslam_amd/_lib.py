@@ -268,6 +268,15 @@ _SIGS = {
     "sship_patch_track_pyramid_batch_device": (ip, [vp, ip, ip, vp, ip, ip, ip, vp, vp, ip, vp, ip, C.POINTER(PyrTrackParams), vp, vp, vp, vp,
                                                     vp, vp, vp]),
     "sship_patch_track_pyramid_host": (ip, [vp, ip, vp, ip, ip, ip, vp, ip, vp, ip, ip, C.POINTER(PyrTrackParams), vp, vp, vp, vp, vp]),
+    "sship_clahe_create": (ip, [ip, ip, ip, ip, dp, ip, C.POINTER(vp)]),
+    "sship_clahe_destroy": (None, [vp]),
+    "sship_clahe_set_clip_limit": (ip, [vp, dp]),
+    "sship_clahe_get_params": (ip, [vp, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(dp), C.POINTER(ip)]),
+    "sship_clahe_apply_batch_device": (ip, [vp, vp, C.c_longlong, ip, vp, C.c_longlong, ip, ip, vp]),
+    "sship_clahe_read_luts": (ip, [vp, ip, ip, vp]),
+    "sship_clahe_apply_host": (ip, [vp, ip, ip, ip, ip, ip, dp, vp, ip]),
+    "sship_clahe_bench": (ip, [vp, ip, C.POINTER(fp)]),
+    "sship_clahe_bench_kernels": (ip, [vp, ip, ip, C.POINTER(fp)]),
     "sship_desc_to_host": (ip, [vp, ip, ip, vp]),
     "sship_frontend_batch_device": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_bench_layer": (ip, [vp, ip, ip, ip, ip, ip, C.POINTER(fp), C.POINTER(C.c_double)]),

@@ -4702,6 +4702,146 @@ extern "C" int sship_patch_track_pyramid_host(const uint8_t* img0, int stride0, 
 }
 
 // ====================================================================================================
+// contrast-limited adaptive histogram equalisation (sship_clahe_*; the rule is in include/sship.h)
+// ====================================================================================================
+struct sship_clahe {
+  int h = 0, w = 0, max_images = 0;
+  double clip_limit = 0.0;
+  ClaheK k = {};
+  hipStream_t stream = nullptr;
+  DevBuf luts;   // [max_images, tiles_y, tiles_x, 256] u8
+  // the last call
+  const uint8_t* src = nullptr;
+  uint8_t* dst = nullptr;
+  long long src_image_stride = 0, dst_image_stride = 0;
+  int src_stride = 0, dst_stride = 0, images = 0;
+  size_t image_luts() const { return (size_t)k.tiles_x * k.tiles_y * 256; }
+};
+static int clahe_check_clip(double clip_limit, const char* who) {
+  if (!std::isfinite(clip_limit) || clip_limit < 0.0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": clip_limit must be finite and >= 0");
+  return SSHIP_OK;
+}
+// L of the rule (0: no clipping): the product and the quotient in fp64, truncated
+static int clahe_limit(double clip_limit, int area) {
+  if (clip_limit == 0.0) return 0;
+  const double q = (clip_limit * (double)area) / 256.0;
+  if (q >= (double)area) return area;
+  return std::max(1, (int)q);
+}
+// the size checks every entry shares; fills the kernels' constants
+static int clahe_geometry(int h, int w, int tiles_x, int tiles_y, double clip_limit, ClaheK* k, const char* who) {
+  if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, std::string(who) + ": h and w must be in [1, 16384]");
+  if (tiles_x < 1 || tiles_x > kClaheMaxTiles || tiles_y < 1 || tiles_y > kClaheMaxTiles)
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": tiles_x and tiles_y must be in [1, 16]");
+  if (int rc = clahe_check_clip(clip_limit, who)) return rc;
+  int ew = w, eh = h;
+  if (w % tiles_x != 0 || h % tiles_y != 0) { ew = w + (tiles_x - w % tiles_x); eh = h + (tiles_y - h % tiles_y); }
+  if (ew - w > w - 1 || eh - h > h - 1)
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": the image is too small for its extension (needs ew - w <= w - 1 and eh - h <= h - 1)");
+  const int tw = ew / tiles_x, th = eh / tiles_y;
+  if ((long long)tw * th > kClaheMaxArea) return fail(SSHIP_ERR_INVALID, std::string(who) + ": a tile must hold at most 2^24 pixels");
+  const int area = tw * th;
+  *k = ClaheK{tiles_x, tiles_y, tw, th, clahe_limit(clip_limit, area), 255.0f / (float)area, 1.0f / (float)tw, 1.0f / (float)th};
+  return SSHIP_OK;
+}
+extern "C" int sship_clahe_create(int h, int w, int tiles_x, int tiles_y, double clip_limit, int max_images, sship_clahe** out) {
+  if (!out) return fail(SSHIP_ERR_INVALID, "clahe_create: null argument");
+  *out = nullptr;
+  ClaheK k;
+  if (int rc = clahe_geometry(h, w, tiles_x, tiles_y, clip_limit, &k, "clahe_create")) return rc;
+  if (max_images < 1 || max_images > 65535) return fail(SSHIP_ERR_INVALID, "clahe_create: max_images must be in [1, 65535]");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  std::unique_ptr<sship_clahe, void (*)(sship_clahe*)> p(new sship_clahe(), sship_clahe_destroy);
+  p->h = h; p->w = w; p->max_images = max_images; p->clip_limit = clip_limit; p->k = k;
+  SSHIP_HIP_CHECK(p->luts.ensure(p->image_luts() * max_images));
+  SSHIP_HIP_CHECK(hipMemset(p->luts.p, 0, p->image_luts() * max_images));
+  SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&p->stream, hipStreamDefault));
+  *out = p.release();
+  return SSHIP_OK;
+}
+extern "C" void sship_clahe_destroy(sship_clahe* clahe) { destroy_handle(clahe); }
+extern "C" int sship_clahe_set_clip_limit(sship_clahe* clahe, double clip_limit) {
+  if (!clahe) return fail(SSHIP_ERR_INVALID, "clahe_set_clip_limit: null argument");
+  if (int rc = clahe_check_clip(clip_limit, "clahe_set_clip_limit")) return rc;
+  clahe->clip_limit = clip_limit;
+  clahe->k.limit = clahe_limit(clip_limit, clahe->k.tw * clahe->k.th);   // by value into the next call's launches
+  return SSHIP_OK;
+}
+extern "C" int sship_clahe_get_params(const sship_clahe* clahe, int* h, int* w, int* tiles_x, int* tiles_y, double* clip_limit, int* max_images) {
+  if (!clahe) return fail(SSHIP_ERR_INVALID, "clahe_get_params: null argument");
+  if (h) *h = clahe->h;
+  if (w) *w = clahe->w;
+  if (tiles_x) *tiles_x = clahe->k.tiles_x;
+  if (tiles_y) *tiles_y = clahe->k.tiles_y;
+  if (clip_limit) *clip_limit = clahe->clip_limit;
+  if (max_images) *max_images = clahe->max_images;
+  return SSHIP_OK;
+}
+// the last call's launches: bit 0 the tables, bit 1 the pixels
+static void clahe_launch(const sship_clahe* c, int kernels, hipStream_t s) {
+  if (kernels & 1) launch_clahe_lut(c->src, c->src_image_stride, c->src_stride, c->h, c->w, c->k, c->luts.as<uint8_t>(), c->images, s);
+  if (kernels & 2)
+    launch_clahe_apply(c->src, c->src_image_stride, c->src_stride, c->dst, c->dst_image_stride, c->dst_stride, c->h, c->w, c->k, c->luts.as<uint8_t>(),
+                       c->images, s);
+}
+extern "C" int sship_clahe_apply_batch_device(sship_clahe* clahe, const uint8_t* src, long long src_image_stride, int src_stride, uint8_t* dst,
+                                              long long dst_image_stride, int dst_stride, int images, void* stream) {
+  if (!clahe || !src || !dst) return fail(SSHIP_ERR_INVALID, "clahe_apply_batch_device: null argument");
+  if (images < 1 || images > clahe->max_images) return fail(SSHIP_ERR_INVALID, "clahe_apply_batch_device: images must be in [1, max_images]");
+  if (src_stride < clahe->w || dst_stride < clahe->w) return fail(SSHIP_ERR_INVALID, "clahe_apply_batch_device: stride (bytes) must be >= w");
+  if (src_image_stride < 0 || dst_image_stride < 0) return fail(SSHIP_ERR_INVALID, "clahe_apply_batch_device: image_stride (bytes) must be >= 0");
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  clahe->src = src; clahe->src_image_stride = src_image_stride; clahe->src_stride = src_stride;
+  clahe->dst = dst; clahe->dst_image_stride = dst_image_stride; clahe->dst_stride = dst_stride; clahe->images = images;
+  clahe_launch(clahe, 3, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("clahe", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_clahe_read_luts(const sship_clahe* clahe, int first, int count, uint8_t* out) {
+  if (!clahe || !out) return fail(SSHIP_ERR_INVALID, "clahe_read_luts: null argument");
+  if (clahe->images <= 0) return fail(SSHIP_ERR_INVALID, "clahe_read_luts: apply the handle first");
+  if (first < 0 || count < 1 || (long long)first + count > clahe->images)
+    return fail(SSHIP_ERR_INVALID, "clahe_read_luts: first and count must name images of the last call");
+  bind_thread();
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());   // the call may have run on the caller's stream
+  SSHIP_HIP_CHECK(hipMemcpy(out, clahe->luts.as<uint8_t>() + (size_t)first * clahe->image_luts(), (size_t)count * clahe->image_luts(), hipMemcpyDeviceToHost));
+  return SSHIP_OK;
+}
+extern "C" int sship_clahe_apply_host(const uint8_t* src, int src_stride, int h, int w, int tiles_x, int tiles_y, double clip_limit, uint8_t* dst,
+                                      int dst_stride) {
+  if (!src || !dst) return fail(SSHIP_ERR_INVALID, "clahe_apply_host: null argument");
+  ClaheK k;
+  if (int rc = clahe_geometry(h, w, tiles_x, tiles_y, clip_limit, &k, "clahe_apply_host")) return rc;
+  if (src_stride < w || dst_stride < w) return fail(SSHIP_ERR_INVALID, "clahe_apply_host: stride (bytes) must be >= w");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  StageLayout lay;   // one device block for the call: the image packed to stride w, the result likewise, the tables
+  const size_t o_src = lay.add((size_t)h * w), o_dst = lay.add((size_t)h * w), o_luts = lay.add((size_t)tiles_x * tiles_y * 256);
+  StageArena a;
+  SSHIP_HIP_CHECK(a.create(lay.end, 0, false));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_src), (size_t)w, src, (size_t)src_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  launch_clahe_lut(a.dev<uint8_t>(o_src), 0, w, h, w, k, a.dev<uint8_t>(o_luts), 1, nullptr);
+  launch_clahe_apply(a.dev<uint8_t>(o_src), 0, w, a.dev<uint8_t>(o_dst), 0, w, h, w, k, a.dev<uint8_t>(o_luts), 1, nullptr);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  SSHIP_HIP_CHECK(hipMemcpy2D(dst, (size_t)dst_stride, a.dev<uint8_t>(o_dst), (size_t)w, (size_t)w, (size_t)h, hipMemcpyDeviceToHost));   // blocking, on the NULL stream: after the launches
+  return SSHIP_OK;
+}
+// Measurement hooks (include/sship.h): the last call's launches re-run `iters` times on the handle's stream; kernels: 1 the tables, 2 the
+// pixels, 3 both
+extern "C" int sship_clahe_bench_kernels(sship_clahe* clahe, int kernels, int iters, float* avg_ms) {
+  if (!clahe || !avg_ms || iters <= 0 || kernels < 1 || kernels > 3) return fail(SSHIP_ERR_INVALID, "clahe_bench: bad arguments");
+  if (clahe->images <= 0) return fail(SSHIP_ERR_INVALID, "clahe_bench: apply the handle first");
+  bind_thread();
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());   // the last call may have run on the caller's stream
+  return bench_loop(clahe->stream, iters, [&]() { clahe_launch(clahe, kernels, clahe->stream); return hipGetLastError(); }, avg_ms);
+}
+extern "C" int sship_clahe_bench(sship_clahe* clahe, int iters, float* avg_ms) { return sship_clahe_bench_kernels(clahe, 3, iters, avg_ms); }
+
+// ====================================================================================================
 // fused front-end step: SuperPoint(batch 2P) + select + gather + LightGlue(P)
 // ====================================================================================================
 extern "C" int sship_frontend_batch_device(sship_sp* sp, sship_lg* lg, const uint8_t* imgs, int pairs, int h, int w,

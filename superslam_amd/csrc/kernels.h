@@ -389,4 +389,16 @@ void launch_pyr_track(const PyrTrackLevels& tab, int pairs, const float* kp, con
                       const PyrTrackK& c, float* kp_out, int* n_out, int* matches0, uint8_t* status, long long* cost, uint8_t* levels_tracked,
                       hipStream_t s);
 
+// contrast-limited adaptive histogram equalisation (clahe_kernels.hip)
+constexpr int kClaheMaxTiles = 16, kClaheMaxArea = 1 << 24, kClaheBlockW = 256, kClaheBlockH = 32;
+// the rule's constants, all formed on the host: tiles of tw x th pixels of the extended image, limit = L (0: no clipping),
+// scale = 255.f / (float)(tw * th), inv_tw = 1.f / (float)tw, inv_th = 1.f / (float)th
+struct ClaheK { int tiles_x, tiles_y, tw, th, limit; float scale, inv_tw, inv_th; };
+// the two launches of one call: the tables of `images` images into luts [images, tiles_y, tiles_x, 256] (16-byte aligned), then every
+// destination pixel from them.  Strides in bytes, no alignment asked; dst may be src with equal strides.
+void launch_clahe_lut(const uint8_t* src, long long src_image_stride, long long src_stride, int h, int w, const ClaheK& c, uint8_t* luts,
+                      int images, hipStream_t s);
+void launch_clahe_apply(const uint8_t* src, long long src_image_stride, long long src_stride, uint8_t* dst, long long dst_image_stride,
+                        long long dst_stride, int h, int w, const ClaheK& c, const uint8_t* luts, int images, hipStream_t s);
+
 }  // namespace sship
