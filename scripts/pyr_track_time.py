@@ -12,7 +12,8 @@ k_pyr_track) next to the plain tracker, in one run on one machine.
    Device events around `iters` calls of the Python functions (launch overhead is inside).
 The configurations alternate inside each of the 7 rounds; the median of the rounds.  The box's sustained MFMA probe reading is recorded with
 the numbers (the README's box-to-box spread is +-3 %).
-usage: python scripts/pyr_track_time.py [--out FILE]
+usage: python scripts/pyr_track_time.py [--out FILE] [--library LIB]
+  --library LIB       measure another build of the library
 """
 import ctypes as C
 import json
@@ -25,7 +26,11 @@ import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from superslam_amd import ImagePyramid, _lib, patch_track_batch, patch_track_pyramid_batch  # noqa: E402
+from superslam_amd import _lib  # noqa: E402
+
+if "--library" in sys.argv:
+    _lib.set_library_path(sys.argv[sys.argv.index("--library") + 1])
+from superslam_amd import ImagePyramid, patch_track_batch, patch_track_pyramid_batch  # noqa: E402
 from superslam_amd.synth import make_stereo_pair  # noqa: E402
 
 ROUNDS = 7
@@ -90,6 +95,7 @@ def main(pairs=512, k=600, h=376, w=1376, images=1024, iters=10, build_iters=50)
                    "k_patch_track through patch_track_batch (device events around the Python calls, so launch overhead is inside); milliseconds, "
                    "the median of `rounds` rounds, the configurations alternating.  The pyramids of the tracker configurations are built outside "
                    "the timed region.  What bounds either kernel was not measured (no counter run).",
+           "library": os.path.relpath(_lib.LIB_PATH, ROOT) if "--library" in sys.argv else "shipped",
            "mfma_probe_tflops_random": round(float(probe.value), 1), "rounds": ROUNDS,
            "build": dict(images=images, size=[w, h], level_shapes=shapes, bytes=build_bytes, ms=round(med["build"], 4),
                          ms_min_max=[round(min(ms["build"]), 4), round(max(ms["build"]), 4)], GB_per_s=round(build_bytes / med["build"] / 1e6, 1),

@@ -4257,20 +4257,48 @@ extern "C" int sship_rgbd_associate_host(const float* keypoints, int kp_stride, 
 }
 
 // ====================================================================================================
+// what the patch-search entries share (stereo refinement and search, patch and pyramid tracker)
+// ====================================================================================================
+static int size_check(int h, int w, const char* who) {
+  if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, std::string(who) + ": h and w must be in [1, 16384]");
+  return SSHIP_OK;
+}
+// a per-pixel threshold (min_texture, max_rms) as the kernels test it: on if > 0, and (value pw^2)^2
+static void patch_threshold(float value, int pw, int* on, double* squared) {
+  const double t = (double)value * (double)(pw * pw);
+  *on = value > 0.f ? 1 : 0;
+  *squared = t * t;
+}
+// One image pair per call, staged through one device block of the call's own (pair_stage in csrc/stage_layout.h).  The copies stay blocking
+// and, for the images and the outputs, straight from / to the caller's memory.  `tail`: the packed input region from the count on.
+static int pair_upload(StageArena& a, const PairStage& st, const uint8_t* img0, int stride0, const uint8_t* img1, int stride1, int h, int w,
+                       const std::vector<char>& tail) {
+  SSHIP_HIP_CHECK(a.create(st.in_bytes, st.out_bytes, false));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(st.img), (size_t)w, img0, (size_t)stride0, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(st.img1), (size_t)w, img1, (size_t)stride1, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<char>(st.n), tail.data(), st.tail_bytes, hipMemcpyHostToDevice));
+  return SSHIP_OK;
+}
+// the outputs the caller asked for (dst != NULL): blocking copies on the NULL stream, so ordered after the launch
+struct PairOut { void* dst; size_t off, bytes; };
+static int pair_fetch(const StageArena& a, std::initializer_list<PairOut> outs) {
+  for (const PairOut& o : outs)
+    if (o.dst) { SSHIP_HIP_CHECK(hipMemcpy(o.dst, a.dev<char>(a.out + o.off), o.bytes, hipMemcpyDeviceToHost)); }
+  return SSHIP_OK;
+}
+
+// ====================================================================================================
 // sub-pixel disparity refinement by patch correlation (the rule is in include/sship.h)
 // ====================================================================================================
 // the checks both entries share; fills the kernel's constants
 static int refine_check(int h, int w, const sship_stereo_refine_params* p, StereoRefineK* c, const char* who) {
-  if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, std::string(who) + ": h and w must be in [1, 16384]");
+  if (int rc = size_check(h, w, who)) return rc;
   if (p->half_window < 1 || p->half_window > 7) return fail(SSHIP_ERR_INVALID, std::string(who) + ": half_window must be in [1, 7]");
   if (p->search_radius < 1 || p->search_radius > 15) return fail(SSHIP_ERR_INVALID, std::string(who) + ": search_radius must be in [1, 15]");
   if (std::isnan(p->max_rms) || std::isnan(p->min_disparity)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": max_rms and min_disparity must not be NaN");
   if (p->on_reject != SSHIP_REFINE_KEEP && p->on_reject != SSHIP_REFINE_DROP)
     return fail(SSHIP_ERR_INVALID, std::string(who) + ": on_reject must be 0 (keep) or 1 (drop)");
-  const int pw = 2 * p->half_window + 1;
-  const double t = (double)p->max_rms * (double)(pw * pw);
-  c->gate = p->max_rms > 0.f ? 1 : 0;
-  c->gate2 = t * t;
+  patch_threshold(p->max_rms, 2 * p->half_window + 1, &c->gate, &c->gate2);
   c->min_disparity = p->min_disparity;
   c->half_window = p->half_window; c->search_radius = p->search_radius;
   c->drop = p->on_reject == SSHIP_REFINE_DROP ? 1 : 0;
@@ -4310,24 +4338,19 @@ extern "C" int sship_stereo_refine_host(const uint8_t* left, int left_stride, co
   if (!stereo || !has_depth || !stereo_out || !has_depth_out) return fail(SSHIP_ERR_INVALID, "stereo_refine_host: null argument");
   bind_thread();
   if (int rc = require_device()) return rc;
-  const size_t img = (size_t)h * w, kb = (size_t)n * 3 * sizeof(float);
-  StageLayout lay;   // one device block for the call: the pair packed to stride w, then the per-keypoint arrays (refined in place)
-  const size_t o_left = lay.add(2 * img), o_right = o_left + img, o_n = lay.add(sizeof(int)), o_st = lay.add(kb), o_hd = lay.add((size_t)n),
-               o_status = lay.add((size_t)n), o_cost = lay.add((size_t)n * sizeof(int64_t));
+  const PairStage st = pair_stage(h, w, n);
+  const size_t m = (size_t)n;
+  std::vector<char> tail(st.tail_bytes, 0);
+  pair_pack_n(tail.data(), n);
   StageArena a;
-  SSHIP_HIP_CHECK(a.create(lay.end, 0, false));
-  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_left), (size_t)w, left, (size_t)left_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_right), (size_t)w, right, (size_t)right_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(a.dev<int>(o_n), &n, sizeof(int), hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(a.dev<float>(o_st), stereo, kb, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(a.dev<uint8_t>(o_hd), has_depth, (size_t)n, hipMemcpyHostToDevice));
-  if (int rc = sship_stereo_refine_batch_device(a.dev<uint8_t>(o_left), 1, h, w, w, a.dev<float>(o_st), a.dev<uint8_t>(o_hd), a.dev<int>(o_n), 1, n, p,
-                                                a.dev<float>(o_st), a.dev<uint8_t>(o_hd), a.dev<uint8_t>(o_status), a.dev<int64_t>(o_cost), nullptr)) return rc;
-  SSHIP_HIP_CHECK(hipMemcpy(stereo_out, a.dev<float>(o_st), kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launch
-  SSHIP_HIP_CHECK(hipMemcpy(has_depth_out, a.dev<uint8_t>(o_hd), (size_t)n, hipMemcpyDeviceToHost));
-  if (status) { SSHIP_HIP_CHECK(hipMemcpy(status, a.dev<uint8_t>(o_status), (size_t)n, hipMemcpyDeviceToHost)); }
-  if (cost) { SSHIP_HIP_CHECK(hipMemcpy(cost, a.dev<int64_t>(o_cost), (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost)); }
-  return SSHIP_OK;
+  if (int rc = pair_upload(a, st, left, left_stride, right, right_stride, h, w, tail)) return rc;
+  float* rows = a.dev<float>(a.out + st.rows);              // the caller's rows go straight into the output slots: refined in place
+  uint8_t* hd = a.dev<uint8_t>(a.out + st.flag);
+  SSHIP_HIP_CHECK(hipMemcpy(rows, stereo, st.rows_bytes, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(hd, has_depth, m, hipMemcpyHostToDevice));
+  if (int rc = sship_stereo_refine_batch_device(a.dev<uint8_t>(st.img), 1, h, w, w, rows, hd, a.dev<int>(st.n), 1, n, p, rows, hd,
+                                                a.dev<uint8_t>(a.out + st.status), a.dev<int64_t>(a.out + st.cost), nullptr)) return rc;
+  return pair_fetch(a, {{stereo_out, st.rows, st.rows_bytes}, {has_depth_out, st.flag, m}, {status, st.status, m}, {cost, st.cost, m * 8}});
 }
 
 // ====================================================================================================
@@ -4335,7 +4358,7 @@ extern "C" int sship_stereo_refine_host(const uint8_t* left, int left_stride, co
 // ====================================================================================================
 // the checks both entries share; fills the kernel's constants
 static int search_check(int h, int w, const sship_stereo_search_params* p, StereoSearchK* c, const char* who) {
-  if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, std::string(who) + ": h and w must be in [1, 16384]");
+  if (int rc = size_check(h, w, who)) return rc;
   if (p->half_window < 1 || p->half_window > 7) return fail(SSHIP_ERR_INVALID, std::string(who) + ": half_window must be in [1, 7]");
   if (p->min_disparity < 0 || p->max_disparity < p->min_disparity)
     return fail(SSHIP_ERR_INVALID, std::string(who) + ": 0 <= min_disparity <= max_disparity is required");
@@ -4344,12 +4367,8 @@ static int search_check(int h, int w, const sship_stereo_search_params* p, Stere
   if (p->uniqueness < 0 || p->uniqueness > 99) return fail(SSHIP_ERR_INVALID, std::string(who) + ": uniqueness must be in [0, 99]");
   if (p->lr_check < -1 || p->lr_check > 16) return fail(SSHIP_ERR_INVALID, std::string(who) + ": lr_check must be in [-1, 16]");
   if (std::isnan(p->min_texture) || std::isnan(p->max_rms)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": min_texture and max_rms must not be NaN");
-  const int pw = 2 * p->half_window + 1;
-  const double tt = (double)p->min_texture * (double)(pw * pw), tr = (double)p->max_rms * (double)(pw * pw);
-  c->tex = p->min_texture > 0.f ? 1 : 0;
-  c->tex2 = tt * tt;
-  c->gate = p->max_rms > 0.f ? 1 : 0;
-  c->gate2 = tr * tr;
+  patch_threshold(p->min_texture, 2 * p->half_window + 1, &c->tex, &c->tex2);
+  patch_threshold(p->max_rms, 2 * p->half_window + 1, &c->gate, &c->gate2);
   c->half_window = p->half_window; c->dlo = p->min_disparity; c->dhi = p->max_disparity;
   c->uniqueness = p->uniqueness; c->lr = p->lr_check;
   return SSHIP_OK;
@@ -4386,25 +4405,17 @@ extern "C" int sship_stereo_search_host(const uint8_t* left, int left_stride, co
   if (!keypoints || !stereo_out || !has_depth_out) return fail(SSHIP_ERR_INVALID, "stereo_search_host: null argument");
   bind_thread();
   if (int rc = require_device()) return rc;
-  std::vector<float> kp((size_t)n * 3, 0.f);
-  for (int i = 0; i < n; ++i) { kp[3 * i] = keypoints[(size_t)i * kp_stride]; kp[3 * i + 1] = keypoints[(size_t)i * kp_stride + 1]; }
-  const size_t img = (size_t)h * w, kb = (size_t)n * 3 * sizeof(float);
-  StageLayout lay;   // one device block for the call: the pair packed to stride w, then the per-keypoint arrays
-  const size_t o_left = lay.add(2 * img), o_right = o_left + img, o_n = lay.add(sizeof(int)), o_kp = lay.add(kb), o_st = lay.add(kb),
-               o_hd = lay.add((size_t)n), o_status = lay.add((size_t)n), o_cost = lay.add((size_t)n * sizeof(int64_t));
+  const PairStage st = pair_stage(h, w, n);
+  const size_t m = (size_t)n;
+  std::vector<char> tail(st.tail_bytes, 0);
+  pair_pack_n(tail.data(), n);
+  pair_pack_kp(tail.data(), st, keypoints, kp_stride, n, false);
   StageArena a;
-  SSHIP_HIP_CHECK(a.create(lay.end, 0, false));
-  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_left), (size_t)w, left, (size_t)left_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_right), (size_t)w, right, (size_t)right_stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(a.dev<int>(o_n), &n, sizeof(int), hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(a.dev<float>(o_kp), kp.data(), kb, hipMemcpyHostToDevice));
-  if (int rc = sship_stereo_search_batch_device(a.dev<uint8_t>(o_left), 1, h, w, w, a.dev<float>(o_kp), a.dev<int>(o_n), 1, n, p, a.dev<float>(o_st),
-                                                a.dev<uint8_t>(o_hd), a.dev<uint8_t>(o_status), a.dev<int64_t>(o_cost), nullptr)) return rc;
-  SSHIP_HIP_CHECK(hipMemcpy(stereo_out, a.dev<float>(o_st), kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launch
-  SSHIP_HIP_CHECK(hipMemcpy(has_depth_out, a.dev<uint8_t>(o_hd), (size_t)n, hipMemcpyDeviceToHost));
-  if (status) { SSHIP_HIP_CHECK(hipMemcpy(status, a.dev<uint8_t>(o_status), (size_t)n, hipMemcpyDeviceToHost)); }
-  if (cost) { SSHIP_HIP_CHECK(hipMemcpy(cost, a.dev<int64_t>(o_cost), (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost)); }
-  return SSHIP_OK;
+  if (int rc = pair_upload(a, st, left, left_stride, right, right_stride, h, w, tail)) return rc;
+  if (int rc = sship_stereo_search_batch_device(a.dev<uint8_t>(st.img), 1, h, w, w, a.dev<float>(st.kp), a.dev<int>(st.n), 1, n, p,
+                                                a.dev<float>(a.out + st.rows), a.dev<uint8_t>(a.out + st.flag), a.dev<uint8_t>(a.out + st.status),
+                                                a.dev<int64_t>(a.out + st.cost), nullptr)) return rc;
+  return pair_fetch(a, {{stereo_out, st.rows, st.rows_bytes}, {has_depth_out, st.flag, m}, {status, st.status, m}, {cost, st.cost, m * 8}});
 }
 
 // ====================================================================================================
@@ -4412,19 +4423,15 @@ extern "C" int sship_stereo_search_host(const uint8_t* left, int left_stride, co
 // ====================================================================================================
 // the checks both entries share; fills the kernel's constants
 static int track_check(int h, int w, int stride0, int stride1, const sship_patch_track_params* p, PatchTrackK* c, const char* who) {
-  if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, std::string(who) + ": h and w must be in [1, 16384]");
+  if (int rc = size_check(h, w, who)) return rc;
   if (stride0 < w || stride1 < w) return fail(SSHIP_ERR_INVALID, std::string(who) + ": stride (bytes) must be >= w");
   if (p->half_window < 1 || p->half_window > 7) return fail(SSHIP_ERR_INVALID, std::string(who) + ": half_window must be in [1, 7]");
   if (p->search_radius < 1 || p->search_radius > 16) return fail(SSHIP_ERR_INVALID, std::string(who) + ": search_radius must be in [1, 16]");
   if (p->uniqueness < 0 || p->uniqueness > 99) return fail(SSHIP_ERR_INVALID, std::string(who) + ": uniqueness must be in [0, 99]");
   if (p->fb_check < -1 || p->fb_check > 16) return fail(SSHIP_ERR_INVALID, std::string(who) + ": fb_check must be in [-1, 16]");
   if (std::isnan(p->min_texture) || std::isnan(p->max_rms)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": min_texture and max_rms must not be NaN");
-  const int pw = 2 * p->half_window + 1;
-  const double tt = (double)p->min_texture * (double)(pw * pw), tr = (double)p->max_rms * (double)(pw * pw);
-  c->tex = p->min_texture > 0.f ? 1 : 0;
-  c->tex2 = tt * tt;
-  c->gate = p->max_rms > 0.f ? 1 : 0;
-  c->gate2 = tr * tr;
+  patch_threshold(p->min_texture, 2 * p->half_window + 1, &c->tex, &c->tex2);
+  patch_threshold(p->max_rms, 2 * p->half_window + 1, &c->gate, &c->gate2);
   c->half_window = p->half_window; c->radius = p->search_radius; c->uniqueness = p->uniqueness; c->fb = p->fb_check;
   return SSHIP_OK;
 }
@@ -4461,29 +4468,19 @@ extern "C" int sship_patch_track_host(const uint8_t* img0, int stride0, const ui
   if (!keypoints || !kp_out || !matches0) return fail(SSHIP_ERR_INVALID, "patch_track_host: null argument");
   bind_thread();
   if (int rc = require_device()) return rc;
-  // (x, y, score) rows: the score is the third float of a keypoint where kp_stride >= 3, else 0; its bits are handed on
-  std::vector<float> kp((size_t)n * 3, 0.f), pr(pred ? (size_t)n * 3 : 0, 0.f);
-  for (int i = 0; i < n; ++i) memcpy(&kp[3 * (size_t)i], keypoints + (size_t)i * kp_stride, (kp_stride >= 3 ? 3 : 2) * sizeof(float));
-  for (int i = 0; pred && i < n; ++i) memcpy(&pr[3 * (size_t)i], pred + (size_t)i * pred_stride, 2 * sizeof(float));
-  const size_t img = (size_t)h * w, kb = (size_t)n * 3 * sizeof(float);
-  StageLayout lay;   // one device block for the call: the two images packed to stride w, then the per-keypoint arrays
-  const size_t o_i0 = lay.add(2 * img), o_i1 = o_i0 + img, o_n = lay.add(sizeof(int)), o_kp = lay.add(kb), o_pr = lay.add(kb), o_out = lay.add(kb),
-               o_m = lay.add((size_t)n * sizeof(int32_t)), o_status = lay.add((size_t)n), o_cost = lay.add((size_t)n * sizeof(int64_t));
+  const PairStage st = pair_stage(h, w, n);
+  const size_t m = (size_t)n;
+  std::vector<char> tail(st.tail_bytes, 0);
+  pair_pack_n(tail.data(), n);
+  pair_pack_kp(tail.data(), st, keypoints, kp_stride, n, true);
+  if (pred) pair_pack_pred(tail.data(), st, pred, pred_stride, n);
   StageArena a;
-  SSHIP_HIP_CHECK(a.create(lay.end, 0, false));
-  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_i0), (size_t)w, img0, (size_t)stride0, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_i1), (size_t)w, img1, (size_t)stride1, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(a.dev<int>(o_n), &n, sizeof(int), hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(a.dev<float>(o_kp), kp.data(), kb, hipMemcpyHostToDevice));
-  if (pred) { SSHIP_HIP_CHECK(hipMemcpy(a.dev<float>(o_pr), pr.data(), kb, hipMemcpyHostToDevice)); }
-  if (int rc = sship_patch_track_batch_device(a.dev<uint8_t>(o_i0), 0, w, a.dev<uint8_t>(o_i1), 0, w, 1, h, w, a.dev<float>(o_kp), a.dev<int>(o_n), 1,
-                                              pred ? a.dev<float>(o_pr) : nullptr, n, p, a.dev<float>(o_out), nullptr, a.dev<int32_t>(o_m),
-                                              a.dev<uint8_t>(o_status), a.dev<int64_t>(o_cost), nullptr)) return rc;
-  SSHIP_HIP_CHECK(hipMemcpy(kp_out, a.dev<float>(o_out), kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launch
-  SSHIP_HIP_CHECK(hipMemcpy(matches0, a.dev<int32_t>(o_m), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (status) { SSHIP_HIP_CHECK(hipMemcpy(status, a.dev<uint8_t>(o_status), (size_t)n, hipMemcpyDeviceToHost)); }
-  if (cost) { SSHIP_HIP_CHECK(hipMemcpy(cost, a.dev<int64_t>(o_cost), (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost)); }
-  return SSHIP_OK;
+  if (int rc = pair_upload(a, st, img0, stride0, img1, stride1, h, w, tail)) return rc;
+  if (int rc = sship_patch_track_batch_device(a.dev<uint8_t>(st.img), 0, w, a.dev<uint8_t>(st.img1), 0, w, 1, h, w, a.dev<float>(st.kp), a.dev<int>(st.n),
+                                              1, pred ? a.dev<float>(st.pred) : nullptr, n, p, a.dev<float>(a.out + st.rows), nullptr,
+                                              a.dev<int32_t>(a.out + st.flag), a.dev<uint8_t>(a.out + st.status), a.dev<int64_t>(a.out + st.cost),
+                                              nullptr)) return rc;
+  return pair_fetch(a, {{kp_out, st.rows, st.rows_bytes}, {matches0, st.flag, m * 4}, {status, st.status, m}, {cost, st.cost, m * 8}});
 }
 
 // ====================================================================================================
@@ -4663,7 +4660,7 @@ extern "C" int sship_patch_track_pyramid_host(const uint8_t* img0, int stride0, 
   if (!img0 || !img1 || !p) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
   if (n < 0 || n > kMaxKp || kp_stride < 2 || (pred && pred_stride < 2))
     return fail(SSHIP_ERR_INVALID, std::string(who) + ": n must be in [0, 4096], kp_stride >= 2 and, with pred, pred_stride >= 2");
-  if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, std::string(who) + ": h and w must be in [1, 16384]");
+  if (int rc = size_check(h, w, who)) return rc;
   if (stride0 < w || stride1 < w) return fail(SSHIP_ERR_INVALID, std::string(who) + ": stride (bytes) must be >= w");
   PyrTrackK c;
   if (int rc = pyr_track_check(h, w, p, &c, who)) return rc;
@@ -4671,34 +4668,24 @@ extern "C" int sship_patch_track_pyramid_host(const uint8_t* img0, int stride0, 
   if (!keypoints || !kp_out || !matches0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
   bind_thread();
   if (int rc = require_device()) return rc;
-  std::vector<float> kp((size_t)n * 3, 0.f), pr(pred ? (size_t)n * 3 : 0, 0.f);
-  for (int i = 0; i < n; ++i) memcpy(&kp[3 * (size_t)i], keypoints + (size_t)i * kp_stride, (kp_stride >= 3 ? 3 : 2) * sizeof(float));
-  for (int i = 0; pred && i < n; ++i) memcpy(&pr[3 * (size_t)i], pred + (size_t)i * pred_stride, 2 * sizeof(float));
-  const size_t img = (size_t)h * w, kb = (size_t)n * 3 * sizeof(float);
-  StageLayout lay;   // one device block for the call: the two images packed to stride w (a two-image pyramid reads them), then the per-keypoint arrays
-  const size_t o_i0 = lay.add(2 * img), o_n = lay.add(sizeof(int)), o_kp = lay.add(kb), o_pr = lay.add(kb), o_out = lay.add(kb),
-               o_m = lay.add((size_t)n * sizeof(int32_t)), o_status = lay.add((size_t)n), o_cost = lay.add((size_t)n * sizeof(int64_t)),
-               o_lv = lay.add((size_t)n);
+  const PairStage st = pair_stage(h, w, n);
+  const size_t m = (size_t)n;
+  std::vector<char> tail(st.tail_bytes, 0);
+  pair_pack_n(tail.data(), n);
+  pair_pack_kp(tail.data(), st, keypoints, kp_stride, n, true);
+  if (pred) pair_pack_pred(tail.data(), st, pred, pred_stride, n);
   StageArena a;
-  SSHIP_HIP_CHECK(a.create(lay.end, 0, false));
-  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_i0), (size_t)w, img0, (size_t)stride0, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(o_i0) + img, (size_t)w, img1, (size_t)stride1, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(a.dev<int>(o_n), &n, sizeof(int), hipMemcpyHostToDevice));
-  SSHIP_HIP_CHECK(hipMemcpy(a.dev<float>(o_kp), kp.data(), kb, hipMemcpyHostToDevice));
-  if (pred) { SSHIP_HIP_CHECK(hipMemcpy(a.dev<float>(o_pr), pr.data(), kb, hipMemcpyHostToDevice)); }
-  sship_pyr* raw = nullptr;
+  if (int rc = pair_upload(a, st, img0, stride0, img1, stride1, h, w, tail)) return rc;
+  sship_pyr* raw = nullptr;   // a two-image pyramid reads the staged pair
   if (int rc = sship_pyr_create(h, w, p->levels, 2, &raw)) return rc;
   std::unique_ptr<sship_pyr, void (*)(sship_pyr*)> pyr(raw, sship_pyr_destroy);
-  if (int rc = sship_pyr_build_batch_device(raw, a.dev<uint8_t>(o_i0), (long long)img, w, 2, nullptr)) return rc;
-  if (int rc = sship_patch_track_pyramid_batch_device(raw, 0, 1, raw, 1, 1, 1, a.dev<float>(o_kp), a.dev<int>(o_n), 1, pred ? a.dev<float>(o_pr) : nullptr, n,
-                                                      p, a.dev<float>(o_out), nullptr, a.dev<int32_t>(o_m), a.dev<uint8_t>(o_status),
-                                                      a.dev<int64_t>(o_cost), a.dev<uint8_t>(o_lv), nullptr)) return rc;
-  SSHIP_HIP_CHECK(hipMemcpy(kp_out, a.dev<float>(o_out), kb, hipMemcpyDeviceToHost));   // a blocking copy on the NULL stream: ordered after the launches
-  SSHIP_HIP_CHECK(hipMemcpy(matches0, a.dev<int32_t>(o_m), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
-  if (status) { SSHIP_HIP_CHECK(hipMemcpy(status, a.dev<uint8_t>(o_status), (size_t)n, hipMemcpyDeviceToHost)); }
-  if (cost) { SSHIP_HIP_CHECK(hipMemcpy(cost, a.dev<int64_t>(o_cost), (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost)); }
-  if (levels_tracked) { SSHIP_HIP_CHECK(hipMemcpy(levels_tracked, a.dev<uint8_t>(o_lv), (size_t)n, hipMemcpyDeviceToHost)); }
-  return SSHIP_OK;
+  if (int rc = sship_pyr_build_batch_device(raw, a.dev<uint8_t>(st.img), (long long)(st.img1 - st.img), w, 2, nullptr)) return rc;
+  if (int rc = sship_patch_track_pyramid_batch_device(raw, 0, 1, raw, 1, 1, 1, a.dev<float>(st.kp), a.dev<int>(st.n), 1,
+                                                      pred ? a.dev<float>(st.pred) : nullptr, n, p, a.dev<float>(a.out + st.rows), nullptr,
+                                                      a.dev<int32_t>(a.out + st.flag), a.dev<uint8_t>(a.out + st.status),
+                                                      a.dev<int64_t>(a.out + st.cost), a.dev<uint8_t>(a.out + st.levels), nullptr)) return rc;
+  return pair_fetch(a, {{kp_out, st.rows, st.rows_bytes}, {matches0, st.flag, m * 4}, {status, st.status, m}, {cost, st.cost, m * 8},
+                        {levels_tracked, st.levels, m}});
 }
 
 // ====================================================================================================

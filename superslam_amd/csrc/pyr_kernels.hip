@@ -1,8 +1,8 @@
 // Image pyramid and coarse-to-fine patch tracking (include/sship.h "Image pyramid" and "Coarse-to-fine patch tracking").
 //   k_pyr_down<ALIGNED>  one reduction (5 x 5 binomial, reflect-101 borders, every second pixel): a 256-thread workgroup owns a 64 x 16
 //                        output tile of one image, one launch per level for the whole batch.
-//   k_pyr_track          the patch search of patch_track_kernels.hip walked down the levels by the wave that owns the keypoint: one wave
-//                        per keypoint, 3 keypoints per 192-thread workgroup, one launch for the whole call.
+//   k_pyr_track          the 2-D patch search (patch_search.h) walked down the levels by the wave that owns the keypoint: one wave per
+//                        keypoint, 3 keypoints per 192-thread workgroup, one launch for the whole call.
 //
 // k_pyr_down stages the 35 rows x 136 bytes of the source that its tile needs (source columns 128 tx - 4 .. 128 tx + 131, rows 32 ty - 2 ..
 // 32 ty + 32, every index through reflect-101, so no load leaves the image) as dwords in LDS: with byte loads where nothing is known about
@@ -13,20 +13,26 @@
 // meet - and a thread stores the four pixels of its dword whole into the padded row (bytes past the level's width are zero).  9 240 B of
 // static LDS, no scratch.
 //
-// k_pyr_track keeps k_patch_track's per-keypoint body (its LDS slot, its scan on packed bytes, its butterflies; see that file) as one
-// device function and calls it once per level, from the top down.  Keypoints are independent, so the prediction a level hands to the next
+// k_pyr_track calls the per-keypoint body that k_patch_track runs once (patch_search.h's track_level: its LDS slot, its scan on packed
+// bytes, its butterflies) once per level, from the top down.  Keypoints are independent, so the prediction a level hands to the next
 // one lives in the wave's registers; nothing but the call's outputs reaches memory.  The per-level pointers, strides and sizes arrive by
 // value.  The slot is sized on the host for max(fine.search_radius, coarse_radius); a level lays its own (smaller or equal) layout over it.
 #include <hip/hip_runtime.h>
 
-#include <climits>
 #include <cstdint>
 
 #include "kernels.h"
+#include "patch_search.h"
 
 namespace sship {
 
+using namespace patch_search;
+using namespace patch_search::search2d;
+
 namespace {
+constexpr int kLanes = kWave;                          // the tracker's lanes per keypoint: one wave
+constexpr int kSlots = 3;                              // its keypoints per workgroup: 3 x 20 496 B = 61 488 B at half_window 7, radius 16
+
 // ------------------------------------------------------------------------------------------------------
 // the reduction
 // ------------------------------------------------------------------------------------------------------
@@ -103,222 +109,8 @@ void launch_pyr_down(const uint8_t* src, long long src_image_stride, long long s
 }
 
 // ------------------------------------------------------------------------------------------------------
-// the tracker: k_patch_track's helpers and per-keypoint body (patch_track_kernels.hip explains them), the body as a function of one level
+// the tracker
 // ------------------------------------------------------------------------------------------------------
-namespace {
-constexpr int kLanes = kWave;                          // lanes per keypoint: one wave
-constexpr int kSlots = 3;                              // keypoints per workgroup: 3 x 20 496 B = 61 488 B at half_window 7, radius 16
-enum { kNone = 0, kTracked = 1, kBorder = 2, kRange = 3, kTexture = 4, kEdge = 5, kCost = 6, kAmbiguous = 7, kFbCheck = 8 };
-constexpr uint32_t kQuietNan = 0x7fc00000u;
-
-__host__ __device__ inline int round16(int v) { return (v + 15) & ~15; }
-struct SlotLayout { int patch, region, hq, hs, bytes; };
-__host__ __device__ inline SlotLayout slot_layout(int hw, int radius) {
-  const int pw = 2 * hw + 1, nd = (pw + 3) / 4, nb = 2 * radius + 1, rw = nb + pw - 1;
-  SlotLayout l;
-  l.patch = round16(8 * nb * nb);
-  l.region = l.patch + round16(pw * 4 * nd);
-  l.hq = l.region + round16(rw * rw + 8);
-  l.hs = l.hq + round16(4 * rw * nb);
-  l.bytes = l.hs + round16(2 * rw * nb);
-  return l;
-}
-
-__device__ inline bool coord_ok(float x) { return x >= 0.f && x < 16384.f; }   // NaN and +-inf: false
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ void wave_argmin(long long& best, int& bk) {
-#pragma unroll
-  for (int m = kLanes / 2; m >= 1; m >>= 1) {
-    const long long oc = __shfl_xor(best, m, kLanes);
-    const int ok = __shfl_xor(bk, m, kLanes);
-    if (oc < best || (oc == best && ok < bk)) { best = oc; bk = ok; }
-  }
-}
-
-struct ScanIn { const uint8_t* patch; const uint8_t* region; const uint32_t* hq; const uint16_t* hs; int pw, rw, ncx, a1, a2; };
-
-template <int ND>
-__device__ __forceinline__ void scan_candidates(const ScanIn& in, int nc, int base_x, int base_y, int step, int t, long long* cost, long long& best,
-                                                int& bk) {
-  const int pw = in.pw, rw = in.rw, ncx = in.ncx;
-  const long long N = pw * pw;
-  best = LLONG_MAX; bk = INT_MAX;
-  for (int k = t; k < nc; k += kLanes) {
-    const int ky = k / ncx, kx = k - ky * ncx;
-    const int col = base_x + step * kx, row = base_y + step * ky;
-    int r1 = 0, r2 = 0;
-    uint32_t cross = 0;
-    for (int r = 0; r < pw; ++r) {
-      r1 += in.hs[(row + r) * ncx + col]; r2 += (int)in.hq[(row + r) * ncx + col];
-      const int o = (row + r) * rw + col;
-      const uint32_t* p = reinterpret_cast<const uint32_t*>(in.region + (o & ~3));
-      const uint32_t* a = reinterpret_cast<const uint32_t*>(in.patch + r * 4 * ND);
-      const uint32_t sh = (uint32_t)o & 3u;
-      uint32_t w0 = p[0];
-#pragma unroll
-      for (int q = 0; q < ND; ++q) {
-        const uint32_t w1 = p[q + 1];
-        cross = __builtin_amdgcn_udot4(a[q], __builtin_amdgcn_alignbyte(w1, w0, sh), cross, false);
-        w0 = w1;
-      }
-    }
-    const int s1 = in.a1 - r1, s2 = in.a2 + r2 - 2 * (int)cross;
-    const long long c = N * s2 - (long long)s1 * s1;
-    if (cost) cost[k] = c;
-    if (c < best) { best = c; bk = k; }
-  }
-}
-__device__ __forceinline__ void scan_candidates(const ScanIn& in, int nc, int base_x, int base_y, int step, int t, long long* cost, long long& best,
-                                                int& bk) {
-  switch ((in.pw + 3) / 4) {
-    case 1: scan_candidates<1>(in, nc, base_x, base_y, step, t, cost, best, bk); break;
-    case 2: scan_candidates<2>(in, nc, base_x, base_y, step, t, cost, best, bk); break;
-    case 3: scan_candidates<3>(in, nc, base_x, base_y, step, t, cost, best, bk); break;
-    default: scan_candidates<4>(in, nc, base_x, base_y, step, t, cost, best, bk); break;
-  }
-}
-
-__device__ __forceinline__ void patch_sums(const uint8_t* patch, int bytes, int t, int& a1, int& a2) {
-  a1 = 0; a2 = 0;
-  for (int k = t; k < bytes; k += kLanes) { const int a = patch[k]; a1 += a; a2 += a * a; }
-#pragma unroll
-  for (int m = kLanes / 2; m >= 1; m >>= 1) { a1 += __shfl_xor(a1, m, kLanes); a2 += __shfl_xor(a2, m, kLanes); }
-}
-
-__device__ __forceinline__ void row_sums(const uint8_t* region, int pw, int rw, int rh, int ncx, int t, uint32_t* hq, uint16_t* hs) {
-  for (int k = t; k < rh * ncx; k += kLanes) {
-    const int r = k / ncx, cc = k - r * ncx;
-    const uint8_t* p = region + r * rw + cc;
-    int s1 = 0, s2 = 0;
-    for (int q = 0; q < pw; ++q) { const int v = p[q]; s1 += v; s2 += v * v; }
-    hs[k] = (uint16_t)s1; hq[k] = (uint32_t)s2;
-  }
-}
-
-__device__ __forceinline__ void stage_region(const uint8_t* __restrict__ src, long long stride, uint8_t* dst, int rh, int rw, int t) {
-  for (int k = t; k < rh * rw; k += kLanes) {
-    const int r = k / rw, cc = k - r * rw;
-    dst[k] = src[r * stride + cc];
-  }
-}
-__device__ __forceinline__ void stage_patch(const uint8_t* __restrict__ src, long long stride, uint8_t* dst, int pw, int pitch, int t) {
-  for (int k = t; k < pw * pitch; k += kLanes) {
-    const int r = k / pitch, cc = k % pitch;
-    dst[k] = cc < pw ? src[r * stride + cc] : (uint8_t)0;
-  }
-}
-
-struct LevelOut { int status; long long cost; uint32_t x, y; };   // x, y: the bits of (x', y'), quiet NaNs unless the status is TRACKED
-
-// steps 2 to 10 of the patch-tracking rule for one keypoint inside the count, on the images (i0, i1) of h x w pixels, by one wave.  Every
-// lane returns the same values.  The template is read only after step 2 found it inside I0, the region only after step 3 found a box of at
-// least 3 x 3 candidates whose patches lie inside I1: no load leaves an image.
-__device__ __forceinline__ LevelOut track_level(const uint8_t* __restrict__ i0p, long long stride0, const uint8_t* __restrict__ i1p, long long stride1,
-                                                int h, int w, float x, float y, float px, float py, const PatchTrackK& c, uint8_t* slot, int t) {
-  const int hw = c.half_window, R = c.radius, pw = 2 * hw + 1;
-  const SlotLayout lay = slot_layout(hw, R);
-  long long* costs = reinterpret_cast<long long*>(slot);
-  uint8_t* patch = slot + lay.patch;
-  uint8_t* region = slot + lay.region;
-  uint32_t* hq = reinterpret_cast<uint32_t*>(slot + lay.hq);
-  uint16_t* hs = reinterpret_cast<uint16_t*>(slot + lay.hs);
-  const int pitch = 4 * ((pw + 3) / 4);
-  ScanIn in{patch, region, hq, hs, pw, 0, 0, 0, 0};
-  LevelOut o{kBorder, -1, kQuietNan, kQuietNan};
-  int xa = 0, ya = 0, xp = 0, yp = 0, lox = 0, loy = 0, ncx = 0, ncy = 0;
-  wave_sync();                                          // the level above read its costs: this level's staging lies over them
-  if (coord_ok(x) && coord_ok(y) && coord_ok(px) && coord_ok(py)) {
-    xa = (int)floor((double)x + 0.5); ya = (int)floor((double)y + 0.5);
-    xp = (int)floor((double)px + 0.5); yp = (int)floor((double)py + 0.5);
-    if (xa - hw >= 0 && xa + hw < w && ya - hw >= 0 && ya + hw < h) {
-      lox = max(-R, hw - xp); loy = max(-R, hw - yp);
-      ncx = min(R, w - 1 - hw - xp) - lox + 1; ncy = min(R, h - 1 - hw - yp) - loy + 1;
-      o.status = (ncx < 3 || ncy < 3) ? kRange : kTracked;
-    }
-  }
-  if (o.status == kTracked) {
-    const uint8_t* i0 = i0p + (size_t)(ya - hw) * stride0 + (xa - hw);
-    const uint8_t* i1 = i1p + (size_t)(yp + loy - hw) * stride1 + (xp + lox - hw);
-    stage_patch(i0, stride0, patch, pw, pitch, t);
-    stage_region(i1, stride1, region, ncy + pw - 1, ncx + pw - 1, t);
-    wave_sync();
-    patch_sums(patch, pw * pitch, t, in.a1, in.a2);
-    if (c.tex) {
-      const long long T = (long long)(pw * pw) * in.a2 - (long long)in.a1 * in.a1;
-      if ((double)T < c.tex2) o.status = kTexture;
-    }
-  }
-  if (o.status != kTracked) return o;
-  const int rw = ncx + pw - 1, rh = ncy + pw - 1, nc = ncx * ncy;
-  long long best; int ks;
-  row_sums(region, pw, rw, rh, ncx, t, hq, hs);
-  wave_sync();
-  in.rw = rw; in.ncx = ncx;
-  scan_candidates(in, nc, 0, 0, 1, t, costs, best, ks);
-  wave_argmin(best, ks);
-  const long long cost = best;
-  o.cost = cost;
-  wave_sync();
-  const int kys = ks / ncx, kxs = ks - kys * ncx;
-  const int dxs = lox + kxs, dys = loy + kys;
-  if (kxs == 0 || kxs == ncx - 1 || kys == 0 || kys == ncy - 1) o.status = kEdge;
-  else if (c.gate && (double)cost > c.gate2) o.status = kCost;
-  else if (c.uniqueness > 0) {
-    long long c2 = LLONG_MAX;
-    for (int k = t; k < nc; k += kLanes) {
-      const int ky = k / ncx, kx = k - ky * ncx;
-      if (abs(kx - kxs) > 1 || abs(ky - kys) > 1) c2 = min(c2, costs[k]);
-    }
-#pragma unroll
-    for (int m = kLanes / 2; m >= 1; m >>= 1) c2 = min(c2, (long long)__shfl_xor(c2, m, kLanes));
-    if (c2 != LLONG_MAX && !(100 * cost < (long long)(100 - c.uniqueness) * c2)) o.status = kAmbiguous;
-  }
-  if (o.status == kTracked && c.fb >= 0) {
-    const int cx = xa + dxs, cy = ya + dys;
-    const int elox = max(-R, cx - (w - 1 - hw)), ehix = min(R, cx - hw), eloy = max(-R, cy - (h - 1 - hw)), ehiy = min(R, cy - hw);
-    const int nbx = ehix - elox + 1, nby = ehiy - eloy + 1, rw2 = nbx + pw - 1, rh2 = nby + pw - 1;
-    uint8_t keep[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int k = t + q * kLanes;
-      keep[q] = k < pw * pw ? region[(kys + k / pw) * rw + kxs + k % pw] : 0;
-    }
-    wave_sync();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int k = t + q * kLanes;
-      if (k < pw * pw) patch[(k / pw) * pitch + k % pw] = keep[q];
-    }
-    const uint8_t* i0 = i0p + (size_t)(cy - ehiy - hw) * stride0 + (cx - ehix - hw);
-    stage_region(i0, stride0, region, rh2, rw2, t);
-    wave_sync();
-    patch_sums(patch, pw * pitch, t, in.a1, in.a2);
-    row_sums(region, pw, rw2, rh2, nbx, t, hq, hs);
-    wave_sync();
-    in.rw = rw2; in.ncx = nbx;
-    long long b; int es;
-    scan_candidates(in, nbx * nby, nbx - 1, nby - 1, -1, t, nullptr, b, es);
-    wave_argmin(b, es);
-    const int eys = es / nbx, exs = es - eys * nbx;
-    if (abs(elox + exs - dxs) > c.fb || abs(eloy + eys - dys) > c.fb) o.status = kFbCheck;
-  }
-  if (o.status == kTracked) {
-    const long long cmx = costs[ks - 1], cpx = costs[ks + 1], cmy = costs[ks - ncx], cpy = costs[ks + ncx];
-    const long long denx = cmx + cpx - 2 * cost, deny = cmy + cpy - 2 * cost;
-    const double deltax = (double)(cmx - cpx) / (double)(2 * denx), deltay = (double)(cmy - cpy) / (double)(2 * deny);
-    o.x = __float_as_uint((float)(((double)x + (double)(xp - xa + dxs)) + deltax));
-    o.y = __float_as_uint((float)(((double)y + (double)(yp - ya + dys)) + deltay));
-  }
-  return o;
-}
-}  // namespace
-
 // pred and kp_out may be the same array: a wave reads its row of pred before lane 0 writes that row of kp_out, and no other wave touches it
 __global__ __launch_bounds__(kLanes * kSlots) void k_pyr_track(PyrTrackLevels tab, const uint32_t* kp, const int* __restrict__ lens, int unit_stride,
                                                               const uint32_t* pred, int K, PyrTrackK c, uint32_t* kp_out, int* n_out,
@@ -349,6 +141,7 @@ __global__ __launch_bounds__(kLanes * kSlots) void k_pyr_track(PyrTrackLevels ta
       const PyrTrackLevel& L = tab.l[l];
       const double sl = 1.0 / (double)(1 << l);
       const float xl = (float)((double)x * sl), yl = (float)((double)y * sl);
+      wave_sync();                                      // the level above read its costs: this level's staging lies over them
       const LevelOut o = track_level(L.img0 + (size_t)pair * L.pair_stride0, L.stride0, L.img1 + (size_t)pair * L.pair_stride1, L.stride1, L.h, L.w,
                                      xl, yl, px, py, l ? coarse : c.fine, slot, t);
       if (o.status == kTracked) mask |= 1 << l;

@@ -1,5 +1,6 @@
-// Staging layouts of the single-item entries (sship_*_solve_host, sship_nn_match_*, sship_index_query_*): where each field of one staged
-// item lies in the handle's arena, and the host-side pack / unpack of that block.  Plain C++17, no HIP: api.hip includes it, and
+// Staging layouts of the single-item entries (sship_*_solve_host, sship_nn_match_*, sship_index_query_*, and the image-pair entries
+// sship_stereo_refine_host, sship_stereo_search_host, sship_patch_track_host, sship_patch_track_pyramid_host): where each field of one staged
+// item lies in the handle's (or, for an image pair, the call's) arena, and the host-side pack / unpack of that block.  Plain C++17, no HIP: api.hip includes it, and
 // tests/cpp/test_stage_layout.cc builds it alone (also under the host sanitizers).  A block has an input region and an output region; each
 // is contiguous, so one copy covers it, and every slot starts on a multiple of kStageAlign (what a hipMalloc of its own would give).
 // Offsets of the output slots count from the start of the output region.
@@ -175,6 +176,42 @@ inline int index_unpack(const char* out, const IndexStage& st, int top_k, const 
   }
   *count_out = n;
   return 0;
+}
+
+// ---- one image pair and its keypoints (stereo refinement and search, patch and pyramid tracker):
+//      img [2][h][w] | n | kp [n][3] | pred [n][3] -> rows [n][3] | flag [n] | status [n] | cost [n] i64 | levels [n] ---------------------------
+// The images are packed to stride w, the second right behind the first (`img1`).  They are copied straight from the caller's strided
+// memory, so the host block that the packs fill mirrors the input region from `n` on only (`tail_bytes` of it): pass its start as `tail`.
+// `flag` holds matches0 (i32) for the trackers and has_depth (u8) for the stereo entries; the stereo refinement works in place on `rows`
+// and `flag` and leaves `kp` and `pred` alone, as the stereo search does `pred`, and only the pyramid tracker writes `levels`.
+struct PairStage { size_t img, img1, n, kp, pred, in_bytes, tail_bytes, rows, flag, status, cost, levels, out_bytes, rows_bytes; };
+inline PairStage pair_stage(int h, int w, int n) {
+  const size_t px = (size_t)h * w, m = (size_t)n;
+  StageLayout in, out;
+  PairStage s;
+  s.rows_bytes = m * 12;
+  s.img = in.add(2 * px); s.img1 = s.img + px; s.n = in.add(4); s.kp = in.add(s.rows_bytes); s.pred = in.add(s.rows_bytes); s.in_bytes = in.end;
+  s.tail_bytes = s.in_bytes - s.n;
+  s.rows = out.add(s.rows_bytes); s.flag = out.add(m * 4); s.status = out.add(m); s.cost = out.add(m * 8); s.levels = out.add(m); s.out_bytes = out.end;
+  return s;
+}
+inline void pair_pack_n(char* tail, int n) {   // the tail starts with the count
+  const int32_t n32 = n;
+  memcpy(tail, &n32, 4);
+}
+// (x, y, third) rows out of the caller's strided ones: with `score`, the third float of a keypoint where kp_stride >= 3 (its bits are
+// handed on), else 0
+inline void pair_pack_kp(char* tail, const PairStage& st, const float* keypoints, int kp_stride, int n, bool score) {
+  char* rows = tail + (st.kp - st.n);
+  const size_t take = score && kp_stride >= 3 ? 12 : 8;
+  memset(rows, 0, st.rows_bytes);
+  for (int i = 0; i < n; ++i) memcpy(rows + (size_t)i * 12, keypoints + (size_t)i * kp_stride, take);
+}
+// (x, y, 0) rows out of pred_stride-strided ones
+inline void pair_pack_pred(char* tail, const PairStage& st, const float* pred, int pred_stride, int n) {
+  char* rows = tail + (st.pred - st.n);
+  memset(rows, 0, st.rows_bytes);
+  for (int i = 0; i < n; ++i) memcpy(rows + (size_t)i * 12, pred + (size_t)i * pred_stride, 8);
 }
 
 }  // namespace sship

@@ -14,6 +14,7 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "patch_search.h"
 
 namespace sship {
 
@@ -28,9 +29,8 @@ struct RefineSlot {
   uint8_t right[(kMaxPatch * kMaxStrip + 3) / 4 * 4];
 };
 enum { kNone = 0, kRefined = 1, kBorder = 2, kEdge = 3, kCost = 4, kDisparity = 5 };
-constexpr uint32_t kQuietNan = 0x7fc00000u;
-
-__device__ inline bool coord_ok(float x) { return x >= 0.f && x < 16384.f; }   // NaN and +-inf: false
+using patch_search::coord_ok;
+using patch_search::kQuietNan;
 }  // namespace
 
 __global__ __launch_bounds__(kLanes * kSlots) void k_stereo_refine(const uint8_t* __restrict__ imgs, int h, int w, long long stride,

@@ -22,16 +22,17 @@
 #include <cstdint>
 
 #include "kernels.h"
+#include "patch_search.h"
 
 namespace sship {
+
+using namespace patch_search;   // the family's helpers; the 1-D slot, scan and sums below are this kernel's own
 
 namespace {
 constexpr int kLanes = kWave;                          // lanes per keypoint: one wave
 constexpr int kSlots = 4;                              // keypoints per workgroup
 enum { kNone = 0, kFound = 1, kBorder = 2, kRange = 3, kTexture = 4, kEdge = 5, kCost = 6, kAmbiguous = 7, kLrCheck = 8 };
-constexpr uint32_t kQuietNan = 0x7fc00000u;
 
-__host__ __device__ inline int round16(int v) { return (v + 15) & ~15; }
 // one keypoint's slot, at the widest strip (every candidate inside the image): byte offsets of the costs (i64 per candidate), the patch
 // (rows padded with zeros to nd dwords), the strip (8 bytes of slack: the last window's aligned dwords end past it), the strip's column
 // sums of squares (u32) and column sums (u16)
@@ -45,25 +46,6 @@ __host__ __device__ inline SlotLayout slot_layout(int hw, int cand) {
   l.cols = l.colq + round16(4 * sw);
   l.bytes = l.cols + round16(2 * sw);
   return l;
-}
-
-__device__ inline bool coord_ok(float x) { return x >= 0.f && x < 16384.f; }   // NaN and +-inf: false
-
-// the lanes of one wave exchange data through LDS: order this wave's LDS traffic
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the smallest (C, k) over the wave, ties to the smaller k; every lane ends with the result
-__device__ __forceinline__ void wave_argmin(long long& best, int& bk) {
-#pragma unroll
-  for (int m = kLanes / 2; m >= 1; m >>= 1) {
-    const long long oc = __shfl_xor(best, m, kLanes);
-    const int ok = __shfl_xor(bk, m, kLanes);
-    if (oc < best || (oc == best && ok < bk)) { best = oc; bk = ok; }
-  }
 }
 
 // what a scan reads: the patch (rows of nd dwords), its sums, the strip (row pitch sw bytes) and its column sums
@@ -109,14 +91,6 @@ __device__ __forceinline__ void scan_candidates(const ScanIn& in, int nc, int ba
   }
 }
 
-// sum and sum of squares of the patch over the wave (the padding is zero); every lane ends with the result
-__device__ __forceinline__ void patch_sums(const uint8_t* patch, int bytes, int t, int& a1, int& a2) {
-  a1 = 0; a2 = 0;
-  for (int k = t; k < bytes; k += kLanes) { const int a = patch[k]; a1 += a; a2 += a * a; }
-#pragma unroll
-  for (int m = kLanes / 2; m >= 1; m >>= 1) { a1 += __shfl_xor(a1, m, kLanes); a2 += __shfl_xor(a2, m, kLanes); }
-}
-
 // per-column sums of the strip, a lane per column
 __device__ __forceinline__ void column_sums(const uint8_t* strip, int pw, int sw, int t, uint32_t* colq, uint16_t* cols) {
   for (int j = t; j < sw; j += kLanes) {
@@ -130,13 +104,6 @@ __device__ __forceinline__ void column_sums(const uint8_t* strip, int pw, int sw
 __device__ __forceinline__ void stage_rows(const uint8_t* __restrict__ src, long long stride, uint8_t* dst, int pw, int width, int t) {
   for (int r = 0; r < pw; ++r, src += stride, dst += width)
     for (int cc = t; cc < width; cc += kLanes) dst[cc] = src[cc];
-}
-// the patch: pw rows of pw bytes from src to rows of `pitch` >= pw bytes, the rest of a row zero
-__device__ __forceinline__ void stage_patch(const uint8_t* __restrict__ src, long long stride, uint8_t* dst, int pw, int pitch, int t) {
-  for (int k = t; k < pw * pitch; k += kLanes) {
-    const int r = k / pitch, cc = k % pitch;
-    dst[k] = cc < pw ? src[r * stride + cc] : (uint8_t)0;
-  }
 }
 }  // namespace
 

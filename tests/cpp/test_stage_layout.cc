@@ -258,6 +258,49 @@ static void index_case(int dim, int max_top_k) {
     }
 }
 
+// ---- one image pair and its keypoints -----------------------------------------------------------------------------------------------------
+static void pair_case(int h, int w, int n) {
+  const PairStage st = pair_stage(h, w, n);
+  const size_t px = (size_t)h * w, m = (size_t)n;
+  check_region({{st.img, 2 * px}, {st.n, 4}, {st.kp, m * 12}, {st.pred, m * 12}}, st.in_bytes);
+  CHECK(st.img1 == st.img + px);                        // [2][h][w]: the second image follows the first without a gap
+  CHECK(st.tail_bytes == st.in_bytes - st.n && st.rows_bytes == m * 12);
+  check_region({{st.rows, m * 12}, {st.flag, m * 4}, {st.status, m}, {st.cost, m * 8}, {st.levels, m}}, st.out_bytes);
+  const size_t o_kp = st.kp - st.n, o_pred = st.pred - st.n;   // in the tail, which starts at the count
+  const int32_t n32 = n;
+  for (int kp_stride : {2, 3, 5})
+    for (int score = 0; score < 2; ++score)
+      for (int pred_stride : {0, 2, 7}) {               // 0: no pred
+        // caller's arrays of exactly n strided rows (the last row ends with its stride: what the API documents)
+        const std::vector<float> kp = ramp<float>(m * kp_stride, 11 + kp_stride), pr = ramp<float>(m * pred_stride, 12 + pred_stride);
+        Block tail(st.tail_bytes, kFill);
+        pair_pack_n(tail.p, n);
+        pair_pack_kp(tail.p, st, kp.data(), kp_stride, n, score != 0);
+        if (pred_stride) pair_pack_pred(tail.p, st, pr.data(), pred_stride, n);
+        std::vector<unsigned char> want(st.tail_bytes, kFill);   // only the slots packed are written: whole, so nothing stale is uploaded from them
+        put(want, 0, &n32, 1);
+        for (int i = 0; i < n; ++i) {
+          const float row[3] = {kp[(size_t)i * kp_stride], kp[(size_t)i * kp_stride + 1], score && kp_stride >= 3 ? kp[(size_t)i * kp_stride + 2] : 0.f};
+          put(want, o_kp + (size_t)i * 12, row, 3);
+          if (pred_stride) {
+            const float prow[3] = {pr[(size_t)i * pred_stride], pr[(size_t)i * pred_stride + 1], 0.f};
+            put(want, o_pred + (size_t)i * 12, prow, 3);
+          }
+        }
+        CHECK(same(tail, want));
+      }
+  // the score travels as bits: a signalling-NaN pattern survives the pack
+  if (n > 0) {
+    const uint32_t bits[3] = {0x40000000u, 0x40400000u, 0x7fa00001u};
+    float row[3];
+    memcpy(row, bits, 12);
+    const PairStage one = pair_stage(h, w, 1);
+    Block t1(one.tail_bytes, kFill);
+    pair_pack_kp(t1.p, one, row, 3, 1, true);
+    CHECK(memcmp(t1.p + (one.kp - one.n), bits, 12) == 0);
+  }
+}
+
 int main() {
   StageLayout lay;
   CHECK(lay.add(1) == 0 && lay.end == 1 && lay.add(255) == 256 && lay.end == 511 && lay.add(0) == 512 && lay.end == 512 && lay.add(7) == 512);
@@ -266,6 +309,7 @@ int main() {
   for (auto c : {std::vector<int>{2, 0}, {3, 1}, {5, 3}, {4096, 128}}) pg_case(c[0], c[1]);
   for (int max_kp : {1, 33, 4096}) nn_case(max_kp);
   for (auto c : {std::vector<int>{4, 1}, {36, 3}, {4, 3}, {36, 1}, {4096, 128}}) index_case(c[0], c[1]);
+  for (auto c : {std::vector<int>{1, 1, 1}, {3, 5, 1}, {5, 5, 5}, {11, 21, 33}, {16384, 16384, 4096}}) pair_case(c[0], c[1], c[2]);
   if (g_fail) { printf("%d checks failed\n", g_fail); return 1; }
   printf("all checks passed (stage layout)\n");
   return 0;

@@ -394,13 +394,68 @@ def _stereo_case(which, n):
     return imgs, rows, prm
 
 
+def _track_case(which, n):
+    """the smallest images with a box of 3 x 3 candidates (5 x 5 at half_window 1, search_radius 1; for the pyramid 9 x 9, whose level 1 is
+    5 x 5), the second image the first one, so the centre keypoint is tracked and the backward search (fb_check = 0) runs; the other rows
+    end at the border and range statuses.  Keypoint rows (x, y, score, junk), predictions (x, y, junk, junk, junk)."""
+    _lib, _ = _api()
+    rng = np.random.default_rng(2)
+    side, c = (5, 2.0) if which == "track" else (9, 4.0)
+    img = rng.integers(0, 256, (side, side), dtype=np.uint8)
+    xy = np.array([(c, c), (c + 0.49, c - 0.49), (c - 1, c), (0, 0), (c + 1.4, c + 0.6)], np.float32)[:n]
+    kp = np.concatenate([xy, np.linspace(0.25, 0.75, n, dtype=np.float32)[:, None], np.full((n, 1), 9, np.float32)], 1)
+    pred = np.concatenate([xy + np.float32(0.2), np.full((n, 3), 7, np.float32)], 1)
+    fine = _lib.PatchTrackParams(half_window=1, search_radius=1, uniqueness=0, min_texture=0.0, max_rms=0.0, fb_check=0)
+    prm = fine if which == "track" else _lib.PyrTrackParams(fine=fine, levels=2, coarse_radius=1)
+    return np.stack([img, img]), kp, pred, prm
+
+
+def _track_host_and_batch(which, n, optional, with_pred):
+    """(host outputs, batch outputs) of one tracker kind, each (required bytes, optional bytes)"""
+    _lib, lib = _api()
+    import torch
+
+    imgs, kp, pred, prm = _track_case(which, n)
+    h, w = imgs.shape[1:]
+    i0, i1 = strided(imgs[0], w + 11, 255), strided(imgs[1], w + 3, 0)
+    out, m0 = np.zeros((n, 3), np.float32), np.zeros(n, np.int32)
+    opt = [np.zeros(n, np.uint8), np.zeros(n, np.int64)] + ([np.zeros(n, np.uint8)] if which == "pyramid" else []) if optional else None
+    host = lib.sship_patch_track_host if which == "track" else lib.sship_patch_track_pyramid_host
+    _lib.check(host(ptr(i0), w + 11, ptr(i1), w + 3, h, w, ptr(kp), 4, ptr(pred) if with_pred else None, 5, n, C.byref(prm), ptr(out), ptr(m0),
+                    *(ptr(a) for a in (opt or [None] * (3 if which == "pyramid" else 2)))))
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda")
+    dout, dm0, dstatus, dcost, dlv = z((n, 3), torch.float32), z(n, torch.int32), z(n, torch.uint8), z(n, torch.int64), z(n, torch.uint8)
+    dimg, dn, dkp = dev(imgs), dev(np.array([n], np.int32)), dev(kp[:, :3])
+    dpred = dev(np.concatenate([pred[:, :2], np.zeros((n, 1), np.float32)], 1)) if with_pred else None
+    if which == "track":
+        _lib.check(lib.sship_patch_track_batch_device(ptr(dimg[0]), 0, w, ptr(dimg[1]), 0, w, 1, h, w, ptr(dkp), ptr(dn), 1, ptr(dpred), n, C.byref(prm),
+                                                      ptr(dout), None, ptr(dm0), ptr(dstatus), ptr(dcost), None))
+        dopt = (dstatus, dcost)
+    else:
+        with Handle(lib.sship_pyr_create, lib.sship_pyr_destroy, h, w, 2, 2) as pyr:
+            _lib.check(lib.sship_pyr_build_batch_device(pyr, ptr(dimg), h * w, w, 2, None))
+            _lib.check(lib.sship_patch_track_pyramid_batch_device(pyr, 0, 1, pyr, 1, 1, 1, ptr(dkp), ptr(dn), 1, ptr(dpred), n, C.byref(prm), ptr(dout),
+                                                                  None, ptr(dm0), ptr(dstatus), ptr(dcost), ptr(dlv), None))
+            torch.cuda.synchronize()                                                         # before the handle goes
+        dopt = (dstatus, dcost, dlv)
+    assert int(dstatus[0]) == 1 and int(dm0[0]) == 0                                         # the centre keypoint is tracked
+    return (raw(out, m0), raw(*opt) if optional else None), (raw(dout, dm0), raw(*dopt))
+
+
 @pytest.mark.parametrize("optional", (True, False))
 @pytest.mark.parametrize("n", (1, 5))
-@pytest.mark.parametrize("which", ("refine", "search"))
+@pytest.mark.parametrize("which", ("refine", "search", "track", "pyramid"))
 def test_stereo_host_call_equals_the_batch_call(which, n, optional):
     _lib, lib = _api()
     import torch
 
+    if which in ("track", "pyramid"):
+        for with_pred in (False, True):
+            got, want = _track_host_and_batch(which, n, optional, with_pred)
+            assert got[0] == want[0], with_pred
+            if optional:
+                assert got[1] == want[1], with_pred
+        return
     imgs, rows, prm = _stereo_case(which, n)
     h, w = imgs.shape[1:]
     left, right = strided(imgs[0], w + 11, 255), strided(imgs[1], w + 3, 0)

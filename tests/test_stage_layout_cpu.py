@@ -3,6 +3,7 @@ unpack, as a stand-alone program (tests/cpp/test_stage_layout.cc), plain and und
 from __future__ import annotations
 
 import os
+import re
 import subprocess
 
 import pytest
@@ -40,3 +41,15 @@ def test_api_includes_the_header_and_keeps_no_offsets_of_its_own():
     for launch in ("launch_pose_solve(", "launch_ransac_solve(", "launch_ba_solve(", "launch_pg_solve(", "launch_index_query(", "launch_nn_match(",
                    "launch_nn_match_gated("):
         assert api.count(launch) == 1, launch
+    # the four image-pair entries stage through pair_stage: no offsets of their own
+    for entry in ("sship_stereo_refine_host", "sship_stereo_search_host", "sship_patch_track_host", "sship_patch_track_pyramid_host"):
+        start = api.index('extern "C" int %s(' % entry)
+        body = api[start:api.index("\n}\n", start)]
+        assert "pair_stage(" in body and "lay.add(" not in body and "StageLayout" not in body, entry
+    # the patch-search family's device helpers and the 2-D search body are defined once (definitions, not uses: a definition's line
+    # carries __device__), whichever kernel files use them
+    csrc = os.path.join(ROOT, "superslam_amd", "csrc")
+    text = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h")))
+    for name in (r"wave_argmin\(", r"stage_patch\(", r"patch_sums\(", r"coord_ok\(", r"slot_layout\(int hw, int radius\)", r"track_level\("):
+        found = re.findall(r"^[^\n;]*__device__[^\n;]*\b" + name, text, re.M)
+        assert len(found) == 1, (name, found)
