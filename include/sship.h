@@ -1549,6 +1549,77 @@ int sship_clahe_bench(sship_clahe* clahe, int iters, float* avg_ms);
 int sship_clahe_bench_kernels(sship_clahe* clahe, int kernels, int iters, float* avg_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * FAST corners - a corner detector with track refill on the device: the one stage of the no-network chain that CREATES keypoints
+ * (detect -> patch tracker -> stereo search -> RANSAC -> pose needs no checkpoint with it), and the classical baseline of the extractor.
+ * VINS-Fusion and OpenVINS re-detect corners outside a mask around their live tracks and append them to the track list; this does the
+ * same without leaving the device.  The rule is modelled on FAST-9/16 (Rosten and Drummond) as OpenCV's cv::FAST implements it.
+ * Equality with OpenCV is NOT claimed: points 2 and 3 differ from it on purpose.  Everything is integer arithmetic on u8 pixels and
+ * comparison of distinct 64-bit keys: the kernels equal the numpy restatement (tests/_fast_ref.py) bit for bit.
+ * The rule.  Image I is u8, h x W; parameters t = threshold in [0, 254], b = border in [3, 64], d = min_distance in [0, 32].
+ *   1. Score.  Ring offsets (dx, dy), k = 0..15, clockwise from the top: (0,-3) (1,-3) (2,-2) (3,-1) (3,0) (3,1) (2,2) (1,3) (0,3) (-1,3)
+ *      (-2,2) (-3,1) (-3,0) (-3,-1) (-2,-2) (-1,-3).  For 3 <= x < W-3 and 3 <= y < h-3: e_k = I[y+dy_k, x+dx_k] - I[y, x] (int32),
+ *      bright = max over a in 0..15 of min over j in 0..8 of e_{(a+j) mod 16}, dark the same with -e, s(x, y) = max(bright, dark, 0);
+ *      elsewhere s = 0.  s lies in 0..255 and is the largest t' such that 9 contiguous ring pixels all differ from the centre by at
+ *      least t' in one direction: OpenCV's score plus one.
+ *   2. Corner and non-maximum suppression.  A pixel is a candidate iff s > t, it lies inside the border (b <= x < W-b, b <= y < h-b) and
+ *      the triple (s, y, x) is lexicographically greater than (s_q, y_q, x_q) of each of its 8 neighbours q: a plateau keeps its last
+ *      pixel in raster order.  (OpenCV's strict > drops whole plateaus: a clean synthetic step corner has three equal scores in a row,
+ *      and OpenCV returns nothing for it.)  This is the order the selection sorts by.  Two candidates are never 8-neighbours, so an
+ *      image has at most ceil(h/2) * ceil(W/2) candidates; the handle sizes its candidate list to that bound, the list cannot
+ *      overflow, and the result therefore cannot depend on the order the slot-reservation atomics resolve in.
+ *   3. Mask.  keep is [units, max_keypoints, 3] f32 with counts keep_n clamped to [0, max_keypoints] on the device; image p reads unit
+ *      p * unit_stride (1 or 2), as the patch tracker does.  Row i < n_keep is LIVE iff x and y are finite and in [0, 16384).  For a
+ *      live row xa = floor(x + 0.5), ya = floor(y + 0.5) in fp64 (the tracker's step 2).  With d > 0 and keep given, a candidate at
+ *      (cx, cy) with max(|cx - xa|, |cy - ya|) < d for any live row is removed.  The mask is applied after step 2: a masked pixel still
+ *      suppresses its neighbours.  M is the number of candidates left.
+ *   4. Selection.  The existing rule, unchanged, on the M keys (bits((float)s) << 32) | (cy * W + cx) with scale 1: SSHIP_SELECT_TOPK
+ *      takes the first K = min(M, max_new) in descending (s, y, x) order; SSHIP_SELECT_BALANCED with bucket_px is the rule stated at
+ *      sship_sp_set_keypoint_selection, written in the default mode's order.  A new keypoint is ((float)cx, (float)cy, (float)s).
+ *   5. Merge.  L is the number of live rows (0 without keep).  The live rows are written first to kp_out, in input order, all three
+ *      floats bit for bit; carry0[i] is the output row of input row i, -1 for dead rows and rows at or beyond n_keep.  Then the first
+ *      A = min(K, max_keypoints - L, target > 0 ? max(0, target - L) : K) selected keypoints are appended; n_out = L + A; rows at or
+ *      beyond n_out are (0, 0, 0).  Every entry of every output is written.  carry0 has the shape and meaning of a matcher's matches0
+ *      between the old list and the new one: sship_ba_tracks_from_matches_batch_device and sship_pose_obs_from_matches_batch_device
+ *      take it unchanged.  In balanced mode with a target that truncates, the kept rows are a score-ordered prefix of the balanced set
+ *      (the K selected keys are emitted in descending key order, and the first A of them are appended), not the balanced set of size A.
+ * sship_fast_params: threshold (default 20), border (8), min_distance (10), selection (SSHIP_SELECT_TOPK), bucket_px (32; read in
+ * balanced mode only, [8, 65535]), max_new in [1, max_keypoints] (default max_keypoints), target >= 0 (0 = off).  sship_fast_create: h
+ * and w in [7, 16384], max_keypoints in [1, 4096], max_images in [1, 65535]; every workspace (the key list of 8 bytes per candidate of
+ * the bound, the balanced rule's workspace, the selected keypoints - per image) is allocated here and nothing later; the mask needs
+ * none (k_fast_detect builds its tile's part of it in LDS from the keep rows, by OR, so it does not depend on execution order).  sship_fast_detect_batch_device: imgs_dev holds `images` <= max_images images, image i at imgs_dev + i *
+ * image_stride, rows `stride` bytes apart (>= w), image_stride >= 0, no alignment asked (image_stride = 2 * h * stride reads the left
+ * images of an L0, R0, ... batch).  keep_dev may be NULL (no live rows, no mask; keep_n_dev and unit_stride are then ignored); given,
+ * keep_n_dev is required and keep_dev must not overlap kp_out_dev (refused).  kp_out_dev [images, max_keypoints, 3] f32, n_out_dev
+ * [images] i32, carry0_dev [images, max_keypoints] i32 or NULL, n_candidates_dev [images] i32 (M) or NULL.  Asynchronous on `stream`,
+ * no host synchronisation: one memset node (the candidate counters), k_fast_detect, k_select_balanced (that mode only), k_topk,
+ * k_fast_merge.  sship_fast_detect_host is one image from host arrays (keep rows keep_stride >= 3 floats apart, n_keep
+ * in [0, max_keypoints]; kp_out [max_keypoints, 3], carry0 [max_keypoints] or NULL), staged through one device block: the same launches
+ * with images = 1, hence the same bits.  sship_fast_score_batch_device is the stage form of step 1 alone and needs no handle: the u8
+ * score map of every image with caller strides.  sship_fast_bench re-runs the last call's launches `iters` times on the handle's
+ * stream; sship_fast_bench_kernels the chosen ones (bit 0 k_fast_detect, 1 the selection, 2 k_fast_merge; 1 .. 7).
+ * Every bad argument is SSHIP_ERR_INVALID before any device is touched; valid create arguments without a GPU are SSHIP_ERR_NO_DEVICE.
+ * Not wired into sship_frontend_batch_device, bench.py or examples/frontend_benchmark.cc; 8-bit images only.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct sship_fast sship_fast;
+typedef struct sship_fast_params {
+  int threshold, border, min_distance, selection, bucket_px, max_new, target;
+} sship_fast_params;
+int sship_fast_create(int h, int w, int max_keypoints, int max_images, sship_fast** out);
+void sship_fast_destroy(sship_fast* fast);
+int sship_fast_set_params(sship_fast* fast, const sship_fast_params* params);
+int sship_fast_get_params(const sship_fast* fast, sship_fast_params* params, int* h, int* w, int* max_keypoints, int* max_images);
+int sship_fast_detect_batch_device(sship_fast* fast, const uint8_t* imgs_dev, long long image_stride, int stride, int images,
+                                   const float* keep_dev, const int* keep_n_dev, int unit_stride, float* kp_out_dev, int* n_out_dev,
+                                   int32_t* carry0_dev, int* n_candidates_dev, void* stream);
+int sship_fast_detect_host(const uint8_t* img, int stride, int h, int w, int max_keypoints, const sship_fast_params* params,
+                           const float* keep, int keep_stride, int n_keep, float* kp_out, int* n_out, int32_t* carry0,
+                           int* n_candidates);
+int sship_fast_score_batch_device(const uint8_t* imgs_dev, long long image_stride, int stride, int images, int h, int w, uint8_t* score_dev,
+                                  long long score_image_stride, int score_stride, void* stream);
+int sship_fast_bench(sship_fast* fast, int iters, float* avg_ms);
+int sship_fast_bench_kernels(sship_fast* fast, int kernels, int iters, float* avg_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused front-end step: what StereoFrontEnd::process asks of the two interfaces per frame
  * (src/StereoFrontEnd.cc:14,33): SuperPoint on L and R (one batch) + gather x2 + one LightGlue match,
  * for `pairs` stereo pairs at once, device-resident, no host synchronisation.  imgs_dev is

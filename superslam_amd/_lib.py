@@ -91,6 +91,11 @@ class PyrTrackParams(C.Structure):
     _fields_ = [("fine", PatchTrackParams), ("levels", C.c_int), ("coarse_radius", C.c_int)]
 
 
+class FastParams(C.Structure):
+    _fields_ = [("threshold", C.c_int), ("border", C.c_int), ("min_distance", C.c_int), ("selection", C.c_int), ("bucket_px", C.c_int),
+                ("max_new", C.c_int), ("target", C.c_int)]
+
+
 _lib = None
 vp, ip, fp, dp = C.c_void_p, C.c_int, C.c_float, C.c_double
 _SIGS = {
@@ -277,6 +282,15 @@ _SIGS = {
     "sship_clahe_apply_host": (ip, [vp, ip, ip, ip, ip, ip, dp, vp, ip]),
     "sship_clahe_bench": (ip, [vp, ip, C.POINTER(fp)]),
     "sship_clahe_bench_kernels": (ip, [vp, ip, ip, C.POINTER(fp)]),
+    "sship_fast_create": (ip, [ip, ip, ip, ip, C.POINTER(vp)]),
+    "sship_fast_destroy": (None, [vp]),
+    "sship_fast_set_params": (ip, [vp, C.POINTER(FastParams)]),
+    "sship_fast_get_params": (ip, [vp, C.POINTER(FastParams), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]),
+    "sship_fast_detect_batch_device": (ip, [vp, vp, C.c_longlong, ip, ip, vp, vp, ip, vp, vp, vp, vp, vp]),
+    "sship_fast_detect_host": (ip, [vp, ip, ip, ip, ip, C.POINTER(FastParams), vp, ip, ip, vp, vp, vp, vp]),
+    "sship_fast_score_batch_device": (ip, [vp, C.c_longlong, ip, ip, ip, ip, vp, C.c_longlong, ip, vp]),
+    "sship_fast_bench": (ip, [vp, ip, C.POINTER(fp)]),
+    "sship_fast_bench_kernels": (ip, [vp, ip, ip, C.POINTER(fp)]),
     "sship_desc_to_host": (ip, [vp, ip, ip, vp]),
     "sship_frontend_batch_device": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_bench_layer": (ip, [vp, ip, ip, ip, ip, ip, C.POINTER(fp), C.POINTER(C.c_double)]),

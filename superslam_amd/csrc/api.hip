@@ -4829,6 +4829,201 @@ extern "C" int sship_clahe_bench_kernels(sship_clahe* clahe, int kernels, int it
 extern "C" int sship_clahe_bench(sship_clahe* clahe, int iters, float* avg_ms) { return sship_clahe_bench_kernels(clahe, 3, iters, avg_ms); }
 
 // ====================================================================================================
+// FAST corners with track refill (sship_fast_*; the rule is in include/sship.h)
+// ====================================================================================================
+struct sship_fast {
+  int h = 0, w = 0, max_kp = 0, max_images = 0, cap = 0, nb_max = 0;
+  sship_fast_params p = {};
+  hipStream_t stream = nullptr;
+  DevBuf cand, counts, new_kp, cells, sel, sel_ws;   // counts: [3][max_images] candidates | selected by the balanced rule | new keypoints
+  // the last call
+  const uint8_t* imgs = nullptr;
+  long long image_stride = 0;
+  int stride = 0, images = 0, unit_stride = 1;
+  const float* keep = nullptr;
+  const int* keep_n = nullptr;
+  float* kp_out = nullptr;
+  int *n_out = nullptr, *carry0 = nullptr, *n_cand = nullptr;
+};
+static int fast_check_size(int h, int w, const char* who) {
+  if (h < 7 || w < 7 || h > 16384 || w > 16384) return fail(SSHIP_ERR_INVALID, std::string(who) + ": h and w must be in [7, 16384]");
+  return SSHIP_OK;
+}
+static int fast_check_params(const sship_fast_params* p, int max_kp, const char* who) {
+  if (p->threshold < 0 || p->threshold > 254) return fail(SSHIP_ERR_INVALID, std::string(who) + ": threshold must be in [0, 254]");
+  if (p->border < 3 || p->border > 64) return fail(SSHIP_ERR_INVALID, std::string(who) + ": border must be in [3, 64]");
+  if (p->min_distance < 0 || p->min_distance > 32) return fail(SSHIP_ERR_INVALID, std::string(who) + ": min_distance must be in [0, 32]");
+  if (p->selection != SSHIP_SELECT_TOPK && p->selection != SSHIP_SELECT_BALANCED)
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": selection must be 0 (top-k) or 1 (balanced)");
+  if (p->selection == SSHIP_SELECT_BALANCED && (p->bucket_px < 8 || p->bucket_px > 65535))
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": bucket_px must be in [8, 65535]");
+  if (p->max_new < 1 || p->max_new > max_kp) return fail(SSHIP_ERR_INVALID, std::string(who) + ": max_new must be in [1, max_keypoints]");
+  if (p->target < 0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": target must be >= 0 (0: off)");
+  return SSHIP_OK;
+}
+static sship_fast_params fast_default_params(int max_kp) { return sship_fast_params{20, 8, 10, SSHIP_SELECT_TOPK, 32, max_kp, 0}; }
+extern "C" int sship_fast_create(int h, int w, int max_keypoints, int max_images, sship_fast** out) {
+  if (!out) return fail(SSHIP_ERR_INVALID, "fast_create: null argument");
+  *out = nullptr;
+  if (int rc = fast_check_size(h, w, "fast_create")) return rc;
+  if (max_keypoints < 1 || max_keypoints > kMaxKp) return fail(SSHIP_ERR_INVALID, "fast_create: max_keypoints must be in [1, 4096]");
+  if (max_images < 1 || max_images > 65535) return fail(SSHIP_ERR_INVALID, "fast_create: max_images must be in [1, 65535]");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  std::unique_ptr<sship_fast, void (*)(sship_fast*)> f(new sship_fast(), sship_fast_destroy);
+  f->h = h; f->w = w; f->max_kp = max_keypoints; f->max_images = max_images; f->p = fast_default_params(max_keypoints);
+  f->cap = ((h + 1) / 2) * ((w + 1) / 2);            // no two candidates are 8-neighbours: the list cannot overflow
+  f->nb_max = ((h + 7) / 8) * ((w + 7) / 8);         // the buckets of the smallest bucket_px
+  const size_t B = (size_t)max_images, mk = (size_t)max_keypoints;
+  SSHIP_HIP_CHECK(f->cand.ensure(B * f->cap * 8));
+  SSHIP_HIP_CHECK(f->counts.ensure(3 * B * 4));
+  SSHIP_HIP_CHECK(f->new_kp.ensure(B * mk * 12));
+  SSHIP_HIP_CHECK(f->cells.ensure(2 * B * mk * 4));
+  SSHIP_HIP_CHECK(f->sel.ensure(B * mk * 8));
+  SSHIP_HIP_CHECK(f->sel_ws.ensure(sel_ws_layout(f->sel_ws, max_images, f->cap, f->nb_max, nullptr)));
+  SSHIP_HIP_CHECK(hipMemset(f->counts.p, 0, 3 * B * 4));
+  SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&f->stream, hipStreamDefault));
+  *out = f.release();
+  return SSHIP_OK;
+}
+extern "C" void sship_fast_destroy(sship_fast* fast) { destroy_handle(fast); }
+extern "C" int sship_fast_set_params(sship_fast* fast, const sship_fast_params* p) {
+  if (!fast || !p) return fail(SSHIP_ERR_INVALID, "fast_set_params: null argument");
+  if (int rc = fast_check_params(p, fast->max_kp, "fast_set_params")) return rc;
+  fast->p = *p;   // by value into the next call's launches
+  return SSHIP_OK;
+}
+extern "C" int sship_fast_get_params(const sship_fast* fast, sship_fast_params* p, int* h, int* w, int* max_keypoints, int* max_images) {
+  if (!fast) return fail(SSHIP_ERR_INVALID, "fast_get_params: null argument");
+  if (p) *p = fast->p;
+  if (h) *h = fast->h;
+  if (w) *w = fast->w;
+  if (max_keypoints) *max_keypoints = fast->max_kp;
+  if (max_images) *max_images = fast->max_images;
+  return SSHIP_OK;
+}
+// the last call's launches: bit 0 k_fast_detect (and the clearing of its counters), bit 1 the selection (k_select_balanced in that mode,
+// k_topk), bit 2 k_fast_merge
+static hipError_t fast_launch(const sship_fast* f, int kernels, hipStream_t s) {
+  const int B = f->images, mk = f->max_kp;
+  const sship_fast_params& p = f->p;
+  int* cand_count = f->counts.as<int>();
+  int* sel_count = cand_count + f->max_images;
+  int* n_new = sel_count + f->max_images;
+  if (kernels & 1) {
+    if (hipError_t e = hipMemsetAsync(cand_count, 0, (size_t)B * 4, s)) return e;
+    const FastK c{f->h, f->w, (f->w + kFastTileW - 1) / kFastTileW, (f->h + kFastTileH - 1) / kFastTileH, p.threshold, p.border, f->cap,
+                  p.min_distance, mk, f->unit_stride};
+    launch_fast_detect(f->imgs, f->image_stride, f->stride, c, f->keep, f->keep_n, f->cand.as<unsigned long long>(), cand_count, B, s);
+  }
+  if (kernels & 2) {
+    TopkArgs t{};
+    t.cand = f->cand.as<unsigned long long>(); t.cand_count = cand_count; t.cap = f->cap; t.max_kp = p.max_new; t.score_w = f->w;
+    t.scale_x = 1.f; t.scale_y = 1.f; t.desc_h = 1; t.desc_w = 1;
+    t.kp_xys = f->new_kp.as<float>(); t.cell_h = f->cells.as<int>(); t.cell_w = f->cells.as<int>() + (size_t)f->max_images * mk;
+    t.n_out = n_new; t.n_cand_out = f->n_cand; t.reset_count = nullptr; t.pix = nullptr;
+    if (p.selection == SSHIP_SELECT_BALANCED) {
+      SelWs ws;
+      sel_ws_layout(f->sel_ws, f->max_images, f->cap, f->nb_max, &ws);
+      SelectBalancedArgs q = select_balanced_args(t.cand, cand_count, f->cap, p.max_new, f->h, f->w, p.bucket_px, f->sel.as<unsigned long long>(),
+                                                  sel_count, ws);
+      q.n_cand_out = f->n_cand;
+      if (hipError_t e = launch_select_balanced(q, B, s)) return e;
+      t.cand = q.sel; t.cand_count = q.sel_count; t.cap = p.max_new; t.n_cand_out = nullptr;
+    }
+    launch_topk(t, B, s);
+  }
+  if (kernels & 4)
+    launch_fast_merge(f->keep, f->keep_n, f->unit_stride, mk, f->new_kp.as<float>(), n_new, p.max_new, p.target, f->kp_out, f->n_out, f->carry0, B, s);
+  return hipGetLastError();
+}
+extern "C" int sship_fast_detect_batch_device(sship_fast* fast, const uint8_t* imgs, long long image_stride, int stride, int images,
+                                              const float* keep, const int* keep_n, int unit_stride, float* kp_out, int* n_out,
+                                              int32_t* carry0, int* n_candidates, void* stream) {
+  const char* who = "fast_detect_batch_device";
+  if (!fast || !imgs || !kp_out || !n_out) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  if (images < 1 || images > fast->max_images) return fail(SSHIP_ERR_INVALID, std::string(who) + ": images must be in [1, max_images]");
+  if (stride < fast->w) return fail(SSHIP_ERR_INVALID, std::string(who) + ": stride (bytes) must be >= w");
+  if (image_stride < 0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": image_stride (bytes) must be >= 0");
+  if (keep) {
+    if (!keep_n) return fail(SSHIP_ERR_INVALID, std::string(who) + ": keep needs keep_n");
+    if (unit_stride != 1 && unit_stride != 2) return fail(SSHIP_ERR_INVALID, std::string(who) + ": unit_stride must be 1 or 2");
+    // the merge of one image reads rows another image's merge may already have written: refused, not ordered
+    const size_t unit = (size_t)fast->max_kp * 12;
+    const char *k0 = reinterpret_cast<const char*>(keep), *k1 = k0 + ((size_t)(images - 1) * unit_stride + 1) * unit;
+    const char *o0 = reinterpret_cast<const char*>(kp_out), *o1 = o0 + (size_t)images * unit;
+    if (k0 < o1 && o0 < k1) return fail(SSHIP_ERR_INVALID, std::string(who) + ": keep must not overlap kp_out");
+  }
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  fast->imgs = imgs; fast->image_stride = image_stride; fast->stride = stride; fast->images = images;
+  fast->keep = keep; fast->keep_n = keep ? keep_n : nullptr; fast->unit_stride = keep ? unit_stride : 1;
+  fast->kp_out = kp_out; fast->n_out = n_out; fast->carry0 = carry0; fast->n_cand = n_candidates;
+  SSHIP_HIP_CHECK(fast_launch(fast, 7, s));
+  g_timer.mark("fast_detect", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_fast_detect_host(const uint8_t* img, int stride, int h, int w, int max_keypoints, const sship_fast_params* p,
+                                      const float* keep, int keep_stride, int n_keep, float* kp_out, int* n_out, int32_t* carry0,
+                                      int* n_candidates) {
+  const char* who = "fast_detect_host";
+  if (!img || !p || !kp_out || !n_out) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  if (int rc = fast_check_size(h, w, who)) return rc;
+  if (max_keypoints < 1 || max_keypoints > kMaxKp) return fail(SSHIP_ERR_INVALID, std::string(who) + ": max_keypoints must be in [1, 4096]");
+  if (int rc = fast_check_params(p, max_keypoints, who)) return rc;
+  if (stride < w) return fail(SSHIP_ERR_INVALID, std::string(who) + ": stride (bytes) must be >= w");
+  if (keep && (n_keep < 0 || n_keep > max_keypoints || keep_stride < 3))
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": with keep, n_keep must be in [0, max_keypoints] and keep_stride >= 3");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  sship_fast* raw = nullptr;
+  if (int rc = sship_fast_create(h, w, max_keypoints, 1, &raw)) return rc;
+  std::unique_ptr<sship_fast, void (*)(sship_fast*)> f(raw, sship_fast_destroy);
+  raw->p = *p;
+  const FastStage st = fast_stage(h, w, max_keypoints);
+  std::vector<char> tail(st.tail_bytes, 0);
+  fast_pack(tail.data(), st, keep, keep_stride, keep ? n_keep : 0);
+  StageArena a;
+  SSHIP_HIP_CHECK(a.create(st.in_bytes, st.out_bytes, false));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(st.img), (size_t)w, img, (size_t)stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<char>(st.n), tail.data(), st.tail_bytes, hipMemcpyHostToDevice));
+  if (int rc = sship_fast_detect_batch_device(raw, a.dev<uint8_t>(st.img), 0, w, 1, keep ? a.dev<float>(st.keep) : nullptr, a.dev<int>(st.n), 1,
+                                              a.dev<float>(a.out + st.kp), a.dev<int>(a.out + st.counts), a.dev<int32_t>(a.out + st.carry),
+                                              a.dev<int>(a.out + st.counts) + 1, nullptr)) return rc;
+  std::vector<char> back(st.out_bytes);
+  SSHIP_HIP_CHECK(hipMemcpy(back.data(), a.dev<char>(a.out), st.out_bytes, hipMemcpyDeviceToHost));   // blocking, on the NULL stream: after the launches
+  fast_unpack(back.data(), st, kp_out, n_out, carry0, n_candidates);
+  return SSHIP_OK;
+}
+extern "C" int sship_fast_score_batch_device(const uint8_t* imgs, long long image_stride, int stride, int images, int h, int w, uint8_t* score,
+                                             long long score_image_stride, int score_stride, void* stream) {
+  const char* who = "fast_score_batch_device";
+  if (!imgs || !score) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  if (int rc = fast_check_size(h, w, who)) return rc;
+  if (images < 1 || images > 65535) return fail(SSHIP_ERR_INVALID, std::string(who) + ": images must be in [1, 65535]");
+  if (stride < w || score_stride < w) return fail(SSHIP_ERR_INVALID, std::string(who) + ": stride (bytes) must be >= w");
+  if (image_stride < 0 || score_image_stride < 0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": image_stride (bytes) must be >= 0");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  launch_fast_score(imgs, image_stride, stride, h, w, score, score_image_stride, score_stride, images, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("fast_score", s);
+  return SSHIP_OK;
+}
+// Measurement hooks (include/sship.h): the last call's launches re-run `iters` times on the handle's stream; kernels as at fast_launch
+extern "C" int sship_fast_bench_kernels(sship_fast* fast, int kernels, int iters, float* avg_ms) {
+  if (!fast || !avg_ms || iters <= 0 || kernels < 1 || kernels > 7) return fail(SSHIP_ERR_INVALID, "fast_bench: bad arguments");
+  if (fast->images <= 0) return fail(SSHIP_ERR_INVALID, "fast_bench: detect with the handle first");
+  bind_thread();
+  SSHIP_HIP_CHECK(hipDeviceSynchronize());   // the last call may have run on the caller's stream
+  return bench_loop(fast->stream, iters, [&]() { return fast_launch(fast, kernels, fast->stream); }, avg_ms);
+}
+extern "C" int sship_fast_bench(sship_fast* fast, int iters, float* avg_ms) { return sship_fast_bench_kernels(fast, 7, iters, avg_ms); }
+
+// ====================================================================================================
 // fused front-end step: SuperPoint(batch 2P) + select + gather + LightGlue(P)
 // ====================================================================================================
 extern "C" int sship_frontend_batch_device(sship_sp* sp, sship_lg* lg, const uint8_t* imgs, int pairs, int h, int w,

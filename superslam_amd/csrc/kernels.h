@@ -401,4 +401,21 @@ void launch_clahe_lut(const uint8_t* src, long long src_image_stride, long long 
 void launch_clahe_apply(const uint8_t* src, long long src_image_stride, long long src_stride, uint8_t* dst, long long dst_image_stride,
                         long long dst_stride, int h, int w, const ClaheK& c, const uint8_t* luts, int images, hipStream_t s);
 
+// FAST corners with track refill (fast_kernels.hip; the rule is in include/sship.h "FAST corners")
+constexpr int kFastTileW = 64, kFastTileH = 32;
+// cap = ceil(h / 2) * ceil(w / 2): the key list of an image cannot overflow (no two candidates are 8-neighbours);
+// min_distance, max_kp and unit_stride describe the keep list of step 3
+struct FastK { int h, w, tiles_x, tiles_y, threshold, border, cap, min_distance, max_kp, unit_stride; };
+// step 1 alone: u8 scores [images, h, w] with caller strides (bytes), no alignment asked of either side
+void launch_fast_score(const uint8_t* imgs, long long image_stride, long long stride, int h, int w, uint8_t* score,
+                       long long score_image_stride, long long score_stride, int images, hipStream_t s);
+// steps 1-3: the keys (bits((float)s) << 32) | (y * w + x) of the candidates into cand [images, cap], their number added to cand_count
+// [images] (zeroed by the caller).  keep [units, max_kp, 3] with counts keep_n, image p reads unit p * unit_stride: the mask of step 3,
+// applied when keep is given and min_distance > 0
+void launch_fast_detect(const uint8_t* imgs, long long image_stride, long long stride, const FastK& c, const float* keep, const int* keep_n,
+                        unsigned long long* cand, int* cand_count, int images, hipStream_t s);
+// step 5: keep may be null (L = 0); new_kp [images, max_new, 3] and n_new [images] are what k_topk left; carry0 may be null
+void launch_fast_merge(const float* keep, const int* keep_n, int unit_stride, int max_kp, const float* new_kp, const int* n_new, int max_new,
+                       int target, float* kp_out, int* n_out, int* carry0, int images, hipStream_t s);
+
 }  // namespace sship

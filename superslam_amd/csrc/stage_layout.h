@@ -214,4 +214,31 @@ inline void pair_pack_pred(char* tail, const PairStage& st, const float* pred, i
   for (int i = 0; i < n; ++i) memcpy(rows + (size_t)i * 12, pred + (size_t)i * pred_stride, 8);
 }
 
+// ---- FAST corners, one image: img [h][w] | n_keep | keep [max_kp][3] -> kp [max_kp][3] | counts (n_out, n_candidates) | carry0 [max_kp] --------
+// The image is packed to stride w and copied straight from the caller's strided memory; the host block mirrors the input region from
+// `n` on (`tail_bytes` of it).
+struct FastStage { size_t img, n, keep, in_bytes, tail_bytes, kp, counts, carry, out_bytes, rows; };
+inline FastStage fast_stage(int h, int w, int max_kp) {
+  StageLayout in, out;
+  FastStage s;
+  s.rows = (size_t)max_kp;
+  s.img = in.add((size_t)h * w); s.n = in.add(4); s.keep = in.add(s.rows * 12); s.in_bytes = in.end;
+  s.tail_bytes = s.in_bytes - s.n;
+  s.kp = out.add(s.rows * 12); s.counts = out.add(8); s.carry = out.add(s.rows * 4); s.out_bytes = out.end;
+  return s;
+}
+// the count, then (x, y, score) rows out of the caller's keep_stride-strided ones (keep_stride >= 3); rows from n_keep on stay zero
+inline void fast_pack(char* tail, const FastStage& st, const float* keep, int keep_stride, int n_keep) {
+  const int32_t n32 = n_keep;
+  memcpy(tail, &n32, 4);
+  char* rows = tail + (st.keep - st.n);
+  for (int i = 0; i < n_keep; ++i) memcpy(rows + (size_t)i * 12, keep + (size_t)i * keep_stride, 12);
+}
+inline void fast_unpack(const char* out, const FastStage& st, float* kp_out, int32_t* n_out, int32_t* carry0, int32_t* n_candidates) {
+  memcpy(kp_out, out + st.kp, st.rows * 12);
+  memcpy(n_out, out + st.counts, 4);
+  if (n_candidates) memcpy(n_candidates, out + st.counts + 4, 4);
+  if (carry0) memcpy(carry0, out + st.carry, st.rows * 4);
+}
+
 }  // namespace sship
