@@ -1620,6 +1620,92 @@ int sship_fast_bench(sship_fast* fast, int iters, float* avg_ms);
 int sship_fast_bench_kernels(sship_fast* fast, int kernels, int iters, float* avg_ms);
 
 /* ------------------------------------------------------------------------------------------------
+ * Binary descriptors - steered BRIEF at given keypoints: the stage that lets the no-network chain RECOGNISE a point (re-acquire a lost
+ * track, match a keyframe against a loop candidate of sship_index_*, associate left and right corner lists by appearance).  Modelled on
+ * ORB's rBRIEF (Rublee et al.).  Equality with OpenCV is NOT claimed: the pattern is this library's own, generated by the rule below, not
+ * OpenCV's learned table.  Integers and comparisons throughout: the kernel equals the numpy restatement (tests/_brief_ref.py) bit for
+ * bit.  Stateless, like sship_patch_track_*.
+ * The rule.  Image I is u8, h x W.  A descriptor is 256 bits in 8 u32 words; bit t is stored in word t >> 5 at position t & 31.
+ *   Tables.  For k = 0..31, C[k] = rint(16384 cos(2 pi k / 32)):
+ *      C = 16384, 16069, 15137, 13623, 11585, 9102, 6270, 3196, 0, -3196, -6270, -9102, -11585, -13623, -15137, -16069,
+ *          -16384, -16069, -15137, -13623, -11585, -9102, -6270, -3196, 0, 3196, 6270, 9102, 11585, 13623, 15137, 16069
+ *      and S[k] = C[(k + 24) % 32] (the sine).  C[k+8] = -S[k] and S[k+8] = C[k] exactly (indices mod 32).
+ *   Pattern.  mix(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16 (mod 2^32; the RANSAC sampler's mix).
+ *      v(c) = mix(mix(1 + 0x9e3779b9 * (c + 1))), coord(c) = v % 8 + (v >> 8) % 8 + (v >> 16) % 7 - 10, in [-10, 10].  Test t takes four
+ *      consecutive counters as (ax, ay, bx, by); a draw with (ax, ay) == (bx, by) is discarded and the next four counters are used
+ *      (the first 1024 counters give the 256 tests; none is discarded).  For bin k a point (x, y) becomes (rd(x C[k] - y S[k]),
+ *      rd(x S[k] + y C[k])) with rd(v) = sgn(v) * ((|v| + 8192) >> 14): symmetric about zero, so that the table of bin k + 8 is the table
+ *      of bin k turned by 90 degrees exactly (floor rounding would break that).  Every rotated coordinate has |.| <= 14; the reach is
+ *      E = 16: 14 plus the box half-width 2, and not less than the moment radius 15.  sship_brief_pattern(bin, out[256 * 4]) returns the
+ *      rotated table of a bin as int8 (ax', ay', bx', by') rows: pure host, no GPU.
+ *   Keypoint i of image p is row i of unit p * unit_stride (1 or 2) of kp [units, max_keypoints, 3] f32 with counts n [units], as FAST
+ *      reads keep.  If i >= n (n clamped to [0, max_keypoints] on the device) the status is NONE.  Otherwise, if x or y is not finite or
+ *      lies outside [0, 16384), BORDER.  Otherwise xa = floor(x + 0.5), ya = floor(y + 0.5) in fp64 (the tracker's step 2), and the status
+ *      is BORDER unless xa - 16 >= 0, xa + 16 < W, ya - 16 >= 0 and ya + 16 < h; else OK.
+ *   Orientation (SSHIP_BRIEF_STEERED).  Over the disc dx^2 + dy^2 <= 225: m10 = sum dx I[ya+dy, xa+dx], m01 = sum dy I[ya+dy, xa+dx]
+ *      (both fit int32).  bin = the smallest k attaining max over k of (m10 C[k] + m01 S[k]), in int64; a flat patch gives bin 0.  With
+ *      SSHIP_BRIEF_UPRIGHT bin = 0 and no moments are computed.
+ *   Bits.  B(x, y) is the sum of the 5 x 5 box of I centred on (x, y).  With (ax', ay', bx', by') the bin's rotated test t,
+ *      bit t = B(xa + ax', ya + ay') < B(xa + bx', ya + by').
+ *   Outputs.  desc [images, max_keypoints, 8] u32, all zero for every status other than OK; status u8 (optional): SSHIP_BRIEF_NONE 0,
+ *      SSHIP_BRIEF_OK 1, SSHIP_BRIEF_BORDER 2; bin u8 (optional): 0 where the status is not OK.  Every entry of every output is written.
+ * sship_brief_describe_batch_device: image i at imgs_dev + i * image_stride in rows of `stride` bytes (>= w), image_stride >= 0, no
+ * alignment asked (image_stride = 2 * h * stride reads the left images of an L0, R0, ... batch); images in [1, 65535], max_keypoints in
+ * [1, 4096], h and w in [33, 16384], unit_stride 1 or 2, mode SSHIP_BRIEF_STEERED or SSHIP_BRIEF_UPRIGHT.  One launch (k_brief_describe),
+ * no host synchronisation.  sship_brief_describe_host is one image from host arrays (n rows kp_stride >= 2 floats apart, n in [0, 4096];
+ * desc [n, 8], status [n] or NULL, bin [n] or NULL), staged through one device block: the same launch with images = 1 and max_keypoints =
+ * n, hence the same bits.  Every bad argument is SSHIP_ERR_INVALID before any device is touched.
+ *
+ * Hamming matcher (sship_hm_*) - mutual nearest neighbour over such descriptors.  A handle whose workspace is sized at create, like
+ * sship_nn_*.  The rule.  Sets d0 [n0, 8] and d1 [n1, 8] u32 with optional per-row status and, when the handle's gate is on, keypoints.
+ * Entry (i, j) is PRESENT iff i < n0 and j < n1, both statuses are SSHIP_BRIEF_OK where a status array is given, and the gate admits it
+ * where the gate is on.  The gate is sship_nn_set_gate's rule and form: with dx = x0_i - x1_j and dy = y0_i - y1_j in fp32, the entry is
+ * admitted iff dx >= dx_lo && dx <= dx_hi && dy >= dy_lo && dy <= dy_hi (a NaN coordinate is in no window; infinite bounds are allowed;
+ * the open gate gives the ungated bits).  Per row i: D_ij = sum over the 8 words of popcount(d0[i] ^ d1[j]); j1 is the smallest present j
+ * of the minimum and e1 that minimum; e2 is the minimum over the other present entries, absent when fewer than two are present;
+ * pass = (max_distance == 0 || e1 <= max_distance) && (ratio_percent == 0 || e2 absent || 100 e1 <= ratio_percent e2), in integers;
+ * fwd_i = pass ? j1 : -1; a row with no present entry gives -1.  Columns follow the same rule (bwd).  matches0_i = fwd_i if fwd_i >= 0 and
+ * (!mutual_check || bwd[fwd_i] == i), else -1; dist0_i = e1 when matched, else -1; the optional mscores0_i = (256 - e1) / 256 as f32 when
+ * matched (exact), else 0 - with it sship_filter_matches yields distance = e1 / 256.  Rows >= n0 are -1 / -1 / 0.  A pair's result does
+ * not depend on the other pairs of the call or on its position; no kernel has an atomic.
+ * Defaults: max_distance 0 (off; 0..256), ratio_percent 0 (off; 0..100), mutual_check on, gate off.
+ * sship_hm_create(max_keypoints 1..4096, max_pairs 1..65535): everything is allocated here and nothing later.
+ * sship_hm_match_batch_device: n_dev [units] i32 (clamped to [0, max_keypoints] on the device), desc_dev [units, max_keypoints, 8] u32
+ * (16-byte aligned), status_dev [units, max_keypoints] u8 or NULL, kp_dev [units, max_keypoints, 3] f32 (NULL unless gated; a gated
+ * handle called without it is refused).  Set 0 of pair p is unit first0 + p * step0, set 1 is unit first1 + p * step1 (the pyramid
+ * tracker's first / step convention; firsts and steps >= 0): (0, 2, 1, 2) is the stereo layout, (0, 1, 1, 1) consecutive frames,
+ * (0, 0, 1, 1) one keyframe against many.  matches0_dev, dist0_dev [pairs, max_keypoints] i32, mscores0_dev [pairs, max_keypoints] f32 or
+ * NULL.  Asynchronous on `stream`, no host synchronisation: k_hm_best, then k_hm_final.  matches0 has the shape and meaning of every
+ * matcher's here: sship_stereo_associate_batch_device, sship_pose_obs_from_matches_batch_device and
+ * sship_ba_tracks_from_matches_batch_device take it unchanged.  sship_hm_match_host is one pair from host arrays (n0, n1 in [0,
+ * max_keypoints]; status0 / status1 may be NULL; kp0 / kp1 rows kp_stride >= 2 floats apart, read only when gated; outputs [n0]) through
+ * the handle's staging arena: the same launches.  sship_hm_bench re-runs the last call's launches `iters` times on the handle's stream.
+ * Not wired into sship_frontend_batch_device, bench.py or examples/frontend_benchmark.cc.
+ * ---------------------------------------------------------------------------------------------- */
+enum { SSHIP_BRIEF_STEERED = 0, SSHIP_BRIEF_UPRIGHT = 1 };
+enum { SSHIP_BRIEF_NONE = 0, SSHIP_BRIEF_OK = 1, SSHIP_BRIEF_BORDER = 2 };
+int sship_brief_pattern(int bin, int8_t* out_256x4);
+int sship_brief_describe_batch_device(const uint8_t* imgs_dev, long long image_stride, int stride, int images, int h, int w,
+                                      const float* kp_dev, const int* n_dev, int unit_stride, int max_keypoints, int mode,
+                                      uint32_t* desc_dev, uint8_t* status_dev, uint8_t* bin_dev, void* stream);
+int sship_brief_describe_host(const uint8_t* img, int stride, int h, int w, const float* keypoints, int kp_stride, int n, int mode,
+                              uint32_t* desc, uint8_t* status, uint8_t* bin);
+typedef struct sship_hm sship_hm;
+int sship_hm_create(int max_keypoints, int max_pairs, sship_hm** out);
+void sship_hm_destroy(sship_hm* hm);
+int sship_hm_set_params(sship_hm* hm, int max_distance, int ratio_percent, int mutual_check);
+int sship_hm_get_params(const sship_hm* hm, int* max_distance, int* ratio_percent, int* mutual_check, int* max_keypoints, int* max_pairs);
+int sship_hm_set_gate(sship_hm* hm, int enabled, float dx_lo, float dx_hi, float dy_lo, float dy_hi);
+int sship_hm_get_gate(const sship_hm* hm, int* enabled, float* dx_lo, float* dx_hi, float* dy_lo, float* dy_hi);
+int sship_hm_match_batch_device(sship_hm* hm, const int* n_dev, const uint32_t* desc_dev, const uint8_t* status_dev, const float* kp_dev,
+                                int first0, int step0, int first1, int step1, int pairs, int32_t* matches0_dev, int32_t* dist0_dev,
+                                float* mscores0_dev, void* stream);
+int sship_hm_match_host(sship_hm* hm, int n0, const uint32_t* desc0, const uint8_t* status0, const float* kp0, int kp_stride0, int n1,
+                        const uint32_t* desc1, const uint8_t* status1, const float* kp1, int kp_stride1, int32_t* matches0,
+                        int32_t* dist0, float* mscores0);
+int sship_hm_bench(sship_hm* hm, int iters, float* avg_ms);
+
+/* ------------------------------------------------------------------------------------------------
  * Fused front-end step: what StereoFrontEnd::process asks of the two interfaces per frame
  * (src/StereoFrontEnd.cc:14,33): SuperPoint on L and R (one batch) + gather x2 + one LightGlue match,
  * for `pairs` stereo pairs at once, device-resident, no host synchronisation.  imgs_dev is

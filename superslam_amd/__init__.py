@@ -20,10 +20,12 @@ from .pool import DescriptorPool, DeviceDescriptors  # noqa: F401
 from .superpoint import Features, SuperPoint  # noqa: F401
 from .window_smoother import WindowSmoother, smooth_batch  # noqa: F401
 from .fast import FastDetector, fast_detect, fast_params, fast_score  # noqa: F401
+from .brief import BRIEF_STATUS, HammingMatcher, brief_describe, brief_describe_batch, brief_pattern  # noqa: F401
 
 __all__ = ["SuperPoint", "LightGlue", "LightGlueEngine", "MatchResult", "Features", "DescriptorPool",
            "DeviceDescriptors", "FrontEndBatch", "process_stereo", "stereo_associate_batch", "EigenPlaces", "NNMatcher", "PlaceIndex", "PoseSolver",
            "track_batch", "RansacVerifier", "verify_batch", "WindowSmoother", "smooth_batch", "PoseGraph", "close_loops_batch", "Rectifier", "build_maps",
            "rgbd_associate_batch", "stereo_refine_batch", "stereo_refine", "stereo_search_batch", "stereo_search",
            "patch_track_batch", "patch_track", "patch_track_stereo_batch", "ImagePyramid", "pyr_down", "patch_track_pyramid_batch",
-           "patch_track_pyramid", "pyr_track_params", "Clahe", "clahe", "FastDetector", "fast_detect", "fast_score", "fast_params"]
+           "patch_track_pyramid", "pyr_track_params", "Clahe", "clahe", "FastDetector", "fast_detect", "fast_score", "fast_params",
+           "brief_describe_batch", "brief_describe", "brief_pattern", "BRIEF_STATUS", "HammingMatcher"]

@@ -291,6 +291,18 @@ _SIGS = {
     "sship_fast_score_batch_device": (ip, [vp, C.c_longlong, ip, ip, ip, ip, vp, C.c_longlong, ip, vp]),
     "sship_fast_bench": (ip, [vp, ip, C.POINTER(fp)]),
     "sship_fast_bench_kernels": (ip, [vp, ip, ip, C.POINTER(fp)]),
+    "sship_brief_pattern": (ip, [ip, vp]),
+    "sship_brief_describe_batch_device": (ip, [vp, C.c_longlong, ip, ip, ip, ip, vp, vp, ip, ip, ip, vp, vp, vp, vp]),
+    "sship_brief_describe_host": (ip, [vp, ip, ip, ip, vp, ip, ip, ip, vp, vp, vp]),
+    "sship_hm_create": (ip, [ip, ip, C.POINTER(vp)]),
+    "sship_hm_destroy": (None, [vp]),
+    "sship_hm_set_params": (ip, [vp, ip, ip, ip]),
+    "sship_hm_get_params": (ip, [vp, C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip), C.POINTER(ip)]),
+    "sship_hm_set_gate": (ip, [vp, ip, fp, fp, fp, fp]),
+    "sship_hm_get_gate": (ip, [vp, C.POINTER(ip), C.POINTER(fp), C.POINTER(fp), C.POINTER(fp), C.POINTER(fp)]),
+    "sship_hm_match_batch_device": (ip, [vp, vp, vp, vp, vp, ip, ip, ip, ip, ip, vp, vp, vp, vp]),
+    "sship_hm_match_host": (ip, [vp, ip, vp, vp, vp, ip, ip, vp, vp, vp, ip, vp, vp, vp]),
+    "sship_hm_bench": (ip, [vp, ip, C.POINTER(fp)]),
     "sship_desc_to_host": (ip, [vp, ip, ip, vp]),
     "sship_frontend_batch_device": (ip, [vp, vp, vp, ip, ip, ip, vp, vp, vp, vp, vp, vp]),
     "sship_sp_bench_layer": (ip, [vp, ip, ip, ip, ip, ip, C.POINTER(fp), C.POINTER(C.c_double)]),

@@ -16,6 +16,7 @@
 
 #include "../../include/sship.h"
 #include "../../include/superslam_hip/place_recognizer.hpp"
+#include "brief_pattern.h"
 #include "kernels.h"
 #include "stage_layout.h"
 
@@ -5022,6 +5023,193 @@ extern "C" int sship_fast_bench_kernels(sship_fast* fast, int kernels, int iters
   return bench_loop(fast->stream, iters, [&]() { return fast_launch(fast, kernels, fast->stream); }, avg_ms);
 }
 extern "C" int sship_fast_bench(sship_fast* fast, int iters, float* avg_ms) { return sship_fast_bench_kernels(fast, 7, iters, avg_ms); }
+
+// ====================================================================================================
+// Steered BRIEF descriptors and the Hamming matcher (sship_brief_*, sship_hm_*; the rules are in include/sship.h)
+// ====================================================================================================
+extern "C" int sship_brief_pattern(int bin, int8_t* out) {
+  if (!out) return fail(SSHIP_ERR_INVALID, "brief_pattern: null argument");
+  if (bin < 0 || bin >= kBriefBins) return fail(SSHIP_ERR_INVALID, "brief_pattern: bin must be in [0, 31]");
+  memcpy(out, brief_table_host().v[bin], (size_t)kBriefBits * 4);
+  return SSHIP_OK;
+}
+static int brief_check(int stride, int h, int w, int mode, const char* who) {
+  if (h < 2 * kBriefReach + 1 || w < 2 * kBriefReach + 1 || h > 16384 || w > 16384)
+    return fail(SSHIP_ERR_INVALID, std::string(who) + ": h and w must be in [33, 16384]");
+  if (stride < w) return fail(SSHIP_ERR_INVALID, std::string(who) + ": stride (bytes) must be >= w");
+  if (mode != SSHIP_BRIEF_STEERED && mode != SSHIP_BRIEF_UPRIGHT) return fail(SSHIP_ERR_INVALID, std::string(who) + ": mode must be 0 (steered) or 1 (upright)");
+  return SSHIP_OK;
+}
+extern "C" int sship_brief_describe_batch_device(const uint8_t* imgs, long long image_stride, int stride, int images, int h, int w,
+                                                 const float* kp, const int* n, int unit_stride, int max_keypoints, int mode, uint32_t* desc,
+                                                 uint8_t* status, uint8_t* bin, void* stream) {
+  const char* who = "brief_describe_batch_device";
+  if (!imgs || !kp || !n || !desc) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  if (images < 1 || images > 65535) return fail(SSHIP_ERR_INVALID, std::string(who) + ": images must be in [1, 65535]");
+  if (max_keypoints < 1 || max_keypoints > kMaxKp) return fail(SSHIP_ERR_INVALID, std::string(who) + ": max_keypoints must be in [1, 4096]");
+  if (unit_stride != 1 && unit_stride != 2) return fail(SSHIP_ERR_INVALID, std::string(who) + ": unit_stride must be 1 or 2");
+  if (image_stride < 0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": image_stride (bytes) must be >= 0");
+  if (int rc = brief_check(stride, h, w, mode, who)) return rc;
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  launch_brief_describe(imgs, image_stride, stride, images, h, w, kp, n, unit_stride, max_keypoints, mode, desc, status, bin, s);
+  SSHIP_HIP_CHECK(hipGetLastError());
+  g_timer.mark("brief_describe", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_brief_describe_host(const uint8_t* img, int stride, int h, int w, const float* keypoints, int kp_stride, int n, int mode,
+                                         uint32_t* desc, uint8_t* status, uint8_t* bin) {
+  const char* who = "brief_describe_host";
+  if (!img) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  if (n < 0 || n > kMaxKp || kp_stride < 2) return fail(SSHIP_ERR_INVALID, std::string(who) + ": n must be in [0, 4096] and kp_stride >= 2");
+  if (int rc = brief_check(stride, h, w, mode, who)) return rc;
+  if (n == 0) return SSHIP_OK;
+  if (!keypoints || !desc) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  const BriefStage st = brief_stage(h, w, n);
+  std::vector<char> tail(st.tail_bytes, 0);
+  brief_pack(tail.data(), st, keypoints, kp_stride, n);
+  StageArena a;
+  SSHIP_HIP_CHECK(a.create(st.in_bytes, st.out_bytes, false));
+  SSHIP_HIP_CHECK(hipMemcpy2D(a.dev<uint8_t>(st.img), (size_t)w, img, (size_t)stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice));
+  SSHIP_HIP_CHECK(hipMemcpy(a.dev<char>(st.n), tail.data(), st.tail_bytes, hipMemcpyHostToDevice));
+  if (int rc = sship_brief_describe_batch_device(a.dev<uint8_t>(st.img), 0, w, 1, h, w, a.dev<float>(st.kp), a.dev<int>(st.n), 1, n, mode,
+                                                 a.dev<uint32_t>(a.out + st.desc), a.dev<uint8_t>(a.out + st.status),
+                                                 a.dev<uint8_t>(a.out + st.bin), nullptr)) return rc;
+  std::vector<char> back(st.out_bytes);
+  SSHIP_HIP_CHECK(hipMemcpy(back.data(), a.dev<char>(a.out), st.out_bytes, hipMemcpyDeviceToHost));   // blocking, on the NULL stream: after the launch
+  brief_unpack(back.data(), st, n, desc, status, bin);
+  return SSHIP_OK;
+}
+
+struct sship_hm {
+  int max_kp = 0, max_pairs = 0;
+  int max_distance = 0, ratio_percent = 0, mutual = 1;
+  int gate_on = 0;                                              // sship_nn's gate: (dx_lo, dx_hi, dy_lo, dy_hi)
+  float gate[4] = {-INFINITY, INFINITY, -INFINITY, INFINITY};
+  hipStream_t stream = nullptr;
+  DevBuf ws;
+  StageArena one;   // sship_hm_match_host: one staged pair and its results (hm_stage)
+  // the last call's launch arguments (sship_hm_bench re-runs them; the caller keeps a batch call's buffers alive until then)
+  struct Last { const int* n = nullptr; const uint32_t* desc = nullptr; const uint8_t* status = nullptr; const float* kp = nullptr;
+                int first0 = 0, step0 = 0, first1 = 0, step1 = 0, items = 0; int32_t* m0 = nullptr; int32_t* dist0 = nullptr; float* ms0 = nullptr; } last;
+};
+extern "C" int sship_hm_create(int max_kp, int max_pairs, sship_hm** out) {
+  if (!out) return fail(SSHIP_ERR_INVALID, "hm_create: null argument");
+  *out = nullptr;
+  if (max_kp < 1 || max_kp > kMaxKp) return fail(SSHIP_ERR_INVALID, "hm_create: max_keypoints must be in [1, 4096]");
+  if (max_pairs < 1 || max_pairs > 65535) return fail(SSHIP_ERR_INVALID, "hm_create: max_pairs must be in [1, 65535]");
+  bind_thread();
+  if (int rc = require_device()) return rc;
+  std::unique_ptr<sship_hm, void (*)(sship_hm*)> hm(new sship_hm(), sship_hm_destroy);
+  hm->max_kp = max_kp; hm->max_pairs = max_pairs;
+  SSHIP_HIP_CHECK(hm->ws.ensure(hm_workspace_ints(max_kp, max_pairs) * 4));
+  const HmStage st = hm_stage(max_kp);
+  SSHIP_HIP_CHECK(hm->one.create(st.in_bytes, st.out_bytes));
+  SSHIP_HIP_CHECK(hipMemset(hm->one.dev<char>(0), 0, st.in_bytes));   // rows never staged are zero
+  SSHIP_HIP_CHECK(hipStreamCreateWithFlags(&hm->stream, hipStreamDefault));
+  *out = hm.release();
+  return SSHIP_OK;
+}
+extern "C" void sship_hm_destroy(sship_hm* hm) { destroy_handle(hm); }
+extern "C" int sship_hm_set_params(sship_hm* hm, int max_distance, int ratio_percent, int mutual_check) {
+  if (!hm) return fail(SSHIP_ERR_INVALID, "hm_set_params: null handle");
+  if (max_distance < 0 || max_distance > 256) return fail(SSHIP_ERR_INVALID, "hm_set_params: max_distance must be in [0, 256] (0: off)");
+  if (ratio_percent < 0 || ratio_percent > 100) return fail(SSHIP_ERR_INVALID, "hm_set_params: ratio_percent must be in [0, 100] (0: off)");
+  hm->max_distance = max_distance; hm->ratio_percent = ratio_percent; hm->mutual = mutual_check ? 1 : 0;
+  return SSHIP_OK;
+}
+extern "C" int sship_hm_get_params(const sship_hm* hm, int* max_distance, int* ratio_percent, int* mutual_check, int* max_keypoints, int* max_pairs) {
+  if (!hm) return fail(SSHIP_ERR_INVALID, "hm_get_params: null handle");
+  if (max_distance) *max_distance = hm->max_distance;
+  if (ratio_percent) *ratio_percent = hm->ratio_percent;
+  if (mutual_check) *mutual_check = hm->mutual;
+  if (max_keypoints) *max_keypoints = hm->max_kp;
+  if (max_pairs) *max_pairs = hm->max_pairs;
+  return SSHIP_OK;
+}
+extern "C" int sship_hm_set_gate(sship_hm* hm, int enabled, float dx_lo, float dx_hi, float dy_lo, float dy_hi) {
+  if (!hm) return fail(SSHIP_ERR_INVALID, "hm_set_gate: null handle");
+  if (std::isnan(dx_lo) || std::isnan(dx_hi) || std::isnan(dy_lo) || std::isnan(dy_hi)) return fail(SSHIP_ERR_INVALID, "hm_set_gate: a bound is NaN");
+  if (dx_lo > dx_hi || dy_lo > dy_hi) return fail(SSHIP_ERR_INVALID, "hm_set_gate: lo > hi");
+  hm->gate_on = enabled ? 1 : 0;
+  hm->gate[0] = dx_lo; hm->gate[1] = dx_hi; hm->gate[2] = dy_lo; hm->gate[3] = dy_hi;
+  return SSHIP_OK;
+}
+extern "C" int sship_hm_get_gate(const sship_hm* hm, int* enabled, float* dx_lo, float* dx_hi, float* dy_lo, float* dy_hi) {
+  if (!hm) return fail(SSHIP_ERR_INVALID, "hm_get_gate: null handle");
+  if (enabled) *enabled = hm->gate_on;
+  if (dx_lo) *dx_lo = hm->gate[0];
+  if (dx_hi) *dx_hi = hm->gate[1];
+  if (dy_lo) *dy_lo = hm->gate[2];
+  if (dy_hi) *dy_hi = hm->gate[3];
+  return SSHIP_OK;
+}
+// kp == nullptr: the ungated launches; otherwise the gated ones with the handle's window
+static hipError_t hm_run(const sship_hm* hm, const sship_hm::Last& l, hipStream_t s) {
+  HmK c{hm->max_kp, hm->max_distance, hm->ratio_percent, hm->mutual, l.kp ? 1 : 0, {hm->gate[0], hm->gate[1], hm->gate[2], hm->gate[3]},
+        l.first0, l.step0, l.first1, l.step1};
+  launch_hm_match(l.n, l.desc, l.status, l.kp, c, l.items, hm->ws.as<int>(), l.m0, l.dist0, l.ms0, s);
+  return hipGetLastError();
+}
+extern "C" int sship_hm_match_batch_device(sship_hm* hm, const int* n, const uint32_t* desc, const uint8_t* status, const float* kp, int first0,
+                                           int step0, int first1, int step1, int pairs, int32_t* m0, int32_t* dist0, float* ms0, void* stream) {
+  const char* who = "hm_match_batch_device";
+  if (!hm || !n || !desc || !m0 || !dist0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  if (pairs < 1 || pairs > hm->max_pairs) return fail(SSHIP_ERR_INVALID, std::string(who) + ": pairs must be in [1, max_pairs]");
+  if (first0 < 0 || step0 < 0 || first1 < 0 || step1 < 0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": firsts and steps must be >= 0");
+  if (reinterpret_cast<uintptr_t>(desc) % 16 != 0) return fail(SSHIP_ERR_INVALID, std::string(who) + ": desc_dev must be 16-byte aligned");
+  if (hm->gate_on && !kp) return fail(SSHIP_ERR_INVALID, std::string(who) + ": the gate is enabled and kp_dev is NULL");
+  bind_thread();
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  g_timer.begin_if_idle(s);
+  hm->last = {n, desc, status, hm->gate_on ? kp : nullptr, first0, step0, first1, step1, pairs, m0, dist0, ms0};
+  SSHIP_HIP_CHECK(hm_run(hm, hm->last, s));
+  g_timer.mark(hm->gate_on ? "hm_match_gated" : "hm_match", s);
+  return SSHIP_OK;
+}
+extern "C" int sship_hm_match_host(sship_hm* hm, int n0, const uint32_t* desc0, const uint8_t* status0, const float* kp0, int kp_stride0, int n1,
+                                   const uint32_t* desc1, const uint8_t* status1, const float* kp1, int kp_stride1, int32_t* matches0,
+                                   int32_t* dist0, float* mscores0) {
+  const char* who = "hm_match_host";
+  if (!hm) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null handle");
+  if (n0 < 0 || n1 < 0 || n0 > hm->max_kp || n1 > hm->max_kp) return fail(SSHIP_ERR_INVALID, std::string(who) + ": n0 and n1 must be in [0, max_keypoints]");
+  if ((n0 && (!desc0 || !matches0 || !dist0)) || (n1 && !desc1)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": null argument");
+  if (hm->gate_on) {
+    if ((n0 && !kp0) || (n1 && !kp1)) return fail(SSHIP_ERR_INVALID, std::string(who) + ": the gate is enabled and a keypoint pointer is NULL");
+    if (kp_stride0 < 2 || kp_stride1 < 2) return fail(SSHIP_ERR_INVALID, std::string(who) + ": kp_stride must be >= 2");
+  }
+  if (n0 == 0) return SSHIP_OK;
+  bind_thread();
+  hipStream_t s = hm->stream;
+  const StageArena& a = hm->one;
+  const HmStage st = hm_stage(hm->max_kp);
+  hm_pack(a.host<char>(0), st, n0, desc0, status0, n1, desc1, status1);
+  SSHIP_HIP_CHECK(a.upload(st.lens, 8, s));
+  SSHIP_HIP_CHECK(a.upload(st.desc, (size_t)n0 * 32, s));
+  SSHIP_HIP_CHECK(a.upload(st.status, (size_t)n0, s));
+  if (n1) { SSHIP_HIP_CHECK(a.upload(st.desc1, (size_t)n1 * 32, s)); SSHIP_HIP_CHECK(a.upload(st.status1, (size_t)n1, s)); }
+  if (hm->gate_on) {
+    hm_pack_kp(a.host<char>(0), st, kp0, kp_stride0, n0, kp1, kp_stride1, n1);
+    SSHIP_HIP_CHECK(a.upload(st.kp, (size_t)n0 * 12, s));
+    if (n1) SSHIP_HIP_CHECK(a.upload(st.kp1, (size_t)n1 * 12, s));
+  }
+  // the arena as two units of one array each: set 0 is unit 0, set 1 is unit 1
+  if (int rc = sship_hm_match_batch_device(hm, a.dev<int>(st.lens), a.dev<uint32_t>(st.desc), a.dev<uint8_t>(st.status),
+                                           hm->gate_on ? a.dev<float>(st.kp) : nullptr, 0, 0, 1, 0, 1, a.dev<int32_t>(a.out + st.m0),
+                                           a.dev<int32_t>(a.out + st.dist0), a.dev<float>(a.out + st.ms0), s)) return rc;
+  SSHIP_HIP_CHECK(a.download(a.out + st.m0, (size_t)n0 * 4, s));
+  SSHIP_HIP_CHECK(a.download(a.out + st.dist0, (size_t)n0 * 4, s));
+  SSHIP_HIP_CHECK(a.download(a.out + st.ms0, (size_t)n0 * 4, s));
+  SSHIP_HIP_CHECK(hipStreamSynchronize(s));
+  hm_unpack(a.host<char>(a.out), st, n0, matches0, dist0, mscores0);
+  return SSHIP_OK;
+}
+// Measurement hook (include/sship.h): the last call's two launches re-run `iters` times on the handle's stream
+extern "C" int sship_hm_bench(sship_hm* hm, int iters, float* avg_ms) { return bench_last(hm, iters, avg_ms, "hm_bench", "match", hm_run); }
 
 // ====================================================================================================
 // fused front-end step: SuperPoint(batch 2P) + select + gather + LightGlue(P)

@@ -418,4 +418,19 @@ void launch_fast_detect(const uint8_t* imgs, long long image_stride, long long s
 void launch_fast_merge(const float* keep, const int* keep_n, int unit_stride, int max_kp, const float* new_kp, const int* n_new, int max_new,
                        int target, float* kp_out, int* n_out, int* carry0, int images, hipStream_t s);
 
+// Steered BRIEF descriptors and the Hamming matcher (brief_kernels.hip; the rules are in include/sship.h "Binary descriptors")
+struct BriefTable;                               // csrc/brief_pattern.h
+const BriefTable& brief_table_host();            // the object the device table is a copy of
+constexpr int kBriefWaves = 4;                   // keypoints (one wave each) per workgroup of k_brief_describe
+// image p reads unit p * unit_stride of kp [units, max_kp, 3] and lens [units]; status and bin may be null
+void launch_brief_describe(const uint8_t* imgs, long long image_stride, int stride, int images, int h, int w, const float* kp, const int* lens,
+                           int unit_stride, int max_kp, int mode, uint32_t* desc, uint8_t* status, uint8_t* bin, hipStream_t s);
+constexpr int kHmRows = 128;                     // rows of one set per workgroup of k_hm_best, one per lane
+constexpr int kHmTile = 64;                      // rows of the other set per LDS tile
+struct HmK { int max_kp, max_distance, ratio_percent, mutual, gate_on; float gate[4]; int first0, step0, first1, step1; };
+inline size_t hm_workspace_ints(int max_kp, int max_pairs) { return (size_t)max_pairs * 3 * max_kp; }   // fwd | bwd per pair, then e1
+// status may be null; kp is read only with c.gate_on; mscores0 may be null.  Two launches: k_hm_best, k_hm_final.
+void launch_hm_match(const int* lens, const uint32_t* desc, const uint8_t* status, const float* kp, const HmK& c, int pairs, int* ws,
+                     int* matches0, int* dist0, float* mscores0, hipStream_t s);
+
 }  // namespace sship

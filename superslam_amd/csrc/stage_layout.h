@@ -1,5 +1,6 @@
 // Staging layouts of the single-item entries (sship_*_solve_host, sship_nn_match_*, sship_index_query_*, and the image-pair entries
-// sship_stereo_refine_host, sship_stereo_search_host, sship_patch_track_host, sship_patch_track_pyramid_host): where each field of one staged
+// sship_stereo_refine_host, sship_stereo_search_host, sship_patch_track_host, sship_patch_track_pyramid_host, and the one-image / one-pair
+// entries sship_fast_detect_host, sship_brief_describe_host, sship_hm_match_host): where each field of one staged
 // item lies in the handle's (or, for an image pair, the call's) arena, and the host-side pack / unpack of that block.  Plain C++17, no HIP: api.hip includes it, and
 // tests/cpp/test_stage_layout.cc builds it alone (also under the host sanitizers).  A block has an input region and an output region; each
 // is contiguous, so one copy covers it, and every slot starts on a multiple of kStageAlign (what a hipMalloc of its own would give).
@@ -239,6 +240,70 @@ inline void fast_unpack(const char* out, const FastStage& st, float* kp_out, int
   memcpy(n_out, out + st.counts, 4);
   if (n_candidates) memcpy(n_candidates, out + st.counts + 4, 4);
   if (carry0) memcpy(carry0, out + st.carry, st.rows * 4);
+}
+
+// ---- binary descriptors, one image: img [h][w] | n | kp [rows][3] -> desc [rows][8] u32 | status [rows] | bin [rows] ---------------------
+// rows = n (at least 1, so that no slot is empty); the image as for FAST; the host block mirrors the input region from `n` on.
+struct BriefStage { size_t img, n, kp, in_bytes, tail_bytes, desc, status, bin, out_bytes, rows; };
+inline BriefStage brief_stage(int h, int w, int n) {
+  StageLayout in, out;
+  BriefStage s;
+  s.rows = (size_t)(n > 0 ? n : 1);
+  s.img = in.add((size_t)h * w); s.n = in.add(4); s.kp = in.add(s.rows * 12); s.in_bytes = in.end;
+  s.tail_bytes = s.in_bytes - s.n;
+  s.desc = out.add(s.rows * 32); s.status = out.add(s.rows); s.bin = out.add(s.rows); s.out_bytes = out.end;
+  return s;
+}
+// the count, then (x, y, 0) rows out of the caller's kp_stride-strided ones (kp_stride >= 2)
+inline void brief_pack(char* tail, const BriefStage& st, const float* keypoints, int kp_stride, int n) {
+  const int32_t n32 = n;
+  memcpy(tail, &n32, 4);
+  char* rows = tail + (st.kp - st.n);
+  for (int i = 0; i < n; ++i) memcpy(rows + (size_t)i * 12, keypoints + (size_t)i * kp_stride, 8);
+}
+inline void brief_unpack(const char* out, const BriefStage& st, int n, uint32_t* desc, uint8_t* status, uint8_t* bin) {
+  const size_t m = (size_t)n;
+  if (!m) return;
+  memcpy(desc, out + st.desc, m * 32);
+  if (status) memcpy(status, out + st.status, m);
+  if (bin) memcpy(bin, out + st.bin, m);
+}
+
+// ---- Hamming matcher, one pair: lens [2] | desc [2][max_kp][8] u32 | status [2][max_kp] | kp [2][max_kp][3] -> matches0 | dist0 | mscores0 [max_kp]
+// `desc1` / `status1` / `kp1`: where the second set's rows start.  Only the rows in use are packed and copied.
+struct HmStage { size_t lens, desc, desc1, status, status1, kp, kp1, in_bytes, m0, dist0, ms0, out_bytes; };
+inline HmStage hm_stage(int max_kp) {
+  const size_t n = (size_t)max_kp;
+  StageLayout in, out;
+  HmStage s;
+  s.lens = in.add(8); s.desc = in.add(2 * n * 32); s.status = in.add(2 * n); s.kp = in.add(2 * n * 12); s.in_bytes = in.end;
+  s.desc1 = s.desc + n * 32; s.status1 = s.status + n; s.kp1 = s.kp + n * 12;
+  s.m0 = out.add(n * 4); s.dist0 = out.add(n * 4); s.ms0 = out.add(n * 4); s.out_bytes = out.end;
+  return s;
+}
+// a NULL status array means "every row OK" (the value 1)
+inline void hm_pack(char* in, const HmStage& st, int n0, const uint32_t* desc0, const uint8_t* status0, int n1, const uint32_t* desc1,
+                    const uint8_t* status1) {
+  const int32_t lens[2] = {n0, n1};
+  memcpy(in + st.lens, lens, 8);
+  if (n0) memcpy(in + st.desc, desc0, (size_t)n0 * 32);
+  if (n1) memcpy(in + st.desc1, desc1, (size_t)n1 * 32);
+  if (n0) { if (status0) memcpy(in + st.status, status0, (size_t)n0); else memset(in + st.status, 1, (size_t)n0); }
+  if (n1) { if (status1) memcpy(in + st.status1, status1, (size_t)n1); else memset(in + st.status1, 1, (size_t)n1); }
+}
+// the gate's keypoints as (x, y, 0) rows out of the caller's strided ones
+inline void hm_pack_kp(char* in, const HmStage& st, const float* kp0, int st0, int n0, const float* kp1, int st1, int n1) {
+  char* h0 = in + st.kp;
+  char* h1 = in + st.kp1;
+  const float zero = 0.f;
+  for (int i = 0; i < n0; ++i) { memcpy(h0 + (size_t)i * 12, kp0 + (size_t)i * st0, 8); memcpy(h0 + (size_t)i * 12 + 8, &zero, 4); }
+  for (int i = 0; i < n1; ++i) { memcpy(h1 + (size_t)i * 12, kp1 + (size_t)i * st1, 8); memcpy(h1 + (size_t)i * 12 + 8, &zero, 4); }
+}
+inline void hm_unpack(const char* out, const HmStage& st, int n0, int32_t* matches0, int32_t* dist0, float* mscores0) {
+  if (!n0) return;
+  memcpy(matches0, out + st.m0, (size_t)n0 * 4);
+  memcpy(dist0, out + st.dist0, (size_t)n0 * 4);
+  if (mscores0) memcpy(mscores0, out + st.ms0, (size_t)n0 * 4);
 }
 
 }  // namespace sship
