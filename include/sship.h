@@ -153,7 +153,10 @@ int sship_nms(const float* scores_dev, int batch, int h, int w, int radius, floa
 /* src/SuperPoint.cc:696-719 on one device score map: strict `score > thr` (thr is a double) inside the
  * border, descending (score, h, w) order, first max_kp; kp (x = w*input_w/score_w, y = h*input_h/score_h,
  * score) triples, cells = min(h/8, desc_h-1), min(w/8, desc_w-1).  All outputs are device arrays
- * ([3*max_kp] f32, [max_kp] i32, [max_kp] i32, [1] i32); n_candidates_dev may be NULL. */
+ * ([3*max_kp] f32, [max_kp] i32, [max_kp] i32, [1] i32); n_candidates_dev may be NULL.
+ * Unlike the other entries that take a stream, this stage and its balanced twin below are NOT asynchronous: they own no handle, so the
+ * candidate list is allocated per call, the launches go to `stream` in order, and the call returns after synchronising `stream` (the
+ * scratch dies with the call).  They are parity-test stages; an extractor's own selection (sship_sp_extract_batch_device) is asynchronous. */
 int sship_select_topk(const float* scores_dev, int score_h, int score_w, int input_h, int input_w,
                       double thr, int border, int max_kp, int desc_h, int desc_w, float* kp_xys_dev,
                       int* cell_h_dev, int* cell_w_dev, int* n_dev, int* n_candidates_dev, void* stream);
